@@ -15,9 +15,15 @@ One *step* = one SLSQP major iteration's worth of callback work at a fixed point
 already resident in HBM: F(x0) plus the n forward-difference columns of
 [cost | c_eq | c_ineq], left in HBM as the transposed Jacobian (n x m, float64).  The
 reference spends 3n+2 Python callback evaluations on this, so
-``value`` = (3n+2) * K / elapsed  [NLP-callback evals/s], BASELINE.json's metric.  The timed region of
-exactly K steps (barrier + synchronize on both sides, MAX over ranks) is repeated ``--reps`` times (25) and
-the median repetition is reported, with min and max next to it.
+``value`` = (3n+2) * K / elapsed  [NLP-callback evals/s], BASELINE.json's metric, and ``ms_per_step`` =
+elapsed / K.  The timed region is exactly K steps (barrier + synchronize on both sides, MAX over ranks); with
+``--reps R`` it is repeated R times and the median repetition is reported, with min and max next to it.
+
+A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps and the line.
+``--dump-outputs DIR`` also writes what the last timed step computed (``DIR/F.npy``: F(x0), ``DIR/JT.npy``: the
+transposed Jacobian, float64; a seeded sample of its rows above 64 MB) - the inputs are the same from run to run,
+so two builds can be compared output for output.  ``--full`` adds everything else described below (and makes
+``--reps`` 25 unless it is given).
 
 Workload: BASELINE.json's target configuration, the 2-phase / 6-state / 3-control /
 80-node-per-phase polar ascent (``polar_tsto``, C3, n = 1442).  Output goes to registered persistent-zero
@@ -26,7 +32,7 @@ step what the previous one left).  With N > 1 ranks the columns are split in con
 total work is fixed) and every rank's replica is completed by ONE RCCL all-gather of the packed non-zeros per
 step (``opengoddard_amd/sharding.py``).
 
-Extra objects on the JSON line: ``roofline`` (the one launch that does evaluation + sweep, ``ogk_fused``,
+Extra objects on the JSON line of a ``--full`` run: ``roofline`` (the one launch that does evaluation + sweep, ``ogk_fused``,
 against the HBM roofline: algorithmic bytes 8*[(n+1)n + m n + sum N_i^2] per launch, duration from HIP events on
 the launch stream, also as a fraction of a fill peak measured in this run); ``cpu_baseline`` (the NumPy
 restatement of the reference path, serial, 1 core), ``cpu_baseline_all_cores`` (its column loop over every host
@@ -191,6 +197,31 @@ def fill_and_copy_peaks(torch, dev):
         out[label] = 5 * nbytes / (e0.elapsed_time(e1) * 1e-3) / 1e9
     del a, b
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def write_outputs(folder, F, JT):
+    """``--dump-outputs``: F(x0) (m) and the transposed Jacobian (n x m) of the last timed step as float64 ``.npy``
+    files, so that two builds can be compared output for output.  Above 64 MB together, JT.npy holds a fixed sample of
+    its rows (seeded; it depends on n and m only) in ascending order, and sample_rows.npy their indices."""
+    import numpy as np
+    import torch
+    os.makedirs(folder, exist_ok=True)
+    n, m = int(JT.shape[0]), int(JT.shape[1])
+    rows = None
+    if 8 * (n * m + m) > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * m) // (8 * (m + 1)))
+        rows = np.sort(np.random.default_rng(20261016).choice(n, size=min(n, keep), replace=False))
+        JT = JT.index_select(0, torch.as_tensor(rows, device=JT.device)) if torch.is_tensor(JT) else JT[rows]
+    out = {"F": F, "JT": JT}
+    for name, value in out.items():
+        value = value.detach().cpu().numpy() if torch.is_tensor(value) else np.asarray(value)
+        np.save(os.path.join(folder, name + ".npy"), np.ascontiguousarray(value, dtype=np.float64))
+    if rows is not None:
+        np.save(os.path.join(folder, "sample_rows.npy"), rows.astype(np.float64))
+    return sorted(out) + (["sample_rows"] if rows is not None else [])
 
 
 def sqp_first_qp_parity(eng, prob, lb, ub):
@@ -491,9 +522,11 @@ def single_process_bench(a):
                 _native.check(lib.og_multi_fd_sweep_enqueue(multi._multi, xp, hp), "og_multi_fd_sweep_enqueue")
             _native.check(lib.og_multi_synchronize(multi._multi), "og_multi_synchronize")
     else:
+        last = [None]
+
         def run(k):
             for _ in range(k):
-                single.sweep_persistent(x0, h)
+                last[0] = single.sweep_persistent(x0, h)
     run(a.warmup)
     times = []
     for _ in range(max(1, a.reps)):
@@ -502,9 +535,10 @@ def single_process_bench(a):
         times.append(time.perf_counter() - t0)
     times = np.sort(np.array(times))
     elapsed = float(np.median(times))
-    F1, J1 = single.sweep_stacked(x0, h)
-    FG, JG = (multi.sweep_persistent(x0, h) if G > 1 else (F1, J1))
-    equal = bool(np.array_equal(J1, JG) and np.array_equal(F1, FG))
+    if a.dump_outputs:
+        # (G > 1: the grouped step leaves its result on the devices; one more step of the same path hands it to the host)
+        F_out, JT_out = multi.sweep_persistent(x0, h) if G > 1 or last[0] is None else last[0]
+        write_outputs(a.dump_outputs, F_out, JT_out)
     result = {
         "metric": "NLP-callback evals/sec (cost+constr+FD-Jacobian)", "value": (3 * n + 2) * a.steps / elapsed,
         "unit": "callback evals/s", "n_gpus": G, "steps": a.steps, "warmup": a.warmup,
@@ -518,10 +552,14 @@ def single_process_bench(a):
             "n": n, "m_eq": single.m_eq, "m_ineq": single.m_ineq, "evals_per_step": 3 * n + 2,
             "parallelism": "fd-columns x%d from ONE process (og_multi_fd_sweep_enqueue; x and h uploaded per step; %s)" % (
                 G, "devices %r" % devices + (", " + ("ncclAllGather" if lib.og_comm_uses_rccl() else "peer copies") if G > 1 else ""))},
-        "self_check": {"multi_device_matrix_equals_single_device_bitwise": equal},
     }
-    assert equal, "the column-sharded matrix differs from the single-device one"
-    if a.sqp_iterations > 0 and n <= 3000:
+    if a.full:
+        F1, J1 = single.sweep_stacked(x0, h)
+        FG, JG = (multi.sweep_persistent(x0, h) if G > 1 else (F1, J1))
+        equal = bool(np.array_equal(J1, JG) and np.array_equal(F1, FG))
+        result["self_check"] = {"multi_device_matrix_equals_single_device_bitwise": equal}
+        assert equal, "the column-sharded matrix differs from the single-device one"
+    if a.full and a.sqp_iterations > 0 and n <= 3000:
         # the SQP leg on the sharded sweep: the QP core reads device d0's replica in place (sqp.DeviceJacobian) - and
         # walks the same iterates as on one device, bit for bit (the sharded matrix IS the single-device matrix)
         from opengoddard_amd import sqp
@@ -591,8 +629,16 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--reps", type=int, default=25,
-                    help="the timed region of --steps steps is repeated this often; the median repetition is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="the timed region of --steps steps is repeated this often; the median repetition is reported "
+                         "(default 1: exactly --steps timed steps; 25 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: roofline and kernel timings, self-checks, host API, hipGraph "
+                         "replay, CPU baselines, exact Jacobian, cold start, SQP and solve legs, the BASELINE "
+                         "configurations of N = 4 / 8 (the --quick / --no-* options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (F(x0): F.npy, the transposed "
+                         "Jacobian: JT.npy, float64; rows of a seeded sample when above 64 MB) into DIR")
     ap.add_argument("--workload", default="polar_tsto")
     ap.add_argument("--nodes", default=None,
                     help="comma-separated LGL node counts per phase (size studies; default: the "
@@ -606,7 +652,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise RCCL and run the all-gather even with one rank (plumbing test)")
-    ap.add_argument("--quick", action="store_true", help="only the timed region and the roofline (profiling runs)")
+    ap.add_argument("--quick", action="store_true",
+                    help="with --full: only the timed region and the roofline (profiling runs)")
     ap.add_argument("--no-cold-start", action="store_true", help="skip the forced rebuild of the workload's kernel module")
     ap.add_argument("--no-solve", action="store_true",
                     help="skip the solve leg (Problem.solve to exit mode 0 at C3 and C4 + the oracle's KKT check: ~45 s)")
@@ -617,6 +664,8 @@ def main():
     ap.add_argument("--single-process", action="store_true",
                     help="N > 1 from ONE process: og_comm_init + og_multi_fd_sweep_enqueue over the N devices (no launcher)")
     a = ap.parse_args()
+    if a.reps is None:
+        a.reps = 25 if a.full else 1
     if a.single_process:
         return single_process_bench(a)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -713,9 +762,32 @@ def main():
         step()
     times = timed_region()
     elapsed = float(np.median(times))
-    # the same steps without the exchange: how the column-sharded kernels alone scale
-    times_local = timed_region(gather=False) if collective else times
-    elapsed_local = float(np.median(times_local))
+    if a.dump_outputs and rank == 0:
+        last = sweeps[counter[0] % nbuf]                # the buffer the last timed step wrote (see step())
+        write_outputs(a.dump_outputs, last.F0, last.replica)
+    result = {
+        "metric": "NLP-callback evals/sec (cost+constr+FD-Jacobian)",
+        "value": (3 * n + 2) * a.steps / elapsed,
+        "unit": "callback evals/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "timed_region": {"repetitions": int(times.size), "steps_each": a.steps, "reported": "median",
+                         "ms_per_step_min": float(times[0]) / a.steps * 1e3,
+                         "ms_per_step_median": elapsed / a.steps * 1e3,
+                         "ms_per_step_max": float(times[-1]) / a.steps * 1e3},
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+        "config": {"workload": "%s: %d phases, %s states, %s controls, %s LGL nodes" % (
+            a.workload, len(prob.nodes), prob.number_of_states, prob.number_of_controls, prob.nodes),
+            "n": n, "m_eq": eng.m_eq, "m_ineq": eng.m_ineq,
+            "evals_per_step": 3 * n + 2,
+            "output_buffers": "%d registered persistent-zero replicas of %.1f MB in rotation" % (nbuf, replica_bytes / 1e6),
+            "parallelism": "fd-columns x%d%s" % (world, " + RCCL all-gather of the packed non-zeros (%d bytes per rank; %s)"
+                                                  % (sweeps[0].message_bytes, backend.direct_note) if collective else "")},
+    }
 
     # ---- who took part (VERDICT r4 #8e): every rank's device as torch sees it and - when the exchange is the direct
     # ncclAllGather of libogpsx.so - what RCCL itself reports about the communicator (ncclCommCount / UserRank / CuDevice)
@@ -739,6 +811,47 @@ def main():
         everyone = [None] * world
         dist.all_gather_object(everyone, mine)
         ranks_report = everyone
+
+    def finish(result):
+        """Who took part, the validity of an N > 1 line, the JSON line; then the process group is taken down."""
+        if ranks_report is not None:
+            result["ranks"] = ranks_report
+            counts = {r_.get("rccl_comm_ranks") for r_ in ranks_report}
+            result["rccl_ranks"] = counts.pop() if len(counts) == 1 else None
+            # PHYSICAL devices (host + uuid / PCI address), not (ordinal, pid) pairs: N ranks piled onto one GPU count as one
+            result.update(device_census(ranks_report))
+            result["message_bytes_per_rank"] = [r_.get("message_bytes") for r_ in ranks_report]
+        eng.close()
+        # The JSON line is the LAST thing on stdout.  RCCL prints its banner through C stdio, which a pipe buffers
+        # until exit: every rank flushes that first, then all ranks meet, then rank 0 prints.
+        try:
+            import ctypes
+            ctypes.CDLL(None).fflush(None)
+        except Exception:
+            pass
+        sys.stdout.flush()
+        if collective:
+            dist.barrier()
+        verdict = multi_gpu_verdict(result, world, same_device) if rank == 0 else None
+        if rank == 0:
+            if same_device:
+                result["dry_run"] = "OG_BENCH_SAME_DEVICE=1: every rank on device 0, gloo through host staging - plumbing only, measures nothing"
+            if verdict:
+                result["invalid"] = verdict
+            print(json.dumps(result), flush=True)
+        if collective:
+            dist.destroy_process_group()
+        if verdict:
+            sys.stderr.write("bench.py: this --gpus %d line is INVALID: %s\n" % (world, verdict))
+            return 3
+
+    # a plain run ends here: set-up, warm-up, the timed steps, their outputs and the line.  Everything below is --full.
+    if not a.full:
+        return finish(result)
+
+    # the same steps without the exchange: how the column-sharded kernels alone scale
+    times_local = timed_region(gather=False) if collective else times
+    elapsed_local = float(np.median(times_local))
 
     # ---- BASELINE.json quotes C4 on 4 GPUs and C5 on 8: with the driver's command (`--gpus N`, default workload) those
     # configurations get their own measurement beside the headline's - same step, same fences, fewer repetitions
@@ -878,30 +991,9 @@ def main():
     achieved_events = achieved
     if rocprof and world == 1:
         achieved = alg_bytes / (rocprof["average_us"] * 1e-6) / 1e9
-    result = {
-        "metric": "NLP-callback evals/sec (cost+constr+FD-Jacobian)",
-        "value": (3 * n + 2) * a.steps / elapsed,
-        "unit": "callback evals/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": elapsed / a.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "timed_region": {"repetitions": int(times.size), "steps_each": a.steps, "reported": "median",
-                         "ms_per_step_min": float(times[0]) / a.steps * 1e3,
-                         "ms_per_step_median": elapsed / a.steps * 1e3,
-                         "ms_per_step_max": float(times[-1]) / a.steps * 1e3},
+    result.update({
         "value_without_collective": (3 * n + 2) * a.steps / elapsed_local,
         "ms_per_step_without_collective": elapsed_local / a.steps * 1e3,
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "%s: %d phases, %s states, %s controls, %s LGL nodes" % (
-            a.workload, len(prob.nodes), prob.number_of_states, prob.number_of_controls, prob.nodes),
-            "n": n, "m_eq": eng.m_eq, "m_ineq": eng.m_ineq,
-            "evals_per_step": 3 * n + 2,
-            "output_buffers": "%d registered persistent-zero replicas of %.1f MB in rotation" % (nbuf, replica_bytes / 1e6),
-            "parallelism": "fd-columns x%d%s" % (world, " + RCCL all-gather of the packed non-zeros (%d bytes per rank; %s)"
-                                                  % (sweeps[0].message_bytes, backend.direct_note) if collective else "")},
         "roofline": {"bound": "hbm", "kernel": kernel, "achieved": achieved,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      # (above 1 the convention prices traffic this kernel does not have: no fraction is reported)
@@ -968,7 +1060,7 @@ def main():
                               "(bytes_actually_written_per_launch): the kernel is a latency chain, not a stream, so the "
                               "fraction can exceed 1 at C5's size - it prices the reference formulation's traffic, not this "
                               "kernel's; measured HBM traffic is `traffic`.")},
-    }
+    })
     if world == 1 and rank == 0 and not a.quick:
         # self-check after the timed loop: every rotated buffer holds exactly what a literal dense sweep
         # (every row re-evaluated for every column, OGPSX_SWEEP=dense) produces, bit for bit
@@ -1107,13 +1199,6 @@ def main():
                     result["solve"]["also"].append(bounded_c5_leg())
         except Exception as exc:                               # a failed leg must not lose the line
             result["solve"] = {"error": repr(exc)}
-    if ranks_report is not None:
-        result["ranks"] = ranks_report
-        counts = {r_.get("rccl_comm_ranks") for r_ in ranks_report}
-        result["rccl_ranks"] = counts.pop() if len(counts) == 1 else None
-        # PHYSICAL devices (host + uuid / PCI address), not (ordinal, pid) pairs: N ranks piled onto one GPU count as one
-        result.update(device_census(ranks_report))
-        result["message_bytes_per_rank"] = [r_.get("message_bytes") for r_ in ranks_report]
     if baseline_config is not None:
         result["baseline_config"] = baseline_config
     if collective:
@@ -1125,29 +1210,8 @@ def main():
             assert all(torch.equal(g, gathered[0]) for g in gathered), "replicas differ between ranks"
             assert all(torch.equal(sh.replica, sweeps[0].replica) for sh in sweeps)
             result["self_check"] = {"replicas_equal_across_ranks": True}
-    eng.close()
-    # The JSON line is the LAST thing on stdout.  RCCL prints its banner through C stdio, which a pipe buffers
-    # until exit: every rank flushes that first, then all ranks meet, then rank 0 prints.
-    try:
-        import ctypes
-        ctypes.CDLL(None).fflush(None)
-    except Exception:
-        pass
-    sys.stdout.flush()
-    if collective:
-        dist.barrier()
-    verdict = multi_gpu_verdict(result, world, same_device) if rank == 0 else None
-    if rank == 0:
-        if same_device:
-            result["dry_run"] = "OG_BENCH_SAME_DEVICE=1: every rank on device 0, gloo through host staging - plumbing only, measures nothing"
-        if verdict:
-            result["invalid"] = verdict
-        print(json.dumps(result), flush=True)
-    if collective:
-        dist.destroy_process_group()
-    if verdict:
-        sys.stderr.write("bench.py: this --gpus %d line is INVALID: %s\n" % (world, verdict))
-        return 3
+    return finish(result)
+
 
 if __name__ == "__main__":
     sys.exit(main() or 0)

@@ -172,6 +172,53 @@ def test_shipped_example_scripts_run_unmodified(tag, script, golden, lgl_golden,
     assert "struct OgGen" in codegen.emit_header(P)
 
 
+@pytest.mark.parametrize("tag,name", [("ex01", "brachistochrone"), ("ex04", "goddard"), ("ex05", "goddard_1knot"),
+                                      ("ex08", "polar_ssto"), ("ex09", "polar_tsto_shipped"),
+                                      ("ex10", "low_thrust_shipped")])
+def test_reauthored_examples_through_the_opengoddard_import_path(tag, name, golden, lgl_golden, oracle_engine,
+                                                                 monkeypatch):
+    """The same conformance as above without the reference's scripts: the examples this repository re-authors
+    (opengoddard_amd/problems), built on the ``OpenGoddard.optimize`` import path and started with ``prob.solve``, must
+    hand SciPy callables whose values and Jacobians equal the goldens captured from the reference's own example
+    scripts (``ex*.npz``) - bit for bit once the reference's LGL data is injected."""
+    from scipy import optimize as sciopt
+    from conftest import inject_reference_lgl
+    from OpenGoddard import optimize as api
+    from oracle import np_path
+    got = {}
+
+    class Stop(Exception):
+        pass
+
+    def fake_minimize(fun, x0, args=(), bounds=None, constraints=(), jac=None, **kw):
+        got.update(fun=fun, x0=np.array(x0), args=args, bounds=bounds, constraints=constraints, jac=jac)
+        raise Stop()
+
+    monkeypatch.setattr(sciopt, "minimize", fake_minimize)
+    prob, obj = problems.build(name, api=api)
+    with pytest.raises(Stop):
+        prob.solve(obj)
+    G = golden(tag)
+    assert got["args"][0] is prob and type(prob).__module__ == "opengoddard_amd.optimize"
+    lb, ub = np_path.bounds_arrays(prob)
+    assert np.array_equal(lb, G["lb"]) and np.array_equal(ub, G["ub"])
+    assert np.max(np.abs(np.clip(got["x0"], lb, ub) - G["x"][0])) <= 1e-13
+    inject_reference_lgl(prob, lgl_golden)
+    prob._engine.m_eq = None
+    m_eq = int(G["m_eq"])
+    for k in range(G["x"].shape[0]):
+        x, Fg = G["x"][k], G["F"][k]
+        vals = [got["fun"](x, *got["args"]), got["constraints"][0]["fun"](x, *got["args"]),
+                got["constraints"][1]["fun"](x, *got["args"])]
+        assert np.array_equal(np.concatenate([np.atleast_1d(v) for v in vals]), Fg)
+    if G["cols"].size == G["x"].shape[1]:                   # full Jacobians stored
+        x = G["x"][0]
+        Jeq = got["constraints"][0]["jac"](x, *got["args"])
+        Jin = got["constraints"][1]["jac"](x, *got["args"])
+        assert np.array_equal(Jeq, G["JT"][0].T[1:1 + m_eq])
+        assert np.array_equal(Jin, G["JT"][0].T[1 + m_eq:])
+
+
 @pytest.mark.parametrize("name,delimiter,tag", [("brachistochrone", ",", ""), ("polar_tsto_shipped", ",", ""),
                                                  ("polar_tsto_shipped", ";", "_semicolon")])
 def test_to_csv_writes_the_reference_bytes(name, delimiter, tag, lgl_golden, tmp_path, capsys):
@@ -211,9 +258,14 @@ def test_auto_falls_back_to_scipys_core_when_the_hip_core_cannot_take_the_proble
     import types
     from opengoddard_amd import sqp
     from oracle import np_path
+    try:                                              # torch without a GPU - on a machine with one as well
+        import torch
+        monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    except ImportError:
+        pass
     assert "16384" in sqp.prepare(types.SimpleNamespace(n=17000, m_eq=10))
     assert "null space" in sqp.prepare(types.SimpleNamespace(n=8000, m_eq=100))
-    reason = sqp.prepare(types.SimpleNamespace(n=300, m_eq=100))           # this container: torch without a GPU
+    reason = sqp.prepare(types.SimpleNamespace(n=300, m_eq=100))
     assert reason is not None and ("GPU" in reason or "torch" in reason)
 
     class Engine(np_path.NumpyEngine):                # an engine "auto" would give the HIP core (n >= AUTO_HIP_FROM)

@@ -192,9 +192,12 @@ def test_bench_launches_its_own_ranks_when_there_is_no_launcher(monkeypatch):
     script = cmd.index(os.path.join(ROOT, "bench.py"))
     assert cmd[script + 1:] == ["--gpus", "4", "--steps", "5", "--warmup", "1"]
     assert seen["env"].get("HSA_ENABLE_IPC_MODE_LEGACY") == "0" or "HSA_ENABLE_IPC_MODE_LEGACY" in os.environ
-    # under a launcher: no second launch (it fails later, for lack of a GPU here, not by launching again)
+    # under a launcher: no second launch (it fails later, for lack of a GPU - made so here, also on a machine with one -
+    # not by launching again)
     seen.clear()
     monkeypatch.setenv("WORLD_SIZE", "4")
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
     with pytest.raises(SystemExit):
         bench.main()
     assert not seen

@@ -7,9 +7,9 @@ rnd=${1:-r03}
 out=$R/gpurun_out/$rnd
 mkdir -p $out
 for w in polar_tsto goddard low_thrust launch4; do
-    timeout 900 python $R/bench.py --workload $w --cpu-seconds 6 2>/dev/null | tail -1 > $out/bench_$w.json
+    timeout 900 python $R/bench.py --full --workload $w --cpu-seconds 6 2>/dev/null | tail -1 > $out/bench_$w.json
 done
-timeout 900 python $R/bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $out/bench_driver_style.json
+timeout 900 python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $out/bench_driver_style.json
 $R/tools/solve_profiles.sh $rnd > /dev/null 2>&1
 $R/tools/sqp_kstats.sh polar_tsto 10 ${rnd}_sqp_polar_tsto > $out/sqp_kstats_10.txt 2>&1
 $R/tools/sqp_kstats.sh polar_tsto 150 ${rnd}_sqp_polar_tsto_150 > $out/sqp_kstats_150.txt 2>&1

@@ -6,7 +6,7 @@ w=${1:-polar_tsto}
 out=/tmp/exch_$w
 cd /tmp && export TMPDIR=/tmp
 MASTER_ADDR=127.0.0.1 MASTER_PORT=29541 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- \
-    python $R/bench.py --gpus 1 --workload $w --steps 200 --warmup 20 --reps 5 --force-collective --quick > $out.log 2>&1
+    python $R/bench.py --full --gpus 1 --workload $w --steps 200 --warmup 20 --reps 5 --force-collective --quick > $out.log 2>&1
 f=$(ls $out/*kernel_stats.csv 2>/dev/null | head -1)
 python - "$f" <<'PY'
 import csv,sys,re

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 w=$1; shift
 tag=$(echo "$w $*" | tr ' =' '__')
 out=/tmp/kstats_$tag
-( cd /tmp && export TMPDIR=/tmp && env "$@" timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python $R/bench.py --workload $w --steps 200 --warmup 20 --no-cpu-baseline > $out.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && env "$@" timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o b -- python $R/bench.py --full --workload $w --steps 200 --warmup 20 --no-cpu-baseline > $out.log 2>&1 )
 python - "$out" "$tag" <<'PY'
 import csv,sys,glob
 f=glob.glob(sys.argv[1]+"/*kernel_stats.csv")

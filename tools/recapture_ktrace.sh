@@ -11,7 +11,7 @@ Q="--quick --no-cpu-baseline --sqp-iterations 0"
 for i in $(seq $times); do
     rm -rf $out/ktrace_$w
     timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ktrace_$w -o b -- \
-        python $R/bench.py --workload $w --steps 200 --warmup 20 --reps ${REPS:-25} $Q > $out/ktrace_$w.log 2>&1
+        python $R/bench.py --full --workload $w --steps 200 --warmup 20 --reps ${REPS:-25} $Q > $out/ktrace_$w.log 2>&1
     python - $out/ktrace_$w <<'PY'
 import csv, glob, sys
 for r in csv.DictReader(open(glob.glob(sys.argv[1] + "/*kernel_stats.csv")[0])):

@@ -11,7 +11,7 @@ runh polar_tsto
 runh polar_tsto --maxiter 400
 runh low_thrust
 runh launch4 --max-restarts 1 --maxiter 7
-timeout 600 python $R/bench.py --steps 50 --warmup 5 --reps 3 --no-cpu-baseline --no-cold-start --sqp-reference-iterations 0 2>/dev/null | tail -1 | python -c "
+timeout 600 python $R/bench.py --full --steps 50 --warmup 5 --reps 3 --no-cpu-baseline --no-cold-start --sqp-reference-iterations 0 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); s=d.get('sqp') or {}
 print('bench sqp:', {k:s.get(k) for k in ('ms_per_major_iteration','qp_s','active_set_iterations','parity_checked','first_qp_step_error_rel','first_qp_active_set_changes')})" >> $out

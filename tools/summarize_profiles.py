@@ -17,7 +17,7 @@ dst = os.path.join(ROOT, "profiles")
 os.makedirs(dst, exist_ok=True)
 lines = ["# rocprofv3 summary, round %s (MI355X, gfx950)" % rnd, "",
          "Commands (run from /tmp with TMPDIR=/tmp, see tools/kstats.sh):",
-         "`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --workload W --steps 200 --warmup 20 "
+         "`rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --full --workload W --steps 200 --warmup 20 "
          "--reps 25 --quick --no-cpu-baseline --sqp-iterations 0` (tools/capture_profiles.sh)",
          "`rocprofv3 --pmc FETCH_SIZE -- ...` and `rocprofv3 --pmc WRITE_SIZE -- ...` (separate passes, 50 steps).",
          "A step is ONE `ogk_fused` launch into a registered persistent-zero buffer (all sizes); "
