@@ -104,9 +104,15 @@ int og_qp_set_active(og_qp_handle qp, const int32_t* ids, int32_t count);
  * shortens the bound (tests force the path with 1).  No reference counterpart. */
 int og_qp_recoveries(og_qp_handle qp, int32_t* count);
 
-/* Round 6.  Where the stack of constraint rows and the inverse of the active triangle fit the chip's LDS (up to 4096
- * rows, one wavefront each, 16 per compute unit: BASELINE.json's C3 and C4), the whole active-set loop of a
- * subproblem is ONE launch (k_rows_resident, csrc/ogsqp_resident.h) instead of two launches per change.
+/* Bound of this handle's inter-workgroup waits from the next solve on (polls; 1 makes every wait that is not answered
+ * at once give up); limit <= 0 restores the bound og_qp_create chose.  Tests force a lost wait on one subproblem and
+ * solve the next ones with the default bound on the same handle. */
+int og_qp_set_spin_limit(og_qp_handle qp, int32_t limit);
+
+/* Round 6.  Where the stack of constraint rows and the inverse of the active triangle fit the chip's LDS (up to 3840
+ * rows: one wavefront each, 15 per workgroup, at most 256 workgroups and no more than the device's compute units -
+ * BASELINE.json's C3 and C4), the whole active-set loop of a subproblem is ONE launch (k_rows_resident,
+ * csrc/ogsqp_resident.h) instead of two launches per change.
  * *launches = such launches so far, *changes = active-set changes they made (0 / 0: the two-launch form serves this
  * handle - rows too many or too long, or OGSQP_RESIDENT=0 in the environment).  No reference counterpart (SciPy's
  * lsq() is a scalar Fortran loop, scipy/optimize/_slsqp_py.py:427-432 -> slsqp_optmz.f). */

@@ -30,6 +30,7 @@ SIGNATURES = {
     "og_qp_get_active": (C.c_int, [C.c_void_p, _ip, C.c_int32, _ip]),
     "og_qp_set_active": (C.c_int, [C.c_void_p, _ip, C.c_int32]),
     "og_qp_recoveries": (C.c_int, [C.c_void_p, _ip]),
+    "og_qp_set_spin_limit": (C.c_int, [C.c_void_p, C.c_int32]),
     "og_qp_resident_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "og_qp_bfgs": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _ip]),
     "og_jt_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, _dp, _dp, C.c_void_p]),
@@ -153,6 +154,11 @@ class QpCore:
         count = C.c_int32(0)
         check(self._lib.og_qp_recoveries(self._handle, C.byref(count)), "og_qp_recoveries")
         return count.value
+
+    def set_spin_limit(self, limit=0):
+        """Bound of the inter-workgroup waits from the next solve on (1: a wait not answered at once gives up);
+        ``limit <= 0`` restores the handle's default."""
+        check(self._lib.og_qp_set_spin_limit(self._handle, int(limit)), "og_qp_set_spin_limit")
 
     def resident_stats(self):
         """(launches, active-set changes) of the one-launch active-set loop (``k_rows_resident``); (0, 0) when the

@@ -2397,9 +2397,11 @@ struct og_qp_s {
     GiPartial *price = nullptr, *ratio = nullptr;
     RowsDecision* rec = nullptr;
     bool resident = true;              // round 6: the active-set loop as ONE launch with every row of W and of the inverse in
-                                       // registers (k_rows_resident, ogsqp_resident.h) where they fit the chip - up to 4096
+                                       // registers (k_rows_resident, ogsqp_resident.h) where they fit the chip - up to 3840
                                        // rows of up to 1024 null-space coordinates: C3, C4; OGSQP_RESIDENT=0: the two-launch form
     unsigned long long* res_mail = nullptr;   // its mailbox (self-validating records) ...
+    size_t res_mail_bytes = 0;
+    int res_wg_alloc = 0;                     // ... sized for this many workgroups: no launch of more
     unsigned* res_seq = nullptr;              // ... and the exchange counters that go on counting from launch to launch
     int warm_pairs_hint = 4;           // two-launch pairs enqueued in front of it for the warm start's removals
     long resident_launches = 0, resident_changes = 0;
@@ -2437,6 +2439,7 @@ struct og_qp_s {
     hipEvent_t ev_join[2] = {nullptr, nullptr};
     int spin_limit = 1 << 19;          // bound of the inter-workgroup waits: polls of ~1.5 us each, i.e. about a second (2^25 - a
                                        // minute per lost wait - until round 5); OGSQP_SPIN_LIMIT: tests force a loss with 1
+    int spin_default = 1 << 19;        // ... as og_qp_create set it (og_qp_set_spin_limit changes it for a while)
     int recoveries = 0;                // subproblems re-run with the separate-launch forms after a wait gave up
     bool lq_ahead = true;              // OGSQP_LQ=16: panel and trailing update as separate launches
     int trsv_mode = 0;                 // OGSQP_TRSV: 0 one chained launch, 1 ("block") a launch per block, 2 ("single")
@@ -2762,11 +2765,16 @@ int og_qp_create(int32_t abi_version, int32_t device, int32_t n, int32_t m_eq, i
     A(&qp->d, n1); A(&qp->bm, n1); A(&qp->tvec, n1); A(&qp->rhs, qp->meq); A(&qp->lam, qp->meq); A(&qp->vz, n1);
     A(&qp->svec, n1); A(&qp->vvec, n1); A(&qp->coef, qp->m + 1); A(&qp->outn, n1);
     A(&qp->isact, mt); A(&qp->act, qc); A(&qp->flag, 4);
-    // the mailbox of the resident active-set launch (ogsqp_resident.h): sized for this handle's rows when they fit the chip
+    // the mailbox of the resident active-set launch (ogsqp_resident.h): sized for the grid of this handle's longest rows
+    // (the relaxed subproblem's), at most the RES_MAX_WG workgroups a launch may have - a plain subproblem has one row
+    // fewer and may fit that grid where the relaxed one does not; the solve launches no more workgroups than this (none
+    // where the inverse's rows are longer than a resident launch holds: qcap > RES_MAX_LEN)
     const size_t res_wg_cap = ((size_t)qp->mg + n1 + qc + RES_ROWS - 1) / RES_ROWS;
-    const size_t res_records = res_mail_records(res_wg_cap <= (size_t)RES_MAX_WG ? (int)res_wg_cap : 1, (int)qc);
+    qp->res_wg_alloc = qc <= (size_t)RES_MAX_LEN ? (int)std::min(res_wg_cap, (size_t)RES_MAX_WG) : 0;
+    const size_t res_records = res_mail_records(qp->res_wg_alloc, (int)qc);
+    qp->res_mail_bytes = 2 * res_records * sizeof(unsigned long long);
     A(&qp->res_mail, 2 * res_records); A(&qp->res_seq, 4);
-    if (!rc && (hipMemset(qp->res_mail, 0, 2 * res_records * sizeof(unsigned long long)) != hipSuccess ||
+    if (!rc && (hipMemset(qp->res_mail, 0, qp->res_mail_bytes) != hipSuccess ||
                 hipMemset(qp->res_seq, 0, 4 * sizeof(unsigned)) != hipSuccess))
         rc = fail(5, "og_qp_create: hipMemset failed");
     A(&qp->partials, ((size_t)qp->mg + n1) / GI_WAVES + 2); A(&qp->st, 1);
@@ -2890,6 +2898,7 @@ int og_qp_create(int32_t abi_version, int32_t device, int32_t n, int32_t m_eq, i
         if (beyond_fallback) qp->spin_limit = 1 << 25;
         const char* spin = getenv("OGSQP_SPIN_LIMIT");
         if (spin && atoi(spin) > 0) qp->spin_limit = atoi(spin);
+        qp->spin_default = qp->spin_limit;
         const char* wspread = getenv("OGSQP_WARM_SPREAD");
         qp->warm_spread = !(wspread && std::string(wspread) == "0");
         const char* warm = getenv("OGSQP_WARM");
@@ -3214,6 +3223,19 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
     ga.limit = 10 * (mt + nr) + 100;
     GiState hst;
     memset(&hst, 0, sizeof(hst));
+    // The attempt is given up (*lost = 1).  A resident launch of this attempt may have stopped half way: its workgroups
+    // published records under exchange numbers that were never written back to res_seq, and the next launch on the
+    // handle counts through the same numbers again and would take those records for its own.  The mailbox is zeroed
+    // first (valid numbers start at 1: a zeroed record matches none).
+    bool res_launched = false;
+    auto clear_mail = [&]() -> int {
+        if (res_launched) OG_HIP(hipMemsetAsync(qp->res_mail, 0, qp->res_mail_bytes, s));
+        return 0;
+    };
+    auto give_up = [&]() -> int {
+        *lost = 1;
+        return clear_mail();
+    };
     const bool rows_mode = qp->gi_mode == 0;
     if (rows_mode && nr > 0) {
         // ---- rotated coordinates, one pass over the rows per change (ogsqp_rows.h)
@@ -3287,7 +3309,8 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, qp->device);
         const int res_len = std::max(nr, qp->qcap);
         const int res_wg = (nrows + qp->qcap + RES_ROWS - 1) / RES_ROWS;
-        bool resident = qp->resident && !debug_stages() && res_len <= RES_MAX_LEN && res_wg <= std::min(RES_MAX_WG, cus) &&
+        // (res_wg_alloc <= RES_MAX_WG: the workgroups the mailbox was sized for)
+        bool resident = qp->resident && !debug_stages() && res_len <= RES_MAX_LEN && res_wg <= std::min(qp->res_wg_alloc, cus) &&
                         res_lds_bytes(nr, qp->qcap) <= LDS_LIMIT;
         if (resident) {
             ResArgs rs;
@@ -3307,20 +3330,25 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
                 }
                 warm_launched += pairs;
                 hipLaunchKernelGGL(k_rows_resident, dim3(res_wg), dim3(RES_THREADS), ldsr, s, rs);
+                res_launched = true;
                 ++qp->resident_launches;
                 OG_HIP(hipGetLastError());
                 OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
                 OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
                 OG_HIP(hipStreamSynchronize(s));
+                // the flags before the phase: workgroup 0 may have written back a phase >= 2 while another workgroup
+                // gave up a wait (or a wait gave up earlier in this attempt: the loop ran on garbage)
+                if (hflag[2] || hflag[3]) return give_up();
                 if (hst.phase >= 2) break;
-                if (hflag[2] || hflag[3] || hst.phase >= 0) {
-                    // a workgroup of the resident launch was not there to answer (or a wait gave up earlier in this
-                    // attempt): nothing was written back; the attempt is run again with the forms that wait for nothing
-                    *lost = 1;
-                    return 0;
+                if (hst.phase >= 0) {
+                    // a workgroup of the resident launch was not there to answer: nothing was written back; the attempt
+                    // is run again with the forms that wait for nothing
+                    return give_up();
                 }
-                if (warm_launched > (long)nwarm + 64)
+                if (warm_launched > (long)nwarm + 64) {
+                    OG_TRY(clear_mail());
                     return fail(8, "og_qp_solve_dev: the warm start's removals made no progress (internal error)");
+                }
                 pairs = std::min(128, std::max(4, 4 * pairs));
             }
             // next time: as many pairs as this warm start's removals took, and a few (a pair that has nothing to do costs
@@ -3357,10 +3385,7 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
                 // nothing, not an internal error)
                 OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
                 OG_HIP(hipStreamSynchronize(s));
-                if (hflag[2] || hflag[3]) {
-                    *lost = 1;
-                    return 0;
-                }
+                if (hflag[2] || hflag[3]) return give_up();
                 return fail(8, "og_qp_solve_dev: the active-set kernels made no progress (internal error)");
             }
             if (batch < 128) batch *= 2;
@@ -3449,10 +3474,7 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
 #endif
         if (habort) {
             OG_HIP(hipMemcpy(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost));
-            if (hflag[2] || hflag[3]) {              // (as above: the input of the loop came from a lost wait)
-                *lost = 1;
-                return 0;
-            }
+            if (hflag[2] || hflag[3]) return give_up();   // (as above: the input of the loop came from a lost wait)
             return fail(7, "og_qp_solve_dev: the cooperative active-set kernel lost a workgroup at a barrier");
         }
     } else if (rows_mode && nr > 0) {
@@ -3506,6 +3528,10 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
 #endif
     if (hst.dbg != 0) fprintf(stderr, "[ogsqp] internal check failed: code %d aux %d (q %d, p %d)\n", hst.dbg, hst.dbg2, hst.q, hst.p);
     if (hst.phase != 2) {
+        // (a phase that came from a lost wait is no verdict on the subproblem: the attempt is run again)
+        OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+        OG_HIP(hipStreamSynchronize(s));
+        if (hflag[2] || hflag[3]) return give_up();
         *status = hst.phase == 3 ? OG_QP_ITERATION_LIMIT : OG_QP_INCOMPATIBLE;
         return 0;
     }
@@ -3528,10 +3554,7 @@ static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, con
     // (the transposed chained solve for the multipliers ran after the first look at the flags)
     OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     OG_HIP(hipStreamSynchronize(s));
-    if (hflag[2] || hflag[3]) {
-        *lost = 1;
-        return 0;
-    }
+    if (hflag[2] || hflag[3]) return give_up();
     if (rows_mode && nr > 0) {
         // the rows active at this solution, in the numbering of og_qp_get_active: where the next subproblem starts
         std::vector<int> act((size_t)std::max(hst.q, 1));
@@ -3613,6 +3636,12 @@ int og_qp_solve_dev(og_qp_handle qp, const double* d_jt, int64_t ld, const doubl
 int og_qp_recoveries(og_qp_handle qp, int32_t* count) {
     if (!qp || !count) return fail(2, "og_qp_recoveries: null argument");
     *count = qp->recoveries;
+    return 0;
+}
+
+int og_qp_set_spin_limit(og_qp_handle qp, int32_t limit) {
+    if (!qp) return fail(2, "og_qp_set_spin_limit: null handle");
+    qp->spin_limit = limit > 0 ? limit : qp->spin_default;
     return 0;
 }
 

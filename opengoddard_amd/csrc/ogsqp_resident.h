@@ -44,7 +44,8 @@
 // k_rows_apply, which the host runs - in `only_warm` form: they return at once when there is nothing of that kind to
 // do - in front of this kernel.  A workgroup that is not resident never answers: waits are bounded, a wait that
 // gives up raises the sweep's `lost` flag, every workgroup leaves WITHOUT writing anything back (the state in memory
-// is the state the kernel started from) and the host goes on with the two-launch form.
+// is the state the kernel started from) and the host goes on with the two-launch form - after it has zeroed the
+// mailbox: the records published so far carry exchange numbers the next launch counts through again.
 
 constexpr int RES_THREADS = 1024;
 constexpr int RES_WAVES = RES_THREADS / 64;

@@ -19,6 +19,10 @@ accurate to about cond(T) x 5e-20 - seven or more digits beyond what a double so
 Only ``tests/`` and ``bench.py``'s parity check call this; it is the checker, never the thing measured.
 (No reference counterpart: SciPy's ``slsqp`` has no such check; ``scipy/optimize/_slsqp_py.py:427-432`` is the call
 whose result this referees.)
+
+:func:`certify` turns the refined solution into a certificate of one solver answer - step, multipliers and the active set
+it reports - that fails with the name of the check that broke; :func:`relaxed_subproblem` builds the data of the relaxed
+subproblem (n + 1 variables) the way ``include/ogsqp.h`` defines it.
 """
 from __future__ import annotations
 
@@ -99,3 +103,116 @@ def distances(Z, g, A, c, lo, hi, m_eq, active, steps, sweeps=6):
             "step_moved": [v / scale for v in history["step_moved"]],
             "min_multiplier_of_inequalities": float(lam[m_eq:].min()) if rows.shape[0] > m_eq else None}
     return out, d_star, info
+
+
+def relaxed_subproblem(Z, g, A, c, lo, hi, m_eq, rho):
+    """The relaxed subproblem of slsqp label 140-150 (``og_qp_solve_dev(augmented=1, rho)``) as plain data in n + 1
+    variables, in the form :func:`distances` and :func:`certify` take: the last column of ``A`` is
+    ``[-c_eq, max(-c_ineq, 0)]`` (``a_j d + c_j (1 - delta) = 0``, ``a_j d + c_j + max(-c_j, 0) delta >= 0``),
+    ``Z[n, n] = 1 / rho``, the relaxation variable delta bounded by [0, 1].  -> ``(Z, g, A, c, lo, hi)``."""
+    n = Z.shape[0]
+    Za = np.zeros((n + 1, n + 1))
+    Za[:n, :n] = Z
+    Za[n, n] = 1.0 / rho
+    extra = np.concatenate([-np.asarray(c[:m_eq], dtype=np.float64), np.maximum(-np.asarray(c[m_eq:], dtype=np.float64), 0.0)])
+    return (Za, np.append(g, 0.0), np.hstack([A, extra[:, None]]), np.asarray(c, dtype=np.float64),
+            np.append(lo, 0.0), np.append(hi, 1.0))
+
+
+class CertificateError(AssertionError):
+    """:func:`certify` refused an answer.  ``failed``: the names of the checks that broke ("status", "active set",
+    "referee", "step", "dual feasibility", "primal feasibility", "multipliers"); ``measured``: what was measured."""
+
+    def __init__(self, failed, measured, details):
+        self.failed, self.measured = list(failed), dict(measured)
+        super().__init__("certificate refused: " + "; ".join(details))
+
+
+def certify(Z, g, A, c, lo, hi, m_eq, status, d, mult, bound_mult, active, tol_d=1e-9, tol_mu=1e-7, tol_p=1e-7,
+            tol_conv=1e-13, sweeps=6):
+    """Certify one answer of a QP solver against the refined solution on the active set it reports.
+
+    Data as :func:`distances` takes it (``A``: the ``m_eq`` equality rows first; for the relaxed subproblem build it with
+    :func:`relaxed_subproblem`); ``status``, ``d``, ``mult`` (m), ``bound_mult`` (n) as ``og_qp_solve`` returns them
+    (``grad L = B d + g - A' mult - bound_mult``, ``bound_mult > 0`` where a lower bound is active, ``< 0`` an upper one:
+    ``include/ogsqp.h``); ``active`` in the numbering of ``og_qp_get_active``.  The checks, each relative to a scale:
+
+    * referee converged - the last two sweeps moved d* by at most ``tol_conv`` x max(1, |d*|_inf); otherwise the
+      certificate is void (the referee cannot vouch for anything);
+    * step - ``|d - d*|_inf <= tol_d`` x max(1, |d*|_inf);
+    * dual feasibility - every multiplier of an active inequality or bound in lambda* ``>= -tol_mu`` x max(1, |lambda*|_inf);
+    * primal feasibility - at d*, every general inequality and every finite bound holds within ``tol_p`` x max(1, |c|_inf);
+    * multipliers - ``mult`` and ``bound_mult`` equal lambda* in their slots (zero where nothing is active) within
+      ``tol_mu`` x max(1, |lambda*|_inf).
+
+    -> dict of the measured (relative) values; raises :class:`CertificateError` naming every check that broke."""
+    n, m = Z.shape[0], A.shape[0]
+    m_ineq = m - m_eq
+    d, mult, bound_mult = (np.asarray(v, dtype=np.float64) for v in (d, mult, bound_mult))
+    if status != 1:
+        raise CertificateError(["status"], {}, ["status: %d, not a solution (1)" % status])
+    if d.shape != (n,) or mult.shape != (m,) or bound_mult.shape != (n,):
+        raise ValueError("d, mult, bound_mult: expected %d, %d, %d entries, got %s, %s, %s" % (
+            n, m, n, d.shape, mult.shape, bound_mult.shape))
+    active = sorted(int(j) for j in active)
+    if len(set(active)) != len(active) or any(j < 0 or j >= m_ineq + 2 * n for j in active):
+        raise CertificateError(["active set"], {}, ["active set: repeated or out-of-range ids"])
+    try:
+        rows, rhs = active_rows(A, c, lo, hi, m_eq, active, n)
+        d_star, lam, history = refine(Z, g, rows, rhs, sweeps)
+    except ValueError as exc:
+        raise CertificateError(["active set"], {}, ["active set: %s" % exc])
+    scale = max(1.0, float(np.abs(d_star).max()))
+    referee = max(history["step_moved"][-2:]) / scale
+    measured = {"active_rows": int(rows.shape[0]), "referee": referee}
+    if not referee <= tol_conv:
+        raise CertificateError(["referee"], measured, [
+            "referee: the refinement did not converge (its last sweeps moved d* by %.2e x max(1, |d*|) > %.0e): the "
+            "certificate is void" % (referee, tol_conv)])
+    failed, details = [], []
+
+    def check(name, ok, text):
+        if not ok:
+            failed.append(name)
+            details.append(name + ": " + text)
+
+    # step
+    measured["step"] = float(np.abs(d.astype(LD) - d_star).max()) / scale
+    check("step", measured["step"] <= tol_d, "|d - d*| = %.2e x max(1, |d*|) > tol_d %.0e" % (measured["step"], tol_d))
+    # dual feasibility: lambda* of the active inequalities and bounds
+    lam64 = lam.astype(np.float64)
+    mscale = max(1.0, float(np.abs(lam64).max(initial=0.0)))
+    least = float(lam64[m_eq:].min()) / mscale if rows.shape[0] > m_eq else 0.0
+    measured["dual"] = least
+    check("dual feasibility", least >= -tol_mu,
+          "a multiplier of an active inequality is %.2e x max(1, |lambda*|) < -tol_mu %.0e" % (least, tol_mu))
+    # primal feasibility at d*: every general inequality, every finite bound
+    pscale = max(1.0, float(np.abs(np.asarray(c, dtype=np.float64)).max(initial=0.0)))
+    worst = 0.0
+    if m_ineq:
+        vals = A[m_eq:].astype(LD) @ d_star + np.asarray(c[m_eq:], dtype=LD)
+        worst = max(worst, float(-vals.min()))
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    for bound, sign in ((lo, 1.0), (hi, -1.0)):
+        fin = np.isfinite(bound)
+        if fin.any():
+            worst = max(worst, float((-sign * (d_star[fin] - bound[fin].astype(LD))).max()))
+    measured["primal"] = max(worst, 0.0) / pscale
+    check("primal feasibility", measured["primal"] <= tol_p,
+          "a constraint is violated at d* by %.2e x max(1, |c|) > tol_p %.0e" % (measured["primal"], tol_p))
+    # multipliers, mapped to the solver's slots (the order of active_rows: equalities, general rows, bounds)
+    want_mult, want_bm = np.zeros(m), np.zeros(n)
+    want_mult[:m_eq] = lam64[:m_eq]
+    general = [j for j in active if j < m_ineq]
+    bounds = [j for j in active if j >= m_ineq]
+    want_mult[m_eq + np.array(general, dtype=int)] = lam64[m_eq:m_eq + len(general)]
+    for j, v in zip(bounds, lam64[m_eq + len(general):]):
+        i, upper = (j - m_ineq) >> 1, (j - m_ineq) & 1
+        want_bm[i] += -v if upper else v
+    measured["multipliers"] = max(float(np.abs(mult - want_mult).max(initial=0.0)),
+                                  float(np.abs(bound_mult - want_bm).max(initial=0.0))) / mscale
+    check("multipliers", measured["multipliers"] <= tol_mu,
+          "|(mult, bound_mult) - lambda*| = %.2e x max(1, |lambda*|) > tol_mu %.0e" % (measured["multipliers"], tol_mu))
+    if failed:
+        raise CertificateError(failed, measured, details)
+    return measured
