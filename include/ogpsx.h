@@ -230,6 +230,54 @@ int og_multi_synchronize(og_multi mh);
 int og_multi_replica_dev(og_multi mh, int32_t g, double** d_JT_full, double** d_F0, void** hip_stream);
 int og_multi_jt_register_host(og_multi mh, double* JT);
 
+/* ---- a batch of points of one problem (one device) ------------------------------------------------
+ * Everything above works at ONE decision vector; screening initial guesses, evaluating a dispersed family of
+ * trajectories or scanning a parameter means many.  A batch is tied to a handle and owns `capacity` lanes: per lane the
+ * sweep scratch, F(x), a persistent-zero n x m J_T of its own (zeroed here, never to be written by the caller) and its
+ * device words.  One call serves `count` <= capacity points: lane k works at X[k] (row k of a [count][n] array) and the
+ * results of a lane are, bit for bit, what og_eval / og_fd_sweep over all n columns give at that point on the same
+ * handle - lanes share nothing but the problem, down to the non-finite protocol (a lane whose F(x) has non-finite rows
+ * fills ITS matrix with NaN in those rows and cleans it in its next sweep).  The kernels live in a part of the callback
+ * module that is built and loaded only for this (batch_part_path: opengoddard_amd.build.build_batch_part; may be NULL
+ * once a batch of the handle has loaded it).  How the sweep runs follows og_sweep_mode: 5 = one launch for all lanes,
+ * 1 / 2 = one batched evaluation and the handle's sweep kernel per lane (validation).  Every call first enqueues one small
+ * launch that tells the lanes where this call's arrays are (no such state is kept on the host), so a call costs two
+ * launches and a captured graph of it can be replayed between calls on other arrays.  og_batch_create reports lanes
+ * that do not fit the device's memory as an error.  og_problem_destroy destroys the batches of its handle; calls on
+ * such a batch fail.  Calls on one batch, and on a batch and its handle, must not overlap.
+ * og_batch_create / _destroy / _capacity / _lane_dev have no reference counterpart (the reference has one Problem and
+ * one solve at one point at a time). */
+typedef struct og_batch_s* og_batch;
+int og_batch_create(og_handle h, int32_t capacity, const char* batch_part_path, og_batch* out);
+void og_batch_destroy(og_batch b);
+int og_batch_capacity(og_batch b);
+/* Device pointers on the handle's device, asynchronous.  d_X: [count][n]; d_F: [count][m] receives F(X[k]).  Replaces
+ * count times one call each of cost_add, equality_add and the user inequality (OpenGoddard/optimize.py:670-709,
+ * 723-728). */
+int og_batch_eval_dev(og_batch b, int32_t count, const double* d_X, double* d_F, void* hip_stream);
+/* The forward-difference sweep over all n columns at every point.  d_H: [count][n] signed steps (og_fd_step per point);
+ * d_F0: [count][m]; d_vals: [count][nnz] receives each lane's structural non-zeros in og_pattern's order (the pattern
+ * of the columns [0, n)), or NULL.  The dense matrix of lane k stays in the batch (og_batch_lane_dev).  Replaces count
+ * times the 3n+2 callback evaluations of one SLSQP major iteration (scipy:_slsqp_py.py:299-313). */
+int og_batch_fd_sweep_dev(og_batch b, int32_t count, const double* d_X, const double* d_H, double* d_F0,
+                          double* d_vals, void* hip_stream);
+/* Lane `lane` of the batch: *d_JT its n x m matrix on the device (JT[j * m + r], as og_fd_sweep over [0, n) lays it out;
+ * valid as long as the batch), *nonfinite_rows the number of non-finite rows of F at the lane's most recent point
+ * (this one waits for the stream of the batch's most recent call, not for the device; the count is the lane's own: calls
+ * that run fewer lanes leave it alone).  Either pointer may be NULL. */
+int og_batch_lane_dev(og_batch b, int32_t lane, double** d_JT, int32_t* nonfinite_rows);
+/* Host pointers, blocking.  X, H: [count][n]; F, F0: [count][m]; vals: [count][nnz]; nonfinite: [count] or NULL.  The
+ * host form returns the packed non-zeros, not count dense matrices.  The packed form cannot carry a NaN fill of
+ * structural zeros: a lane whose F(x) has non-finite rows is reported in nonfinite[k] (the number of such rows), its
+ * vals[k] hold what the sweep computed at the pattern's entries only, and its dense matrix - NaN in those rows of
+ * every column, as dense differencing makes them - is read from the lane (og_batch_lane_dev + og_device_read).
+ * When F0 and vals both lie in page-locked memory the device can address (og_pinned_alloc) the launch writes them in
+ * place over PCIe; otherwise they come down through the batch's staging buffers (same values).
+ * Replace the same reference code as the device forms. */
+int og_batch_eval(og_batch b, int32_t count, const double* X, double* F);
+int og_batch_fd_sweep(og_batch b, int32_t count, const double* X, const double* H, double* F0, double* vals,
+                      int32_t* nonfinite);
+
 /* ---- exact Jacobian (opt-in, changes the numbers SLSQP sees) ---
  * Same layout as the sweep: JT[(j - col_lo) * m + r] = dF_r/dx_j, but by forward-mode
  * differentiation of the traced callbacks (no step h, no subtraction, no FD noise; where a callback

@@ -70,7 +70,7 @@ def _core_sources():
 
 
 def _kernel_sources():
-    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk.h", "og_math.h", "og_dual.h")]
+    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h")]
 
 
 def build_core(force=False):
@@ -137,6 +137,43 @@ def part_path(out, index):
     return out if index == 0 else out[:-3] + ".p%d.so" % index
 
 
+BATCH_PART = 4                  # OGK_PART of <module>.batch.so: the kernels of a batch of points (og_batch_*)
+
+
+def batch_part_path(out):
+    return out[:-3] + ".batch.so"
+
+
+def _write_header(header_source, digest):
+    """The generated header of a module, next to its shared objects (written through a temporary file: concurrent
+    builds of one digest see a whole file) -> its path."""
+    header = os.path.join(JITDIR, "og_gen_%s.h" % digest)
+    with tempfile.NamedTemporaryFile("w", dir=JITDIR, suffix=".h", delete=False) as fh:
+        fh.write(header_source)
+        tmp_header = fh.name
+    os.replace(tmp_header, header)
+    return header
+
+
+def build_batch_part(header_source, force=False):
+    """Compile the batch kernels (``ogk_fused_batch`` / ``ogk_eval_batch``, csrc/ogk_kernels.hip, ``OGK_PART=4``)
+    against one generated header -> path of ``<module>.batch.so``, next to the module of the same digest and cached
+    like it.  Not one of ``MODULE_PARTS``: it is built when a batch is first asked for (``HipEngine.batch``), so that
+    ``build_module`` and the cold start of a user who never batches stay what they are."""
+    os.makedirs(JITDIR, exist_ok=True)
+    digest = module_digest(header_source)
+    out = batch_part_path(module_path(digest))
+    if not force and os.path.exists(out):
+        return out
+    header = _write_header(header_source, digest)
+    tmp = out + ".tmp%d" % os.getpid()
+    _run([hipcc()] + HIP_FLAGS + MODULE_FLAGS + ["-DOGK_PART=%d" % BATCH_PART, "-I" + CSRC,
+                                                 "-DOG_GEN_HEADER=\"%s\"" % header,
+                                                 os.path.join(CSRC, "ogk_kernels.hip"), "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):
     """Compile the sweep kernels against one generated header -> path of the module (its part 0; the other
     parts are built next to it, in parallel).  ``out_suffix``: write the result next to the cached module instead
@@ -157,11 +194,7 @@ def build_module(header_source, digest=None, force=False, out_suffix="", parts=N
         cached = True                   # a whole module serves a split request too: it holds every kernel
     if not force and cached:
         return out
-    header = os.path.join(JITDIR, "og_gen_%s.h" % digest)
-    with tempfile.NamedTemporaryFile("w", dir=JITDIR, suffix=".h", delete=False) as fh:
-        fh.write(header_source)
-        tmp_header = fh.name
-    os.replace(tmp_header, header)
+    header = _write_header(header_source, digest)
 
     def compile_part(index):
         """-> (temporary file, target); the caller renames, in an order a concurrent reader can rely on"""

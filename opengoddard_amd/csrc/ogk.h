@@ -4,7 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-#define OGK_ABI 11
+#define OGK_ABI 13
 #define OGK_MAX_PHASE 32
 
 // MFMA operand image of a differentiation matrix D (N x N, row-major [k][l]) for
@@ -82,6 +82,29 @@ typedef struct ogk_args {
     int64_t dfrag_off[OGK_MAX_PHASE];
 } ogk_args;
 
+// A batch (og_batch_*, include/ogpsx.h): B points of one problem in one launch, lane = blockIdx.y.  A lane is one
+// ogk_args record in a device table that the runtime writes when the batch is created: its own scratch, ticket,
+// counters and persistent-zero jt with its own jt_state / jt_launches words; dfrag, cvec and the pattern tables are
+// the handle's.  The table holds OGK_BATCH_SETS record sets of `capacity` lanes each: set 0 is what the one-launch
+// sweep (mode 11) runs; sets 1 and 2 are what the evaluation (mode 12) runs, with jt_bump = 0 and 1.  What changes
+// from call to call - where the caller's X, H, F0 and packed values are - is written into the records by mode 13
+// (one thread per record) ahead of EVERY mode 11 / 12 launch, stream-ordered before it, so that those launches take
+// the table and the lane count only and a captured graph carries its own binding.  Mode 13 also zeroes the non-finite
+// counter of the lanes an evaluation is about to run (a lane's count stays where it is while launches run without it).
+#define OGK_BATCH_SETS 3
+typedef struct ogk_batch_args {
+    ogk_args* lanes;        // modes 11, 12: the record set to run ([capacity] records); mode 13: the whole table
+    int32_t count;          // lanes of this launch (<= capacity)
+    int32_t capacity;
+    // mode 13: lane k reads X + k * n (and H + k * n), writes F0 + k * m (and vals + k * nnz; vals may be NULL)
+    const double* X;
+    const double* H;
+    double* F0;
+    double* vals;
+    int64_t nnz;
+    int32_t clear_set;      // mode 13: zero *nonfinite of the first `count` records of this set (-1: none)
+} ogk_batch_args;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -96,6 +119,10 @@ int ogk_get_info(ogk_info* out);
 // previous step left such a fill behind.  mode 10: count one launch into *jt_launches.
 // Only enqueues kernels on `stream`; returns a hipError_t value (0 = success).
 int ogk_launch(const ogk_args* args, int mode, void* stream);
+// exported by the batch part of a module only (OGK_PART == 4, built when a batch is first asked for).
+// mode 11: ogk_fused over all n columns for `count` lanes in one launch.  mode 12: ogk_eval for `count` lanes.
+// mode 13: bind the caller's arrays to the records (see above).
+int ogk_launch_batch(const ogk_batch_args* args, int mode, void* stream);
 #ifdef __cplusplus
 }
 #endif

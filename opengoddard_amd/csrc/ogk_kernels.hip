@@ -192,6 +192,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #if !defined(OGK_PART) || OGK_PART == 3
 #define OGK_HAS_SWEEP 1      // mode 1: the structured sweep as a launch of its own
 #endif
+#if defined(OGK_PART) && OGK_PART == 4
+#define OGK_HAS_BATCH 1      // modes 11 - 13: a batch of points per launch; never part of a module's default build
+#endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
 // ------------------------------------------------------------------------------------------
@@ -1530,53 +1533,59 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
                                                            const int group_lo, const int n_light, const int sum_lo,
                                                            const int n_sum) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
-    int id = (int)blockIdx.x;
-    if (id < n_eval) {
-        FZ_TRACE_DECL(0);
-        if (!(OGK_FZ & 16)) {
-            if (id < ndef) eval_defect_body<true>(a, id, lds);
-            else eval_rows_body<true>(a, id - ndef, lds);
-        }
-        FZ_STAMP(1);
-        finish_eval(a, (unsigned)n_eval, reinterpret_cast<unsigned*>(lds));
-        FZ_STAMP(4);
-        FZ_TRACE_OUT(a);
-        return;
-    }
-    id -= n_eval;
-    // nothing in the sweep workgroups waits for the evaluation workgroups (finish_eval).  Grid order (OGK_ORDER,
-    // timing experiments): 0 = light, heavy parts, MFMA tiles; 1 = MFMA tiles, heavy parts, light; 2 = tiles and
-    // light workgroups interleaved, heavy parts first
-#ifndef OGK_ORDER
-#define OGK_ORDER 0
+#include "ogk_fused_workgroup.inc"
+}
 #endif
-    const int n_tile = OGT_N_FTILES, n_heavy = OGT_N_HPART;
-    int kind, idx;                                     // 0 light, 1 heavy, 2 tile
-    if (OGK_ORDER == 0) {
-        if (id < n_light) kind = 0, idx = id;
-        else if (id < n_light + n_heavy) kind = 1, idx = id - n_light;
-        else kind = 2, idx = id - n_light - n_heavy;
-    } else if (OGK_ORDER == 1) {
-        if (id < n_tile) kind = 2, idx = id;
-        else if (id < n_tile + n_heavy) kind = 1, idx = id - n_tile;
-        else kind = 0, idx = id - n_tile - n_heavy;
-    } else {
-        if (id < n_heavy) kind = 1, idx = id;
-        else {
-            const int r = id - n_heavy, pairs = n_light < n_tile ? n_light : n_tile;
-            if (r < 2 * pairs) kind = (r & 1) ? 0 : 2, idx = r >> 1;
-            else if (n_light > n_tile) kind = 0, idx = r - pairs;
-            else kind = 2, idx = r - pairs;
-        }
+
+// ------------------------------------------------------------------------------------------
+// Modes 11 - 13 (the batch part, ogk.h: ogk_batch_args): B points of the problem in one launch.  blockIdx.y is the
+// lane, blockIdx.x means what it means in ogk_fused / ogk_eval, and the workgroup runs the same device functions on
+// the lane's record - so a lane's results are the single-point path's, bit for bit.  Nothing in the one-launch form
+// waits for another workgroup (finish_eval takes a ticket), so the grid needs no co-residency: lanes beyond one round
+// of residency start later.  The records stay where they are, in the table: the workgroup reads the fields it uses
+// through the constant address space (scalar loads, as it reads a launch's argument block) - a copy of a 500-byte
+// record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_BATCH
+typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
+__device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
+    // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
+    return *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.y);
+}
+
+__global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused_batch(const ogk_args* __restrict__ lanes,
+                                                                 const int ndef, const int n_eval, const int group_lo,
+                                                                 const int n_light, const int sum_lo, const int n_sum) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const ogk_args& a = batch_lane(lanes);
+#include "ogk_fused_workgroup.inc"
+}
+
+__global__ __launch_bounds__(SWEEP_THREADS) void ogk_eval_batch(const ogk_args* __restrict__ lanes, const int ndef) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const ogk_args& a = batch_lane(lanes);
+    const int id = (int)blockIdx.x;
+    if (id == 0 && threadIdx.x == 0) {                  // as ogk_eval (a lane's nonfinite_next is a word nobody reads:
+                                                        // ogk_batch_bind zeroes the counter ahead of this launch)
+        *a.nonfinite_next = 0;
+        if (a.jt_bump) __hip_atomic_store(a.jt_launches, *a.jt_launches + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    // light workgroups: the ones that carry a sequential sum first (OGT_LSUM / OGT_LPLAIN: both in column order;
-    // sum_lo of the first list and group_lo - sum_lo of the second lie below this launch's column range)
-    // (n_sum < 0: column order - the launch fits one round of residency and the order only decides who shares a compute unit)
-    if (kind == 0)
-        fz_light_body(a, n_sum < 0 ? group_lo + idx
-                                   : idx < n_sum ? OGT_LSUM[sum_lo + idx] : OGT_LPLAIN[group_lo - sum_lo + idx - n_sum], lds);
-    else if (kind == 1) { if (!(OGK_FZ & 32)) fz_heavy_part(a, idx, lds); }
-    else fz_tile_body(a, idx, lds);
+    if (id < ndef) eval_defect_body<false>(a, id, lds);
+    else eval_rows_body<false>(a, id - ndef, lds);
+}
+
+// where this call's arrays are: one thread per record of the table (every lane of every set: a later launch may run
+// more lanes of the same arrays); the lanes an evaluation is about to run get their non-finite counter zeroed
+__global__ void ogk_batch_bind(const ogk_batch_args b) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= OGK_BATCH_SETS * b.capacity) return;
+    const int k = i % b.capacity;
+    ogk_args& a = b.lanes[i];
+    a.x0 = b.X + (long)k * OgGen::N_VAR;
+    a.h = b.H ? b.H + (long)k * OgGen::N_VAR : nullptr;
+    a.f0 = b.F0 + (long)k * OgGen::M;
+    a.pvals = b.vals ? b.vals + (long)k * b.nnz : nullptr;
+    if (i / b.capacity == b.clear_set && k < b.count) *a.nonfinite = 0;
 }
 #endif
 
@@ -1830,3 +1839,40 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
 #endif
     return OGK_OTHER_PART;
 }
+
+#ifdef OGK_HAS_BATCH
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity) return (int)hipErrorInvalidValue;
+    const int ndef = defect_blocks();
+    const int eval_row_blocks = (OGT_N_ROWWAVES + SWEEP_WAVES - 1) / SWEEP_WAVES;
+    if (mode == 13) {
+        const int records = OGK_BATCH_SETS * b->capacity;
+        hipLaunchKernelGGL(ogk_batch_bind, dim3((records + 63) / 64), dim3(64), 0, stream, *b);
+        return (int)hipGetLastError();
+    }
+    if (mode == 12) {
+        if (ndef + eval_row_blocks > 0)
+            hipLaunchKernelGGL(ogk_eval_batch, dim3(ndef + eval_row_blocks, b->count), dim3(SWEEP_THREADS),
+                               defect_lds_bytes(), stream, (const ogk_args*)b->lanes, ndef);
+        return (int)hipGetLastError();
+    }
+    if (mode == 11) {
+        // the geometry of mode 5 over all n columns, once per lane
+        size_t lds_bytes = defect_lds_bytes() > FZ_LDS_BYTES ? defect_lds_bytes() : FZ_LDS_BYTES;
+        const size_t fill_lds = (size_t)ROW_WORDS * sizeof(unsigned);
+        if (fill_lds > lds_bytes) lds_bytes = fill_lds;
+        if (lds_bytes > 64 * 1024 || ndef + eval_row_blocks == 0) return (int)hipErrorInvalidValue;
+        int n_sum = 0;
+        for (int gidx = 0; gidx < OGT_N_LGRP; ++gidx) n_sum += OGH_LGRP_SUM[gidx];
+        const int grid = ndef + eval_row_blocks + OGT_N_FTILES + OGT_N_HPART + OGT_N_LGRP;
+        // (the order of a lane's light workgroups as in mode 5: column order while the whole launch fits one round
+        // of residency, the ones with a sequential sum first beyond that)
+        if ((long)grid * b->count <= 512) n_sum = -1;
+        hipLaunchKernelGGL(ogk_fused_batch, dim3(grid, b->count), dim3(SWEEP_THREADS), lds_bytes, stream,
+                           (const ogk_args*)b->lanes, ndef, ndef + eval_row_blocks, 0, OGT_N_LGRP, 0, n_sum);
+        return (int)hipGetLastError();
+    }
+    return (int)hipErrorInvalidValue;
+}
+#endif

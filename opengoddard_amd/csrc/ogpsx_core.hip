@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -59,6 +60,7 @@ __global__ void lgl_dmat_kernel(int N, const double* tau, const double* pval, do
 
 typedef int (*ogk_get_info_fn)(ogk_info*);
 typedef int (*ogk_launch_fn)(const ogk_args*, int, void*);
+typedef int (*ogk_launch_batch_fn)(const ogk_batch_args*, int, void*);
 
 // A callback module is one shared object, or several PARTS of it that were compiled side by side (build.py:
 // <module>.so, <module>.p1.so, ...; each holds some of the kernels and answers OGK_OTHER_PART for the modes of the
@@ -87,6 +89,8 @@ struct ogk_module {
 };
 
 }  // namespace
+
+struct og_batch_s;
 
 struct og_problem_s {
     int device = 0;
@@ -175,6 +179,10 @@ struct og_problem_s {
     int64_t* d_shard_off = nullptr;
     void* shard_comm = nullptr;         // ncclComm_t of this rank (og_shard_comm_init), one process per GPU
     int shard_rank = -1;
+    // batches of points (og_batch_create): the batch part of the module is loaded by the first of them
+    void* batch_module = nullptr;
+    ogk_launch_batch_fn batch_launch = nullptr;
+    std::vector<og_batch_s*> batches;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -698,6 +706,8 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
 void og_problem_destroy(og_handle p) {
     if (!p) return;
     hipSetDevice(p->device);
+    while (!p->batches.empty()) og_batch_destroy(p->batches.back());
+    if (p->batch_module) dlclose(p->batch_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -1263,6 +1273,362 @@ int og_jacobian_exact(og_handle p, const double* x, int32_t lo, int32_t hi, doub
     rc = og_jacobian_exact_dev(p, p->d_x, lo, hi, p->d_jt, p->d_f0, p->stream);
     if (rc) return rc;
     return download_block(p, lo, hi, JT, F0);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Batches: `capacity` lanes of one handle, each with everything ogk_args makes per-point (scratch, counters, ticket,
+// a persistent-zero n x m J_T with its own state words); one launch of the module's batch part (ogk.h:
+// ogk_batch_args) runs `count` of them.  The lane records are written once, here; a launch takes the table and the
+// lane count, and the one-thread-per-record bind kernel ahead of it says where the caller's arrays are - skipped
+// while they are where they were (and never skipped on a capturing stream: a captured graph binds for itself).
+// ------------------------------------------------------------------------------------------------
+struct og_batch_s {
+    og_problem_s* p = nullptr;
+    int capacity = 0;
+    int64_t nnz = 0;
+    ogk_args* d_table = nullptr;            // [OGK_BATCH_SETS][capacity]
+    std::vector<ogk_args> table;            // the host's copy (the per-lane launches of the split / dense form use it)
+    double* d_jt = nullptr;                 // [capacity][n][m]
+    double* d_scratch = nullptr;            // per lane: y0 | xop | t0 | z
+    size_t scratch_lane = 0, n_y0 = 0;
+    int* d_flags = nullptr;                 // [capacity][8]: as og_problem_s::d_flags
+    uint32_t* d_state = nullptr;            // [capacity][2]: jt_state, jt_launches
+    // per lane: the word of its d_flags that holds the count of non-finite rows at its most recent point (0 after an
+    // evaluation launch, 4 after a one-launch sweep) - a lane keeps it while later launches run fewer lanes
+    std::vector<int> nf_word;
+    hipStream_t last_stream = nullptr;      // of the most recent launch (og_batch_lane_dev waits for this one only)
+    // host-pointer entry points: device arrays [X | H], F, packed values and their pinned images
+    double *d_xh = nullptr, *d_f = nullptr, *d_vals = nullptr;
+    double *h_up = nullptr, *h_down = nullptr;
+    int* h_flags = nullptr;
+};
+
+namespace {
+
+// live batches: a batch whose handle is gone is not among them.  Batches of different handles may be used from
+// different threads: the list has a lock of its own
+std::mutex g_batches_lock;
+std::vector<og_batch_s*> g_batches;
+
+og_batch_s* live_batch(og_batch b) {
+    std::lock_guard<std::mutex> guard(g_batches_lock);
+    for (og_batch_s* q : g_batches)
+        if (q == b) return q;
+    return nullptr;
+}
+
+int batch_check(og_batch b, int32_t count, const char* who) {
+    if (!b) return fail(1, std::string(who) + ": null batch");
+    if (!live_batch(b)) return fail(1, std::string(who) + ": the batch or its handle has been destroyed");
+    if (count < 1) return fail(1, std::string(who) + ": count must be at least 1");
+    if (count > b->capacity)
+        return fail(1, std::string(who) + ": count " + std::to_string(count) + " exceeds the batch's capacity " +
+                           std::to_string(b->capacity));
+    return 0;
+}
+
+ogk_args* batch_set(og_batch_s* b, int set) { return b->d_table + (size_t)set * (size_t)b->capacity; }
+
+// Where this call's arrays are, written into the lane records by a one-thread-per-record launch ahead of EVERY batched
+// launch: the records are device state that a replayed graph rewrites behind the host's back, so the host keeps no
+// memory of what they hold.  The same launch zeroes the non-finite counter of the lanes an evaluation is about to
+// run (clear_set: the record set of that evaluation, or -1).
+int batch_bind(og_batch_s* b, int count, const double* X, const double* H, double* F, double* vals, int clear_set,
+               hipStream_t s, const char* who) {
+    ogk_batch_args ba;
+    memset(&ba, 0, sizeof ba);
+    ba.lanes = b->d_table;
+    ba.count = count;
+    ba.capacity = b->capacity;
+    ba.X = X, ba.H = H, ba.F0 = F, ba.vals = vals, ba.nnz = b->nnz;
+    ba.clear_set = clear_set;
+    const int rc = b->p->batch_launch(&ba, 13, s);
+    if (rc) return launch_failed(b->p, rc, who);
+    b->last_stream = s;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void og_batch_destroy(og_batch b) {
+    if (!b || !live_batch(b)) return;
+    {
+        std::lock_guard<std::mutex> guard(g_batches_lock);
+        g_batches.erase(std::find(g_batches.begin(), g_batches.end(), b));
+    }
+    og_problem_s* p = b->p;
+    auto it = std::find(p->batches.begin(), p->batches.end(), b);
+    if (it != p->batches.end()) p->batches.erase(it);
+    hipSetDevice(p->device);
+    hipFree(b->d_table);
+    hipFree(b->d_jt);
+    hipFree(b->d_scratch);
+    hipFree(b->d_flags);
+    hipFree(b->d_state);
+    hipFree(b->d_xh);
+    hipFree(b->d_f);
+    hipFree(b->d_vals);
+    if (b->h_up) hipHostFree(b->h_up);
+    if (b->h_down) hipHostFree(b->h_down);
+    if (b->h_flags) hipHostFree(b->h_flags);
+    (void)hipGetLastError();
+    delete b;
+}
+
+int og_batch_capacity(og_batch b) { return live_batch(b) ? b->capacity : 0; }
+
+int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, og_batch* out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(1, "og_batch_create: null argument");
+    if (capacity < 1 || capacity > 65535) return fail(1, "og_batch_create: capacity must be in [1, 65535]");
+    OG_HIP(hipSetDevice(p->device));
+    if (!p->batch_launch) {
+        if (!batch_part_path) return fail(4, "og_batch_create: the module's batch part is not loaded and no path was given");
+        void* mod = dlopen(batch_part_path, RTLD_NOW | RTLD_LOCAL);
+        if (!mod) return fail(4, std::string("og_batch_create: dlopen of the batch part failed: ") + dlerror());
+        ogk_get_info_fn get_info = (ogk_get_info_fn)dlsym(mod, "ogk_get_info");
+        ogk_launch_batch_fn fn = (ogk_launch_batch_fn)dlsym(mod, "ogk_launch_batch");
+        ogk_info info;
+        memset(&info, 0, sizeof info);
+        if (get_info && fn) get_info(&info);
+        if (!get_info || !fn || info.abi != OGK_ABI || info.n != p->n || info.m != p->m || info.m_eq != p->m_eq ||
+            info.n_eval_blocks != p->n_eval_blocks) {
+            dlclose(mod);
+            return fail(5, "og_batch_create: the batch part does not belong to the handle's module");
+        }
+        p->batch_module = mod;
+        p->batch_launch = fn;
+    }
+    int rc = ensure_pattern(p);
+    if (rc) return rc;
+    ogk_info info;
+    memset(&info, 0, sizeof info);
+    ((ogk_get_info_fn)dlsym(p->batch_module, "ogk_get_info"))(&info);
+
+    og_batch_s* b = new og_batch_s();
+    b->p = p;
+    b->capacity = capacity;
+    b->nnz = p->indptr[(size_t)p->n];
+    b->n_y0 = (size_t)(info.n_y0 > 0 ? info.n_y0 : 1);
+    b->scratch_lane = 2 * b->n_y0 + 2 * (size_t)p->m;
+    b->nf_word.assign((size_t)capacity, 4);
+    {
+        std::lock_guard<std::mutex> guard(g_batches_lock);
+        g_batches.push_back(b);
+    }
+    p->batches.push_back(b);
+    const size_t cap = (size_t)capacity, n = (size_t)p->n, m = (size_t)p->m, nnz = (size_t)(b->nnz ? b->nnz : 1);
+    // an allocation that does not fit is an error of this call (C5: 304 MB of J_T per lane)
+    hipError_t e = hipMalloc(&b->d_jt, sizeof(double) * cap * n * m);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_jt, 0, sizeof(double) * cap * n * m, p->stream);
+    if (e == hipSuccess) e = hipMalloc(&b->d_scratch, sizeof(double) * cap * b->scratch_lane);
+    if (e == hipSuccess) e = hipMalloc(&b->d_flags, sizeof(int) * 8 * cap);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_flags, 0, sizeof(int) * 8 * cap, p->stream);
+    if (e == hipSuccess) e = hipMalloc(&b->d_state, sizeof(uint32_t) * 2 * cap);
+    if (e == hipSuccess) e = hipMalloc(&b->d_table, sizeof(ogk_args) * OGK_BATCH_SETS * cap);
+    if (e == hipSuccess) e = hipMalloc(&b->d_xh, sizeof(double) * 2 * cap * n);
+    if (e == hipSuccess) e = hipMalloc(&b->d_f, sizeof(double) * cap * m);
+    if (e == hipSuccess) e = hipMalloc(&b->d_vals, sizeof(double) * cap * nnz);
+    if (e == hipSuccess) e = hipHostMalloc(&b->h_up, sizeof(double) * 2 * cap * n, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(&b->h_down, sizeof(double) * cap * (nnz + m), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(&b->h_flags, sizeof(int) * 8 * cap, hipHostMallocDefault);
+    if (e == hipSuccess) {
+        // per lane {state: no NaN fill, launches so far: 0}
+        std::vector<uint32_t> st(2 * cap);
+        for (size_t k = 0; k < cap; ++k) st[2 * k] = 0xffffffffu, st[2 * k + 1] = 0u;
+        e = hipMemcpy(b->d_state, st.data(), sizeof(uint32_t) * 2 * cap, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) {
+        b->table.resize((size_t)OGK_BATCH_SETS * cap);
+        for (int set = 0; set < OGK_BATCH_SETS; ++set)
+            for (size_t k = 0; k < cap; ++k) {
+                ogk_args& a = b->table[(size_t)set * cap + k];
+                fill_args(p, &a, nullptr, nullptr, nullptr, nullptr, 0, p->n);
+                double* scr = b->d_scratch + k * b->scratch_lane;
+                int* fl = b->d_flags + 8 * k;
+                a.y0 = scr;
+                a.xop = scr + b->n_y0;
+                a.t0 = scr + 2 * b->n_y0;
+                a.z = a.t0 + m;
+                a.trace = nullptr;
+                a.jt = b->d_jt + k * n * m;
+                a.jt_sparse = 1;
+                a.jt_state = b->d_state + 2 * k;
+                a.jt_launches = a.jt_state + 1;
+                a.ready = reinterpret_cast<unsigned*>(fl + 2);
+                a.nonfinite_result = fl + 4;
+                a.poff = p->d_indptr;
+                if (set == 0) {
+                    a.nonfinite = fl + 3;
+                    a.nonfinite_next = fl + 3;
+                } else {
+                    // an evaluation counts into word 0, which the bind launch ahead of it zeroes for the lanes that run;
+                    // the kernel's own "clear the other counter" goes to a word nobody reads
+                    a.nonfinite = fl;
+                    a.nonfinite_next = fl + 1;
+                    a.jt_bump = set - 1;
+                }
+            }
+        e = hipMemcpy(b->d_table, b->table.data(), sizeof(ogk_args) * b->table.size(), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        og_batch_destroy(b);
+        return fail(100 + (int)e, std::string("og_batch_create: ") + hipGetErrorString(e) + " (" +
+                                      std::to_string(capacity) + " lanes of " +
+                                      std::to_string((double)(n * m) * 8.0 / 1048576.0) + " MB each)");
+    }
+    *out = b;
+    return 0;
+}
+
+int og_batch_eval_dev(og_batch b, int32_t count, const double* d_X, double* d_F, void* hip_stream) {
+    int rc = batch_check(b, count, "og_batch_eval_dev");
+    if (rc) return rc;
+    if (!d_X || !d_F) return fail(1, "og_batch_eval_dev: null argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    rc = batch_bind(b, count, d_X, nullptr, d_F, nullptr, 1, s, "og_batch_eval_dev");
+    if (rc) return rc;
+    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
+    ogk_batch_args ba;
+    memset(&ba, 0, sizeof ba);
+    ba.lanes = batch_set(b, 1);
+    ba.count = count;
+    ba.capacity = b->capacity;
+    rc = b->p->batch_launch(&ba, 12, s);
+    if (rc) return launch_failed(b->p, rc, "og_batch_eval_dev");
+    return 0;
+}
+
+int og_batch_fd_sweep_dev(og_batch b, int32_t count, const double* d_X, const double* d_H, double* d_F0,
+                          double* d_vals, void* hip_stream) {
+    int rc = batch_check(b, count, "og_batch_fd_sweep_dev");
+    if (rc) return rc;
+    if (!d_X || !d_H || !d_F0) return fail(1, "og_batch_fd_sweep_dev: null argument");
+    og_problem_s* p = b->p;
+    hipStream_t s = (hipStream_t)hip_stream;
+    const bool one_launch = p->sweep_mode == 5 && p->fused_ok;
+    rc = batch_bind(b, count, d_X, d_H, d_F0, d_vals, one_launch ? -1 : 2, s, "og_batch_fd_sweep_dev");
+    if (rc) return rc;
+    ogk_batch_args ba;
+    memset(&ba, 0, sizeof ba);
+    ba.count = count;
+    ba.capacity = b->capacity;
+    if (one_launch) {
+        // ONE launch for all lanes; its arguments are the table and the lane count
+        ba.lanes = batch_set(b, 0);
+        for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 4;
+        rc = p->batch_launch(&ba, 11, s);
+        if (rc) return launch_failed(p, rc, "og_batch_fd_sweep_dev");
+        return 0;
+    }
+    // the validation forms (OGPSX_SWEEP=split | dense, or a module whose one-launch form does not fit): one batched
+    // evaluation, then the handle's own sweep kernel lane by lane
+    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
+    const int set = 2;
+    ba.lanes = batch_set(b, set);
+    rc = p->batch_launch(&ba, 12, s);
+    for (int k = 0; !rc && k < count; ++k) {
+        ogk_args a = b->table[(size_t)set * (size_t)b->capacity + (size_t)k];
+        a.x0 = d_X + (size_t)k * (size_t)p->n;
+        a.h = d_H + (size_t)k * (size_t)p->n;
+        a.f0 = d_F0 + (size_t)k * (size_t)p->m;
+        rc = p->launch(&a, p->sweep_mode == 5 ? 1 : p->sweep_mode, s);
+        if (!rc && d_vals) {
+            a.pind = p->d_indptr;
+            a.prow = p->d_rows;
+            a.pvals = d_vals + (size_t)k * (size_t)b->nnz;
+            rc = p->launch(&a, 8, s);
+        }
+    }
+    if (rc) return launch_failed(p, rc, "og_batch_fd_sweep_dev");
+    return 0;
+}
+
+int og_batch_lane_dev(og_batch b, int32_t lane, double** d_JT, int32_t* nonfinite_rows) {
+    if (!b) return fail(1, "og_batch_lane_dev: null batch");
+    if (!live_batch(b)) return fail(1, "og_batch_lane_dev: the batch or its handle has been destroyed");
+    if (lane < 0 || lane >= b->capacity) return fail(1, "og_batch_lane_dev: lane out of range");
+    if (d_JT) *d_JT = b->d_jt + (size_t)lane * (size_t)b->p->n * (size_t)b->p->m;
+    if (nonfinite_rows) {
+        // stream-ordered after the batch's most recent launch: waits for that stream, not for the whole device
+        OG_HIP(hipSetDevice(b->p->device));
+        OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags + 8 * (size_t)lane + b->nf_word[(size_t)lane], sizeof(int),
+                              hipMemcpyDeviceToHost, b->last_stream));
+        OG_HIP(hipStreamSynchronize(b->last_stream));
+        *nonfinite_rows = b->h_flags[0];
+    }
+    return 0;
+}
+
+int og_batch_eval(og_batch b, int32_t count, const double* X, double* F) {
+    int rc = batch_check(b, count, "og_batch_eval");
+    if (rc) return rc;
+    if (!X || !F) return fail(1, "og_batch_eval: null argument");
+    og_problem_s* p = b->p;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count;
+    memcpy(b->h_up, X, sizeof(double) * c * n);
+    OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
+    rc = og_batch_eval_dev(b, count, b->d_xh, b->d_f, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(b->h_down, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    memcpy(F, b->h_down, sizeof(double) * c * m);
+    return 0;
+}
+
+int og_batch_fd_sweep(og_batch b, int32_t count, const double* X, const double* H, double* F0, double* vals,
+                      int32_t* nonfinite) {
+    int rc = batch_check(b, count, "og_batch_fd_sweep");
+    if (rc) return rc;
+    if (!X || !H || !F0 || !vals) return fail(1, "og_batch_fd_sweep: null argument");
+    og_problem_s* p = b->p;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    const size_t nnz = (size_t)b->nnz;
+    // [X | H] up in one copy when the batch is full, in two otherwise (the device arrays are [capacity][n] each)
+    memcpy(b->h_up, X, sizeof(double) * c * n);
+    memcpy(b->h_up + cap * n, H, sizeof(double) * c * n);
+    if (c == cap) {
+        OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * 2 * cap * n, hipMemcpyHostToDevice, p->stream));
+    } else {
+        OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
+        OG_HIP(hipMemcpyAsync(b->d_xh + cap * n, b->h_up + cap * n, sizeof(double) * c * n, hipMemcpyHostToDevice,
+                              p->stream));
+    }
+    // F0 and vals in page-locked memory the device can address (og_pinned_alloc, hipHostRegister): the launch writes
+    // them over PCIe as it goes, and only the lanes' counts of non-finite rows are left to fetch
+    void *m_f = nullptr, *m_vals = nullptr;
+    if (hipHostGetDevicePointer(&m_f, F0, 0) != hipSuccess || hipHostGetDevicePointer(&m_vals, vals, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        m_f = m_vals = nullptr;
+    }
+    if (m_f && m_vals) {
+        rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + cap * n, (double*)m_f, (double*)m_vals, p->stream);
+        if (rc) return rc;
+        OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
+        OG_HIP(hipStreamSynchronize(p->stream));
+        if (nonfinite)
+            for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
+        return 0;
+    }
+    rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + cap * n, b->d_f, b->d_vals, p->stream);
+    if (rc) return rc;
+    if (nnz) OG_HIP(hipMemcpyAsync(b->h_down, b->d_vals, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipMemcpyAsync(b->h_down + cap * nnz, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
+    memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
+    if (nonfinite)
+        for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
+    return 0;
 }
 
 }  // extern "C"

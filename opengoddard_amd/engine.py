@@ -68,6 +68,7 @@ class HipEngine:
         # the matrix SciPy's callbacks read: allocated once, registered as persistent-zero, so that a sweep
         # moves and writes the non-zeros only (og_jt_register_host)
         self._JT_host = None
+        self._batches = []
         self.devices = devices if devices and len(devices) > 1 else None
         self._multi = C.c_void_p()
         if self.devices:
@@ -77,6 +78,8 @@ class HipEngine:
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
+        for batch in list(getattr(self, "_batches", ())):     # their lanes belong to the handle
+            batch.close()
         cache = getattr(self, "_sqp_cache", None)
         if cache is not None:                       # QP work space of the SQP driver (sqp.py)
             cache[1].close()
@@ -93,6 +96,13 @@ class HipEngine:
             self.close()
         except Exception:
             pass
+
+    # ------------------------------------------------------------------ batches
+    def batch(self, capacity):
+        """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
+        (:class:`BatchSweep`, ``og_batch_create``).  The batch kernels are a part of the callback module that is
+        compiled now, the first time a batch is asked for (``build.build_batch_part``; cached like the module)."""
+        return BatchSweep(self, capacity)
 
     # ------------------------------------------------------------------ raw calls
     def eval_stacked(self, x):
@@ -236,3 +246,132 @@ class HipEngine:
             self._val, self._val_key = self._split(F0), key
             self.n_sweeps += 1
         return self._jac
+
+
+class BatchSweep:
+    """B points of one engine's problem per call (``og_batch_*``, include/ogpsx.h).  Lane ``k`` of a call works at row
+    ``k`` of ``P``; its results are bit for bit what :meth:`HipEngine.eval_stacked` / :meth:`HipEngine.sweep_stacked`
+    give at that point.  A sweep returns the packed structural non-zeros of every lane's J_T (``pattern`` order) - B
+    dense matrices would be tens of megabytes each - and keeps the dense matrix of lane ``k`` on the device
+    (:meth:`dense`).  Replaces B times what the single-point calls replace (``scipy/optimize/_slsqp_py.py:299-313``)."""
+
+    def __init__(self, engine, capacity):
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("BatchSweep: capacity must be at least 1, got %d" % capacity)
+        self.engine = engine
+        self._lib = engine._lib
+        self.n, self.m, self.m_eq, self.m_ineq = engine.n, engine.m, engine.m_eq, engine.m_ineq
+        self.part_path = build.build_batch_part(engine.header)
+        self._handle = C.c_void_p()
+        _native.check(self._lib.og_batch_create(engine._handle, capacity, self.part_path.encode(),
+                                                C.byref(self._handle)), "og_batch_create")
+        self.capacity = int(self._lib.og_batch_capacity(self._handle))
+        self._pattern = None
+        self._pinned = None             # page-locked result arrays of sweep(persistent=True), made when first asked for
+        engine._batches.append(self)
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.og_batch_destroy(self._handle)
+            self._handle = C.c_void_p()
+        if self in getattr(self.engine, "_batches", ()):
+            self.engine._batches.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def pattern(self):
+        """``(indptr, rows)`` of the packed values of one lane: :meth:`HipEngine.pattern` over all columns."""
+        if self._pattern is None:
+            self._pattern = self.engine.pattern()
+        return self._pattern
+
+    @property
+    def nnz(self):
+        return int(self.pattern[0][-1])
+
+    def _points(self, P, what="P"):
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if P.ndim != 2 or P.shape[1] != self.n:
+            raise ValueError("BatchSweep: %s must have shape [B, %d], got %s" % (what, self.n, P.shape))
+        return P
+
+    # -------------------------------------------------------------- host arrays (blocking)
+    def values(self, P):
+        """``F[B, m]``: row ``k`` = ``[cost | c_eq | c_ineq]`` at ``P[k]`` (``og_batch_eval``)."""
+        P = self._points(P)
+        F = np.empty((P.shape[0], self.m))
+        _native.check(self._lib.og_batch_eval(self._handle, P.shape[0], _native.dptr(P), _native.dptr(F)),
+                      "og_batch_eval")
+        return F
+
+    def sweep(self, P, H, persistent=False):
+        """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):
+        ``vals[k]`` are the structural non-zeros of lane ``k``'s J_T in ``pattern`` order.  ``nonfinite[k]`` is the
+        number of non-finite rows of ``F(P[k])``; where it is not zero the dense matrix has NaN in those rows of every
+        column, which the packed form cannot carry - read it with :meth:`dense`.
+
+        ``persistent=True``: ``F0`` and ``vals`` are views of the batch's own page-locked result arrays, which the launch
+        writes in place over PCIe (no staging copy) - valid until the next sweep of this batch, the contract of
+        :meth:`HipEngine.jacobians`.  The default returns fresh arrays."""
+        P, H = self._points(P), self._points(H, "H")
+        if H.shape != P.shape:
+            raise ValueError("BatchSweep: P and H differ in shape: %s, %s" % (P.shape, H.shape))
+        B = P.shape[0]
+        if persistent and 1 <= B <= self.capacity:
+            if self._pinned is None:
+                both = _native.pinned_matrix(self.capacity, self.m + self.nnz)
+                self._pinned = False if both is None else (both.reshape(-1)[:self.capacity * self.m],
+                                                           both.reshape(-1)[self.capacity * self.m:])
+            if self._pinned:
+                F0 = self._pinned[0][:B * self.m].reshape(B, self.m)
+                vals = self._pinned[1][:B * self.nnz].reshape(B, self.nnz)
+            else:
+                persistent = False
+        else:
+            persistent = False
+        if not persistent:
+            F0 = np.empty((B, self.m))
+            vals = np.empty((B, self.nnz))
+        nonfinite = np.zeros(B, dtype=np.int32)
+        _native.check(self._lib.og_batch_fd_sweep(self._handle, B, _native.dptr(P), _native.dptr(H), _native.dptr(F0),
+                                                  _native.dptr(vals), nonfinite.ctypes.data_as(C.POINTER(C.c_int32))),
+                      "og_batch_fd_sweep")
+        return F0, vals, nonfinite
+
+    def jacobians(self, P, lb, ub):
+        """:meth:`sweep` with SciPy's forward-difference step at every point (``_native.fd_step``):
+        ``(F0, vals, nonfinite, H)``."""
+        P = self._points(P)
+        H = np.stack([_native.fd_step(p, lb, ub) for p in P]) if P.shape[0] else np.empty_like(P)
+        return self.sweep(P, H) + (H,)
+
+    def lane_dev(self, k):
+        """``(device pointer of lane k's n x m matrix, non-finite rows at its last point)`` (``og_batch_lane_dev``)."""
+        ptr, bad = C.c_void_p(), C.c_int32()
+        _native.check(self._lib.og_batch_lane_dev(self._handle, int(k), C.byref(ptr), C.byref(bad)),
+                      "og_batch_lane_dev")
+        return int(ptr.value), int(bad.value)
+
+    def dense(self, k):
+        """Lane ``k``'s dense ``n x m`` J_T from its most recent sweep, on the host."""
+        ptr, _ = self.lane_dev(k)
+        JT = np.empty((self.n, self.m))
+        _native.check(self._lib.og_device_read(self.engine.device, ptr, _native.dptr(JT), JT.nbytes), "og_device_read")
+        return JT
+
+    # -------------------------------------------------------------- device pointers (asynchronous)
+    def values_dev(self, count, d_X, d_F, stream=0):
+        """``og_batch_eval_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_X`` ``[count, n]``, ``d_F`` ``[count, m]``."""
+        _native.check(self._lib.og_batch_eval_dev(self._handle, int(count), d_X, d_F, stream), "og_batch_eval_dev")
+
+    def sweep_dev(self, count, d_X, d_H, d_F0, d_vals=None, stream=0):
+        """``og_batch_fd_sweep_dev``: ``d_X``, ``d_H`` ``[count, n]``, ``d_F0`` ``[count, m]``, ``d_vals``
+        ``[count, nnz]`` or None."""
+        _native.check(self._lib.og_batch_fd_sweep_dev(self._handle, int(count), d_X, d_H, d_F0, d_vals, stream),
+                      "og_batch_fd_sweep_dev")

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import trace as _tr
 
-__all__ = ["Problem", "Guess", "Condition", "Dynamics"]
+__all__ = ["Problem", "Guess", "Condition", "Dynamics", "BatchResult"]
 
 # Callable ``factory(prob, obj) -> engine`` used by ``Problem.solve``.  ``None`` selects the HIP
 # engine.  The test-suite swaps in the NumPy oracle here to exercise host logic without a GPU
@@ -48,6 +48,28 @@ def _default_engine(prob, obj, devices=None):
 
 def _noop():
     pass
+
+
+class BatchResult:
+    """What :meth:`Problem.evaluate_batch` returns for ``B`` points: ``cost[B]``, ``equality[B, m_eq]``,
+    ``inequality[B, m_ineq]`` and ``violation[B]`` - SLSQP's measure of infeasibility, ``sum |c_eq| +
+    sum max(-c_ineq, 0)`` - and, when the Jacobians were asked for, ``gradient[B, n]`` (the cost gradient),
+    ``steps[B, n]`` (the signed forward-difference steps), ``values[B, nnz]`` (the structural non-zeros of every
+    point's transposed Jacobian ``J_T[j, r] = dF_r/dx_j`` of ``F = [cost | c_eq | c_ineq]``) and ``pattern =
+    (indptr, rows)``: the entries of column ``j`` are ``values[:, indptr[j]:indptr[j + 1]]``, their rows
+    ``rows[indptr[j]:indptr[j + 1]]``.  ``nonfinite[B]`` counts the non-finite rows of ``F`` per point."""
+
+    def __init__(self, F, m_eq):
+        F = np.asarray(F, dtype=float)
+        self.cost = F[:, 0].copy()
+        self.equality = F[:, 1:1 + m_eq].copy()
+        self.inequality = F[:, 1 + m_eq:].copy()
+        self.violation = np.sum(np.abs(self.equality), axis=1) + np.sum(np.maximum(-self.inequality, 0.0), axis=1)
+        self.nonfinite = np.sum(~np.isfinite(F), axis=1).astype(np.int32)
+        self.gradient = self.steps = self.values = self.pattern = None
+
+    def __len__(self):
+        return self.cost.shape[0]
 
 
 class Problem:
@@ -430,6 +452,14 @@ class Problem:
             import warnings
             warnings.warn("Problem.solve: devices=%r is not used with a stand-in engine" % (list(devices),),
                           RuntimeWarning, stacklevel=2)
+        # lanes of an earlier evaluate_batch (B dense matrices on the device) do not live through the solve, nor does the
+        # engine evaluate_batch built for them: this solve makes its own
+        stale = self.__dict__.pop("_batch", None)
+        if stale is not None:
+            stale.close()
+        if self.__dict__.pop("_engine_of_batch", False) and getattr(self, "_engine", None) is not None \
+                and hasattr(self._engine, "close"):
+            self._engine.close()
         if ENGINE_FACTORY is not None:
             engine = ENGINE_FACTORY(self, obj)
         else:
@@ -508,6 +538,82 @@ class Problem:
             if not opt.status:
                 break
             self.iterator += 1
+
+    # ------------------------------------------------------------------ many points at once
+    def evaluate_batch(self, obj, points, jacobian=False):
+        """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
+        guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
+        shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
+        ``jacobian=True`` adds the forward-difference Jacobians SLSQP would see at every point (SciPy's step rule with
+        this problem's bounds).  Returns a :class:`BatchResult`; every row of it is bit for bit what the single-point
+        path (``engine.values`` / ``engine.jacobians``) gives.  The reference has no counterpart (one ``Problem``, one
+        ``solve``): per point this replaces what ``solve`` replaces (``optimize.py:670-733``).  ``self.p`` is left alone.
+
+        The engine of an earlier ``solve`` is reused when there is one.  A stand-in engine (``ENGINE_FACTORY``) without
+        a ``batch`` method is served point by point through its ``values`` / ``jacobians``."""
+        points = np.asarray(points, dtype=float)
+        assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
+        assert points.shape[1] == self.number_of_variables, \
+            "points must have %d columns (number_of_variables), got %d" % (self.number_of_variables, points.shape[1])
+        assert points.shape[0] >= 1, "points holds no point"
+        assert len(self.dynamics) != 0, "It must be set dynamics"
+        assert self.cost is not None, "It must be set cost function"
+        assert self.equality is not None, "It must be set equality function"
+        assert self.inequality is not None, "It must be set inequality function"
+
+        engine = getattr(self, "_engine", None)
+        if engine is None:
+            engine = ENGINE_FACTORY(self, obj) if ENGINE_FACTORY is not None else _default_engine(self, obj)
+            self._engine = engine
+            self._engine_of_batch = True         # (solve closes an engine that was only made for batches)
+        points = np.ascontiguousarray(points)
+        B, n = points.shape
+        lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
+        ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
+
+        if not hasattr(engine, "batch"):
+            saved = self.p
+            try:
+                if not jacobian:
+                    rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
+                            for p in points]
+                    return BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[0])[1]).size))
+                rows, dense, steps = [], [], []
+                for p in points:
+                    (grad, jeq, jineq), h = engine.jacobians(p, lb, ub)
+                    rows.append(np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)]))
+                    dense.append(np.vstack([np.atleast_2d(grad), np.atleast_2d(jeq), np.atleast_2d(jineq)]).T.copy())
+                    steps.append(np.array(h, dtype=float, copy=True))
+                m_eq = int(np.atleast_2d(jeq).shape[0])
+            finally:
+                self.p = saved
+            res = BatchResult(np.stack(rows), m_eq)
+            m = rows[0].size
+            # a stand-in knows no pattern: every entry of the dense matrix is one
+            res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
+            res.values = np.stack([d.reshape(-1) for d in dense])
+            res.gradient = np.stack([d[:, 0] for d in dense])
+            res.steps = np.stack(steps)
+            return res
+
+        batch = getattr(self, "_batch", None)
+        if batch is None or batch.engine is not engine or batch.capacity < B or not batch._handle.value:
+            if batch is not None:
+                batch.close()
+            batch = self._batch = engine.batch(B)
+        if not jacobian:
+            return BatchResult(batch.values(points), engine.m_eq)
+        F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
+        res = BatchResult(F0, engine.m_eq)
+        indptr, rows = batch.pattern
+        res.pattern, res.values, res.steps = (indptr, rows), vals, H
+        # column 0 of J_T: the pattern entries whose row is the cost
+        res.gradient = np.zeros((B, n))
+        at = np.flatnonzero(rows == 0)
+        res.gradient[:, np.searchsorted(indptr, at, side="right") - 1] = vals[:, at]
+        for k in np.flatnonzero(nonfinite):          # (NaN rows fill every column: the packed form cannot say so)
+            res.gradient[k] = batch.dense(k)[:, 0]
+        return res
 
     # ------------------------------------------------------------------ reporting
     def __repr__(self):
