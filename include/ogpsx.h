@@ -288,6 +288,31 @@ int og_jacobian_exact(og_handle h, const double* x, int32_t col_lo, int32_t col_
 int og_jacobian_exact_dev(og_handle h, const double* d_x, int32_t col_lo, int32_t col_hi, double* d_JT,
                           double* d_F0, void* hip_stream);
 
+/* ---- exact Jacobian of a batch of points -----------------------------------------------------------
+ * og_jacobian_exact_batch(_dev) is og_jacobian_exact(_dev) over all n columns at `count` points of a batch in one call:
+ * three launches whatever `count` is (where the arrays are, the batched evaluation, the batched derivative kernel, which
+ * also writes every lane's packed non-zeros) in place of count times og_jacobian_exact_dev + og_pack_dev.  Lane k's F0,
+ * packed values and dense matrix (og_batch_lane_dev) are, bit for bit, what the single-point path gives at X[k]; per
+ * point it replaces the same 3n+2 evaluations of `approx_derivative` (`scipy/optimize/_slsqp_py.py:299-313`).
+ * NaN rule: a lane's results are the single-point path's at that point - F0 with its non-finite rows, nonfinite[k]
+ * their count, and in the matrix what the exact kernel computes there (it does not fill rows with NaN as the FD sweep
+ * does).  A lane that an FD sweep at a bad point left with a NaN fill is cleaned by its next exact call.
+ * Load rule: the kernel lives in a part of the callback module of its own, neither in the module nor in the batch part
+ * (exact_part_path: opengoddard_amd.build.build_batch_exact_part).  og_jacobian_exact_batch_load loads it once per
+ * handle - a later call on any batch of the handle is a no-op and may pass NULL - and og_problem_destroy closes it;
+ * error 4: the part is missing or cannot be loaded, 5: it belongs to another module.  The other two fail with error 4
+ * while it is not loaded, except under OGPSX_SWEEP=dense, the validation form (batched evaluation, then the handle's
+ * dense exact kernel and the pack lane by lane), which does not need it.
+ * _dev: device pointers, asynchronous on hip_stream, capturable; d_X [count][n], d_F0 [count][m], d_vals [count][nnz]
+ * in og_pattern's order or NULL (the lanes' matrices are then the result).  Host form: blocking; F0 and vals are
+ * written in place when both lie in page-locked memory the device can address, staged otherwise; nonfinite: [count]
+ * or NULL. */
+int og_jacobian_exact_batch_load(og_batch b, const char* exact_part_path);
+int og_jacobian_exact_batch_dev(og_batch b, int32_t count, const double* d_X, double* d_F0, double* d_vals,
+                                void* hip_stream);
+int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* F0, double* vals,
+                            int32_t* nonfinite);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

@@ -174,6 +174,33 @@ def build_batch_part(header_source, force=False):
     return out
 
 
+BATCH_EXACT_PART = 5            # OGK_PART of <module>.batchx.so: the exact Jacobian of a batch (og_jacobian_exact_batch*)
+
+
+def batch_exact_part_path(out):
+    return out[:-3] + ".batchx.so"
+
+
+def build_batch_exact_part(header_source, force=False):
+    """Compile ``ogk_exact_struct_batch`` (csrc/ogk_kernels.hip, ``OGK_PART=5``) against one generated header -> path
+    of ``<module>.batchx.so``, next to the module of the same digest and cached like it.  A part of its own, neither
+    one of ``MODULE_PARTS`` nor in the batch part: the kernel instantiates the callbacks on dual numbers, and a user
+    who batches evaluations or FD sweeps only builds and loads what they did before.  Built when an exact Jacobian of
+    a batch is first asked for (``BatchSweep.exact``)."""
+    os.makedirs(JITDIR, exist_ok=True)
+    digest = module_digest(header_source)
+    out = batch_exact_part_path(module_path(digest))
+    if not force and os.path.exists(out):
+        return out
+    header = _write_header(header_source, digest)
+    tmp = out + ".tmp%d" % os.getpid()
+    _run([hipcc()] + HIP_FLAGS + MODULE_FLAGS + ["-DOGK_PART=%d" % BATCH_EXACT_PART, "-I" + CSRC,
+                                                 "-DOG_GEN_HEADER=\"%s\"" % header,
+                                                 os.path.join(CSRC, "ogk_kernels.hip"), "-o", tmp])
+    os.replace(tmp, out)
+    return out
+
+
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):
     """Compile the sweep kernels against one generated header -> path of the module (its part 0; the other
     parts are built next to it, in parallel).  ``out_suffix``: write the result next to the cached module instead

@@ -122,6 +122,10 @@ int ogk_launch(const ogk_args* args, int mode, void* stream);
 // exported by the batch part of a module only (OGK_PART == 4, built when a batch is first asked for).
 // mode 11: ogk_fused over all n columns for `count` lanes in one launch.  mode 12: ogk_eval for `count` lanes.
 // mode 13: bind the caller's arrays to the records (see above).
+// The exact batch part (OGK_PART == 5, <module>.batchx.so, built when a batched exact Jacobian is first asked for)
+// exports the same name for its one mode, and ogk_get_info.  mode 14: ogk_exact_struct over all n columns for `count`
+// lanes in one launch, on record set 2 after a mode-12 launch on the same set (which counts the launch into each
+// lane's *jt_launches); every value also goes to its place in the lane's packed array when the record's pvals is set.
 int ogk_launch_batch(const ogk_batch_args* args, int mode, void* stream);
 #ifdef __cplusplus
 }

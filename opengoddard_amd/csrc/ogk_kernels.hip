@@ -195,6 +195,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #if defined(OGK_PART) && OGK_PART == 4
 #define OGK_HAS_BATCH 1      // modes 11 - 13: a batch of points per launch; never part of a module's default build
 #endif
+#if defined(OGK_PART) && OGK_PART == 5
+#define OGK_HAS_BATCH_EXACT 1    // mode 14: the exact Jacobian of a batch of points; a part of its own, built on demand
+#endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
 // ------------------------------------------------------------------------------------------
@@ -1546,13 +1549,15 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // through the constant address space (scalar loads, as it reads a launch's argument block) - a copy of a 500-byte
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
-#ifdef OGK_HAS_BATCH
+#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
     return *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.y);
 }
+#endif
 
+#ifdef OGK_HAS_BATCH
 __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused_batch(const ogk_args* __restrict__ lanes,
                                                                  const int ndef, const int n_eval, const int group_lo,
                                                                  const int n_light, const int sum_lo, const int n_sum) {
@@ -1586,6 +1591,81 @@ __global__ void ogk_batch_bind(const ogk_batch_args b) {
     a.f0 = b.F0 + (long)k * OgGen::M;
     a.pvals = b.vals ? b.vals + (long)k * b.nnz : nullptr;
     if (i / b.capacity == b.clear_set && k < b.count) *a.nonfinite = 0;
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Mode 14 (the exact batch part, OGK_PART == 5): ogk_exact_struct for B points in one launch, lane = blockIdx.y.  Per
+// column it computes what ogk_exact_struct computes - every entry by one thread from x0, y0, cvec and dfrag alone, so
+// who computes an entry cannot change a bit of it - and also stores each value at its place of the lane's packed array
+// (pattern order: the own block's row k is entry k, item e is entry own + (e - first item)), so no pack launch follows.
+// Mapping: a column has a few dozen entries, a phase's final time a thousand.  The columns the tracer marked heavy
+// (HEAVY_FLAG, OGT_HEAVY: longest first) get a workgroup each and lead the grid; every other column gets ONE wavefront,
+// four columns per workgroup - a workgroup per column would leave three of four wavefronts without work on almost
+// every column and make the grid four times as long, times B.
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_BATCH_EXACT
+constexpr int XB_THREADS = 256;
+constexpr int XB_COLS = XB_THREADS / 64;            // ordinary columns per workgroup: one per wavefront
+
+// column j by the `width` threads that share it; t = this thread's index among them.  (One copy of the callbacks'
+// dual-number code for both widths: it is what the part's build time and the kernel's registers consist of.)
+__device__ __forceinline__ void exact_column(const ogk_args& a, const int j, const int t, const int width) {
+    double* jrow = a.jt + (long)j * OgGen::M;
+    const XDual xd{a.x0, j};
+    const int4 rec = OGT_COL[j];
+    const int own_lo = rec.z, own_hi = rec.w & ~HEAVY_FLAG;
+    double* pcol = a.pvals ? a.pvals + a.poff[j] : nullptr;
+    double* pitem = pcol ? pcol + (own_hi - own_lo) - rec.x : nullptr;
+    for (int e = rec.x + t; e < rec.y; e += width) {
+        const int4 it = OGT_ELEM[e];
+        int row;
+        const ogdual v = OgGen::item_value(it.x, it.y, it.z, xd, a.y0, a.cvec, &row);
+        jrow[row] = v.d;
+        if (pitem) pitem[e] = v.d;
+    }
+    if (own_hi > own_lo) {
+        // x_j is node l of the state behind one collocation product
+        int si = -1, l = 0;
+        for (int s = 0; s < OgGen::N_MV; ++s) {
+            const int leaf = OGT_SLOT[s].v[2], len = OGT_SLOT[s].v[0];
+            if (j >= leaf && j < leaf + len) {
+                si = s;
+                l = j - leaf;
+            }
+        }
+        if (si >= 0) {
+            const int N = OGT_SLOT[si].v[0], phase = OGT_SLOT[si].v[5], row0 = OGT_SLOT[si].v[3];
+            const int reads = OGT_SLOT[si].v[6];            // (bits as in ogk_exact_struct)
+            const ogdual op = OgGen::mv_operand(si, l, xd, a.cvec);
+            for (int k = t; k < N; k += width) {
+                double v = __builtin_fma(op.d, dfrag_entry(a, phase, N, k, l), 0.0);
+                if ((reads & 2) || ((reads & 1) && k == l)) v = v - OgGen::tail_one(si, k, xd, a.cvec).d;
+                jrow[row0 + k] = v;
+                if (pcol) pcol[row0 - own_lo + k] = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(XB_THREADS) void ogk_exact_struct_batch(const ogk_args* __restrict__ lanes) {
+    const ogk_args& a = batch_lane(lanes);
+    const int id = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const bool heavy = id < OgGen::N_HEAVY;
+    // heavy: the workgroup's column; else the wavefront's (none past the end, and the heavy ones have their own)
+    // (the same in all 64 lanes of a wavefront - said to the compiler, so that the column's tables stay scalar loads)
+    int j = heavy ? OGT_HEAVY[id] : (id - OgGen::N_HEAVY) * XB_COLS + __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (!heavy && (j >= OgGen::N_VAR || (OGT_COL[j].w & HEAVY_FLAG))) j = -1;
+    if (jt_needs_fill(a)) {                     // the same for every workgroup of the lane
+        if (j >= 0) {
+            double* jrow = a.jt + (long)j * OgGen::M;
+            if (heavy) for (int r = tid; r < OgGen::M; r += XB_THREADS) jrow[r] = 0.0;
+            else for (int r = tid & 63; r < OgGen::M; r += 64) jrow[r] = 0.0;
+        }
+        __syncthreads();                        // the zeros of a row before its entries
+    }
+    if (j < 0) return;
+    exact_column(a, j, heavy ? tid : (tid & 63), heavy ? XB_THREADS : 64);
 }
 #endif
 
@@ -1874,5 +1954,18 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
         return (int)hipGetLastError();
     }
     return (int)hipErrorInvalidValue;
+}
+#endif
+
+#ifdef OGK_HAS_BATCH_EXACT
+// the exact batch part's only mode: it exports the same entry name as the batch part and is looked up in its own
+// shared object
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || mode != 14) return (int)hipErrorInvalidValue;
+    const int grid = OgGen::N_HEAVY + (OgGen::N_VAR + XB_COLS - 1) / XB_COLS;
+    hipLaunchKernelGGL(ogk_exact_struct_batch, dim3(grid, b->count), dim3(XB_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes);
+    return (int)hipGetLastError();
 }
 #endif

@@ -183,6 +183,9 @@ struct og_problem_s {
     void* batch_module = nullptr;
     ogk_launch_batch_fn batch_launch = nullptr;
     std::vector<og_batch_s*> batches;
+    // the exact Jacobian of a batch (og_jacobian_exact_batch_load): a part of its own, loaded when first asked for
+    void* batch_exact_module = nullptr;
+    ogk_launch_batch_fn batch_exact_launch = nullptr;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -708,6 +711,7 @@ void og_problem_destroy(og_handle p) {
     hipSetDevice(p->device);
     while (!p->batches.empty()) og_batch_destroy(p->batches.back());
     if (p->batch_module) dlclose(p->batch_module);
+    if (p->batch_exact_module) dlclose(p->batch_exact_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -1626,6 +1630,108 @@ int og_batch_fd_sweep(og_batch b, int32_t count, const double* X, const double* 
     OG_HIP(hipStreamSynchronize(p->stream));
     if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
     memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
+    if (nonfinite)
+        for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
+    return 0;
+}
+
+// ---- the exact Jacobian of a batch (include/ogpsx.h) ----
+int og_jacobian_exact_batch_load(og_batch b, const char* exact_part_path) {
+    if (!b) return fail(1, "og_jacobian_exact_batch_load: null batch");
+    if (!live_batch(b)) return fail(1, "og_jacobian_exact_batch_load: the batch or its handle has been destroyed");
+    og_problem_s* p = b->p;
+    if (p->batch_exact_launch) return 0;
+    if (!exact_part_path)
+        return fail(4, "og_jacobian_exact_batch_load: the module's exact batch part is not loaded and no path was given");
+    void* mod = dlopen(exact_part_path, RTLD_NOW | RTLD_LOCAL);
+    if (!mod) return fail(4, std::string("og_jacobian_exact_batch_load: dlopen of the exact batch part failed: ") + dlerror());
+    ogk_get_info_fn get_info = (ogk_get_info_fn)dlsym(mod, "ogk_get_info");
+    ogk_launch_batch_fn fn = (ogk_launch_batch_fn)dlsym(mod, "ogk_launch_batch");
+    ogk_info info;
+    memset(&info, 0, sizeof info);
+    if (get_info && fn) get_info(&info);
+    if (!get_info || !fn || info.abi != OGK_ABI || info.n != p->n || info.m != p->m || info.m_eq != p->m_eq ||
+        info.n_eval_blocks != p->n_eval_blocks) {
+        dlclose(mod);
+        return fail(5, "og_jacobian_exact_batch_load: the exact batch part does not belong to the handle's module");
+    }
+    p->batch_exact_module = mod;
+    p->batch_exact_launch = fn;
+    return 0;
+}
+
+int og_jacobian_exact_batch_dev(og_batch b, int32_t count, const double* d_X, double* d_F0, double* d_vals,
+                                void* hip_stream) {
+    int rc = batch_check(b, count, "og_jacobian_exact_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_F0) return fail(1, "og_jacobian_exact_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    const bool dense = p->exact_mode == 3;
+    if (!dense && !p->batch_exact_launch)
+        return fail(4, "og_jacobian_exact_batch_dev: the module's exact batch part is not loaded "
+                       "(og_jacobian_exact_batch_load)");
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 2: the evaluation counts one launch into every lane's *jt_launches, as the evaluation of
+    // og_jacobian_exact_dev does for a registered buffer
+    const int set = 2;
+    rc = batch_bind(b, count, d_X, nullptr, d_F0, d_vals, set, s, "og_jacobian_exact_batch_dev");
+    if (rc) return rc;
+    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
+    ogk_batch_args ba;
+    memset(&ba, 0, sizeof ba);
+    ba.lanes = batch_set(b, set);
+    ba.count = count;
+    ba.capacity = b->capacity;
+    rc = p->batch_launch(&ba, 12, s);               // F(X[k]) and the base collocation products of every lane
+    if (!rc && !dense) rc = p->batch_exact_launch(&ba, 14, s);      // every lane's derivatives and packed values
+    // the validation form (OGPSX_SWEEP=dense): the handle's dense exact kernel and the pack, lane by lane
+    for (int k = 0; dense && !rc && k < count; ++k) {
+        ogk_args a = b->table[(size_t)set * (size_t)b->capacity + (size_t)k];
+        a.x0 = d_X + (size_t)k * (size_t)p->n;
+        a.f0 = d_F0 + (size_t)k * (size_t)p->m;
+        rc = p->launch(&a, 3, s);
+        if (!rc && d_vals) {
+            a.pind = p->d_indptr;
+            a.prow = p->d_rows;
+            a.pvals = d_vals + (size_t)k * (size_t)b->nnz;
+            rc = p->launch(&a, 8, s);
+        }
+    }
+    if (rc) return launch_failed(p, rc, "og_jacobian_exact_batch_dev");
+    return 0;
+}
+
+int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* F0, double* vals,
+                            int32_t* nonfinite) {
+    int rc = batch_check(b, count, "og_jacobian_exact_batch");
+    if (rc) return rc;
+    if (!X || !F0 || !vals) return fail(1, "og_jacobian_exact_batch: null argument");
+    og_problem_s* p = b->p;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    const size_t nnz = (size_t)b->nnz;
+    memcpy(b->h_up, X, sizeof(double) * c * n);
+    OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
+    // F0 and vals in page-locked memory the device can address: written in place, as og_batch_fd_sweep does
+    void *m_f = nullptr, *m_vals = nullptr;
+    if (hipHostGetDevicePointer(&m_f, F0, 0) != hipSuccess || hipHostGetDevicePointer(&m_vals, vals, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        m_f = m_vals = nullptr;
+    }
+    const bool in_place = m_f && m_vals;
+    rc = og_jacobian_exact_batch_dev(b, count, b->d_xh, in_place ? (double*)m_f : b->d_f,
+                                     in_place ? (double*)m_vals : b->d_vals, p->stream);
+    if (rc) return rc;
+    if (!in_place) {
+        if (nnz) OG_HIP(hipMemcpyAsync(b->h_down, b->d_vals, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, p->stream));
+        OG_HIP(hipMemcpyAsync(b->h_down + cap * nnz, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    }
+    OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    if (!in_place) {
+        if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
+        memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
+    }
     if (nonfinite)
         for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
     return 0;

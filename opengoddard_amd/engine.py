@@ -269,6 +269,7 @@ class BatchSweep:
         self.capacity = int(self._lib.og_batch_capacity(self._handle))
         self._pattern = None
         self._pinned = None             # page-locked result arrays of sweep(persistent=True), made when first asked for
+        self.exact_part_path = None     # the module's exact batch part: built and loaded by the first exact call
         engine._batches.append(self)
 
     def close(self):
@@ -310,6 +311,45 @@ class BatchSweep:
                       "og_batch_eval")
         return F
 
+    def _result_arrays(self, B, persistent):
+        """``(F0[B, m], vals[B, nnz])``: fresh arrays, or - ``persistent`` - views of the batch's own page-locked result
+        arrays (made when first asked for; fresh arrays when the runtime gives no such memory)."""
+        if persistent and 1 <= B <= self.capacity:
+            if self._pinned is None:
+                both = _native.pinned_matrix(self.capacity, self.m + self.nnz)
+                self._pinned = False if both is None else (both.reshape(-1)[:self.capacity * self.m],
+                                                           both.reshape(-1)[self.capacity * self.m:])
+            if self._pinned:
+                return (self._pinned[0][:B * self.m].reshape(B, self.m),
+                        self._pinned[1][:B * self.nnz].reshape(B, self.nnz))
+        return np.empty((B, self.m)), np.empty((B, self.nnz))
+
+    def _load_exact(self):
+        if self.exact_part_path is None:
+            path = build.build_batch_exact_part(self.engine.header)
+            _native.check(self._lib.og_jacobian_exact_batch_load(self._handle, path.encode()),
+                          "og_jacobian_exact_batch_load")
+            self.exact_part_path = path
+
+    def exact(self, P, persistent=False):
+        """``(F0[B, m], vals[B, nnz], nonfinite[B])`` like :meth:`sweep`, but ``vals[k]`` are the EXACT derivatives at
+        ``P[k]`` (forward-mode differentiation of the traced callbacks, ``og_jacobian_exact_batch``): bit for bit
+        :meth:`HipEngine.exact_stacked` at that point, gathered at the pattern's entries - no step, no FD noise.  One
+        call is three launches whatever ``B`` is.  A lane whose ``F`` has non-finite rows (``nonfinite[k]``) holds what
+        the single-point path computes there; the exact kernel does not fill rows with NaN.  The kernel is a part of
+        the callback module of its own, compiled and loaded by the first call (``build.build_batch_exact_part``).
+        ``persistent`` as in :meth:`sweep`."""
+        P = self._points(P)
+        B = P.shape[0]
+        self._load_exact()
+        F0, vals = self._result_arrays(B, persistent)
+        nonfinite = np.zeros(B, dtype=np.int32)
+        _native.check(self._lib.og_jacobian_exact_batch(self._handle, B, _native.dptr(P), _native.dptr(F0),
+                                                        _native.dptr(vals),
+                                                        nonfinite.ctypes.data_as(C.POINTER(C.c_int32))),
+                      "og_jacobian_exact_batch")
+        return F0, vals, nonfinite
+
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):
         ``vals[k]`` are the structural non-zeros of lane ``k``'s J_T in ``pattern`` order.  ``nonfinite[k]`` is the
@@ -323,21 +363,7 @@ class BatchSweep:
         if H.shape != P.shape:
             raise ValueError("BatchSweep: P and H differ in shape: %s, %s" % (P.shape, H.shape))
         B = P.shape[0]
-        if persistent and 1 <= B <= self.capacity:
-            if self._pinned is None:
-                both = _native.pinned_matrix(self.capacity, self.m + self.nnz)
-                self._pinned = False if both is None else (both.reshape(-1)[:self.capacity * self.m],
-                                                           both.reshape(-1)[self.capacity * self.m:])
-            if self._pinned:
-                F0 = self._pinned[0][:B * self.m].reshape(B, self.m)
-                vals = self._pinned[1][:B * self.nnz].reshape(B, self.nnz)
-            else:
-                persistent = False
-        else:
-            persistent = False
-        if not persistent:
-            F0 = np.empty((B, self.m))
-            vals = np.empty((B, self.nnz))
+        F0, vals = self._result_arrays(B, persistent)
         nonfinite = np.zeros(B, dtype=np.int32)
         _native.check(self._lib.og_batch_fd_sweep(self._handle, B, _native.dptr(P), _native.dptr(H), _native.dptr(F0),
                                                   _native.dptr(vals), nonfinite.ctypes.data_as(C.POINTER(C.c_int32))),
@@ -375,3 +401,10 @@ class BatchSweep:
         ``[count, nnz]`` or None."""
         _native.check(self._lib.og_batch_fd_sweep_dev(self._handle, int(count), d_X, d_H, d_F0, d_vals, stream),
                       "og_batch_fd_sweep_dev")
+
+    def exact_dev(self, count, d_X, d_F0, d_vals=None, stream=0):
+        """``og_jacobian_exact_batch_dev``: ``d_X`` ``[count, n]``, ``d_F0`` ``[count, m]``, ``d_vals`` ``[count, nnz]``
+        or None (the lanes' dense matrices are then the result)."""
+        self._load_exact()
+        _native.check(self._lib.og_jacobian_exact_batch_dev(self._handle, int(count), d_X, d_F0, d_vals, stream),
+                      "og_jacobian_exact_batch_dev")

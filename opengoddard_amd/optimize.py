@@ -57,7 +57,10 @@ class BatchResult:
     ``steps[B, n]`` (the signed forward-difference steps), ``values[B, nnz]`` (the structural non-zeros of every
     point's transposed Jacobian ``J_T[j, r] = dF_r/dx_j`` of ``F = [cost | c_eq | c_ineq]``) and ``pattern =
     (indptr, rows)``: the entries of column ``j`` are ``values[:, indptr[j]:indptr[j + 1]]``, their rows
-    ``rows[indptr[j]:indptr[j + 1]]``.  ``nonfinite[B]`` counts the non-finite rows of ``F`` per point."""
+    ``rows[indptr[j]:indptr[j + 1]]``.  ``nonfinite[B]`` counts the non-finite rows of ``F`` per point.
+    ``jacobian`` says what ``values`` and ``gradient`` hold: ``None`` (no Jacobians were asked for), ``"fd"`` (forward
+    differences) or ``"exact"`` (forward-mode derivatives of the traced callbacks; there is no step, ``steps`` is
+    ``None``)."""
 
     def __init__(self, F, m_eq):
         F = np.asarray(F, dtype=float)
@@ -67,6 +70,7 @@ class BatchResult:
         self.violation = np.sum(np.abs(self.equality), axis=1) + np.sum(np.maximum(-self.inequality, 0.0), axis=1)
         self.nonfinite = np.sum(~np.isfinite(F), axis=1).astype(np.int32)
         self.gradient = self.steps = self.values = self.pattern = None
+        self.jacobian = None
 
     def __len__(self):
         return self.cost.shape[0]
@@ -544,13 +548,18 @@ class Problem:
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
-        ``jacobian=True`` adds the forward-difference Jacobians SLSQP would see at every point (SciPy's step rule with
-        this problem's bounds).  Returns a :class:`BatchResult`; every row of it is bit for bit what the single-point
-        path (``engine.values`` / ``engine.jacobians``) gives.  The reference has no counterpart (one ``Problem``, one
-        ``solve``): per point this replaces what ``solve`` replaces (``optimize.py:670-733``).  ``self.p`` is left alone.
+        ``jacobian=True`` (or ``"fd"``) adds the forward-difference Jacobians SLSQP would see at every point (SciPy's
+        step rule with this problem's bounds); ``jacobian="exact"`` adds the exact ones instead - forward-mode
+        derivatives of the traced callbacks, the ``jacobian="exact"`` of :meth:`solve`, without a step and its noise
+        (``BatchResult.steps`` is then ``None``).  Any other string is a ``ValueError``; the environment's
+        ``OG_JACOBIAN`` is not consulted here.  Returns a :class:`BatchResult`; every row of it is bit for bit what the
+        single-point path (``engine.values`` / ``engine.jacobians`` / ``engine.exact_stacked``) gives.  The reference has
+        no counterpart (one ``Problem``, one ``solve``): per point this replaces what ``solve`` replaces
+        (``optimize.py:670-733``).  ``self.p`` is left alone.
 
         The engine of an earlier ``solve`` is reused when there is one.  A stand-in engine (``ENGINE_FACTORY``) without
-        a ``batch`` method is served point by point through its ``values`` / ``jacobians``."""
+        a ``batch`` method is served point by point through its ``values`` / ``jacobians`` (``exact_stacked`` for the
+        exact Jacobians: an engine without one has no exact mode, a ``ValueError``)."""
         points = np.asarray(points, dtype=float)
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
@@ -560,6 +569,11 @@ class Problem:
         assert self.cost is not None, "It must be set cost function"
         assert self.equality is not None, "It must be set equality function"
         assert self.inequality is not None, "It must be set inequality function"
+        if isinstance(jacobian, str):
+            if jacobian not in ("fd", "exact"):
+                raise ValueError("jacobian must be 'fd' or 'exact', got %r" % (jacobian,))
+        else:
+            jacobian = "fd" if jacobian else None
 
         engine = getattr(self, "_engine", None)
         if engine is None:
@@ -570,6 +584,8 @@ class Problem:
         B, n = points.shape
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
+        if jacobian == "exact" and not hasattr(engine, "exact_stacked"):
+            raise ValueError("this engine has no exact-Jacobian mode")
 
         if not hasattr(engine, "batch"):
             saved = self.p
@@ -579,12 +595,19 @@ class Problem:
                             for p in points]
                     return BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[0])[1]).size))
                 rows, dense, steps = [], [], []
-                for p in points:
-                    (grad, jeq, jineq), h = engine.jacobians(p, lb, ub)
-                    rows.append(np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)]))
-                    dense.append(np.vstack([np.atleast_2d(grad), np.atleast_2d(jeq), np.atleast_2d(jineq)]).T.copy())
-                    steps.append(np.array(h, dtype=float, copy=True))
-                m_eq = int(np.atleast_2d(jeq).shape[0])
+                if jacobian == "exact":
+                    for p in points:
+                        F0, JT = engine.exact_stacked(p)
+                        rows.append(np.array(F0, dtype=float, copy=True))
+                        dense.append(np.array(JT, dtype=float, copy=True))
+                    m_eq = int(np.atleast_1d(engine.values(points[0])[1]).size)
+                else:
+                    for p in points:
+                        (grad, jeq, jineq), h = engine.jacobians(p, lb, ub)
+                        rows.append(np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)]))
+                        dense.append(np.vstack([np.atleast_2d(grad), np.atleast_2d(jeq), np.atleast_2d(jineq)]).T.copy())
+                        steps.append(np.array(h, dtype=float, copy=True))
+                    m_eq = int(np.atleast_2d(jeq).shape[0])
             finally:
                 self.p = saved
             res = BatchResult(np.stack(rows), m_eq)
@@ -593,7 +616,8 @@ class Problem:
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
             res.values = np.stack([d.reshape(-1) for d in dense])
             res.gradient = np.stack([d[:, 0] for d in dense])
-            res.steps = np.stack(steps)
+            res.steps = np.stack(steps) if jacobian == "fd" else None
+            res.jacobian = jacobian
             return res
 
         batch = getattr(self, "_batch", None)
@@ -603,15 +627,20 @@ class Problem:
             batch = self._batch = engine.batch(B)
         if not jacobian:
             return BatchResult(batch.values(points), engine.m_eq)
-        F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
+        if jacobian == "exact":
+            F0, vals, nonfinite = batch.exact(points)
+            H = None
+        else:
+            F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
         indptr, rows = batch.pattern
-        res.pattern, res.values, res.steps = (indptr, rows), vals, H
+        res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost
         res.gradient = np.zeros((B, n))
         at = np.flatnonzero(rows == 0)
         res.gradient[:, np.searchsorted(indptr, at, side="right") - 1] = vals[:, at]
-        for k in np.flatnonzero(nonfinite):          # (NaN rows fill every column: the packed form cannot say so)
+        # (FD: NaN rows fill every column, which the packed form cannot say; the exact kernel writes pattern entries only)
+        for k in np.flatnonzero(nonfinite) if jacobian == "fd" else ():
             res.gradient[k] = batch.dense(k)[:, 0]
         return res
 

@@ -13,7 +13,13 @@ B x ``HipEngine.sweep_persistent``) are timed with the host clock around the blo
 timed twice: with the same four arrays on every call, and with arrays that change from call to call (the library binds
 the arrays to the lanes with a small launch ahead of every batched launch either way).  On a tree without batches the
 batch legs are skipped and the single-point legs remain (the baseline of an older commit).  ``--merge`` /
-``--merge-parent`` put the result files of several runs into one.  B is limited by the device's free memory (every lane owns a dense n x m matrix)."""
+``--merge-parent`` put the result files of several runs into one.  B is limited by the device's free memory (every lane owns a dense n x m matrix).
+
+``--exact`` measures the exact Jacobians instead (device-pointer forms only; result file profiles/batch_exact.json): one
+og_jacobian_exact_batch_dev call with packed values against B consecutive og_jacobian_exact_dev calls into B registered
+buffers, each followed by the og_pack_dev launch the batched kernel makes unnecessary - and against the same calls
+without the pack - with the batched FD sweep of the same points alternating in the same rounds (what exactness costs per
+point).  On a tree without the batched exact form the single-point legs remain (the baseline of the parent commit)."""
 import argparse
 import json
 import os
@@ -47,6 +53,67 @@ def stats(samples_us, per):
             "intervals": int(s.size)}
 
 
+def exact_legs(a, eng, timed, stream_obj, stream, dev, B, X, d_X, d_H, d_F, d_JT, has_batch):
+    """The ``--exact`` legs of one (size, B): the forms alternate ``--rounds`` times -> the result row."""
+    import torch
+    from opengoddard_amd import _native
+    n, m = eng.n, eng.m
+    nnz = int(eng.pattern()[0][-1])
+    with torch.cuda.stream(stream_obj):
+        d_P = torch.empty((B, nnz), dtype=torch.float64, device=dev)
+    ptrs = [(d_X[k].data_ptr(), d_JT[k].data_ptr(), d_F[k].data_ptr(), d_P[k].data_ptr()) for k in range(B)]
+
+    def singles():
+        for px, pj, pf, _pp in ptrs:
+            eng.exact_dev(px, 0, n, pj, pf, stream)
+
+    def singles_packed():
+        for px, pj, pf, pp in ptrs:
+            eng.exact_dev(px, 0, n, pj, pf, stream)
+            _native.check(eng._lib.og_pack_dev(eng._handle, pj, 0, n, pp, stream), "og_pack_dev")
+
+    batch = eng.batch(B) if has_batch else None
+    has_exact = batch is not None and hasattr(batch, "exact_dev")
+    if batch is not None:
+        with torch.cuda.stream(stream_obj):
+            d_Fb = torch.empty((B, m), dtype=torch.float64, device=dev)
+            d_V = torch.empty((B, nnz), dtype=torch.float64, device=dev)
+            d_Ff = torch.empty((B, m), dtype=torch.float64, device=dev)
+            d_Vf = torch.empty((B, nnz), dtype=torch.float64, device=dev)
+
+        def fd_batched():
+            batch.sweep_dev(B, d_X.data_ptr(), d_H.data_ptr(), d_Ff.data_ptr(), d_Vf.data_ptr(), stream)
+
+        def batched():
+            batch.exact_dev(B, d_X.data_ptr(), d_Fb.data_ptr(), d_V.data_ptr(), stream)
+
+    single_us, packed_us, batch_us, fd_us = [], [], [], []
+    for _ in range(a.rounds):
+        packed_us += timed(singles_packed, a.reps, a.inner)
+        if has_exact:
+            batch_us += timed(batched, a.reps, a.inner)
+        single_us += timed(singles, a.reps, a.inner)
+        if batch is not None:
+            fd_us += timed(fd_batched, a.reps, a.inner)
+    row = {"exact_single_packed_dev": stats(packed_us, B), "exact_single_dev": stats(single_us, B)}
+    if batch is not None:
+        row["fd_batch_dev"] = stats(fd_us, B)
+    if has_exact:
+        row["exact_batch_dev"] = stats(batch_us, B)
+        # same results, at the size that was timed (the lanes' matrices hold the FD sweep's values by now: run once more)
+        with torch.cuda.stream(stream_obj):
+            singles_packed()
+            batched()
+        stream_obj.synchronize()
+        row["all_points_finite"] = bool(torch.isfinite(d_F).all())
+        row["bitwise_equal_F"] = bool(torch.equal(d_F, d_Fb))
+        row["bitwise_equal_packed_values"] = bool(torch.equal(d_P, d_V))
+        row["bitwise_equal_JT_lane0"] = bool(np.array_equal(batch.dense(0), d_JT[0].cpu().numpy()))
+    if batch is not None:
+        batch.close()
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", default="C1,C3,C4,C5")
@@ -55,6 +122,8 @@ def main():
     ap.add_argument("--inner", type=int, default=10, help="repetitions of the unit inside one interval")
     ap.add_argument("--rounds", type=int, default=3, help="alternations of the two forms")
     ap.add_argument("--host-reps", type=int, default=30)
+    ap.add_argument("--exact", action="store_true",
+                    help="the exact-Jacobian legs (og_jacobian_exact_batch_dev against B x og_jacobian_exact_dev + pack)")
     ap.add_argument("--commit", default=None, help="recorded in the result (default: git rev-parse HEAD)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--merge", nargs="+", metavar="JSON", default=None,
@@ -81,7 +150,9 @@ def main():
         if a.merge_parent:
             result["parent_commit"] = merged(a.merge_parent)
             result["parent_commit"]["note"] = ("the same tool on the parent commit's tree in the same lease: "
-                                               "single-point legs only, there are no batches there")
+                                               + ("the single-point exact legs and the FD batch, there is no batched "
+                                                  "exact form there" if result.get("exact") else
+                                                  "single-point legs only, there are no batches there"))
         with open(a.out, "w") as fh:
             fh.write(json.dumps(result, indent=1, sort_keys=True) + "\n")
         return
@@ -114,6 +185,10 @@ def main():
               "device": torch.cuda.get_device_name(0), "reps": a.reps, "inner": a.inner, "rounds": a.rounds,
               "baseline": "B consecutive og_fd_sweep_dev calls (one launch each) into B registered n x m buffers",
               "sizes": {}}
+    if a.exact:
+        result["exact"] = True
+        result["baseline"] = ("B consecutive og_jacobian_exact_dev calls (two launches each) into B registered n x m "
+                              "buffers, each followed by og_pack_dev (one launch); also without the pack")
     want_b = [int(v) for v in a.batches.split(",")]
     for tag in a.sizes.split(","):
         name = SIZES[tag]
@@ -149,6 +224,23 @@ def main():
                 for px, ph, pj, pf in ptrs:
                     eng.sweep_dev(px, ph, 0, n, pj, pf, stream)
 
+            if a.exact:
+                entry["by_batch"][str(B)] = row = exact_legs(a, eng, timed, stream_obj, stream, dev, B, X, d_X, d_H, d_F,
+                                                             d_JT, has_batch)
+                for k in range(B):
+                    eng.unregister_jt_dev(d_JT[k].data_ptr())
+                del d_JT
+                torch.cuda.empty_cache()
+                line = "%s B=%-2d exact: single+pack %8.2f us/point (p10 %.2f p90 %.2f), single %8.2f" % (
+                    tag, B, row["exact_single_packed_dev"]["us_per_point"], row["exact_single_packed_dev"]["p10_us"] / B,
+                    row["exact_single_packed_dev"]["p90_us"] / B, row["exact_single_dev"]["us_per_point"])
+                if "exact_batch_dev" in row:
+                    line += " | batch %8.2f us/point (p10 %.2f p90 %.2f), %8.2f us/call | FD batch %8.2f us/point" % (
+                        row["exact_batch_dev"]["us_per_point"], row["exact_batch_dev"]["p10_us"] / B,
+                        row["exact_batch_dev"]["p90_us"] / B, row["exact_batch_dev"]["us_per_launch"],
+                        row["fd_batch_dev"]["us_per_point"])
+                print(line, flush=True)
+                continue
             batch = d_V = None
             if has_batch:
                 batch = eng.batch(B)
