@@ -130,12 +130,13 @@ OG_HDI ogdual fmod_(const ogdual a, const ogdual b) {
 }
 OG_HDI ogdual fmod_(const ogdual a, const double b) { return ogdual(fmod_(a.v, b), a.d); }
 OG_HDI ogdual fmod_(const double a, const ogdual b) { return fmod_(ogdual(a), b); }
-// x ** y: d = x^y (y' log x + y x' / x); a part whose factor does not depend on the seeded variable stays out (0 log 0)
+// x ** y: d = x^y (y' log x + y x' / x); a part whose factor does not depend on the seeded variable stays out (0 log 0),
+// and so does the y' part where x^y is 0
 OG_HDI ogdual pow_(const ogdual x, const ogdual y) {
     const double p = pow_(x.v, y.v);
     double d = 0.0;
     if (x.d != 0.0) d += y.v * pow_(x.v, y.v - 1.0) * x.d;
-    if (y.d != 0.0) d += p * log_(x.v) * y.d;
+    if (y.d != 0.0 && p != 0.0) d += p * log_(x.v) * y.d;        // p == 0: x^y log x -> 0 (x = 0, y > 0), not 0 * -inf
     return ogdual(p, d);
 }
 OG_HDI ogdual pow_(const ogdual x, const double y) { return pow_(x, ogdual(y)); }

@@ -13,6 +13,12 @@
 // The reference calls NumPy ufuncs here (np.exp / np.sin / np.cos / np.sqrt, e.g.
 // examples/04_Goddard_0knot.py:35, examples/01_Brachistochrone_Problem.py:26-28); results agree
 // with NumPy to <= 1 ulp, which is inside the FD noise floor defined in SURVEY.md section 8(c).
+//
+// Measured against mpmath at every branch threshold, over the whole exponent range and at the special values
+// (tests/test_og_math_edges.py, figures in profiles/og_math_edges.md), in ulp of the correctly rounded result:
+// exp log sin cos atan asin acos cbrt hypot <= 0.75, tan <= 1.75, atan2 <= 1.35, log2 log10 <= 1.35,
+// expm1 log1p sinh cosh <= 1.5, tanh <= 1.8, pow <= 1.75 max(1, |y log x|).  Every constant a condition below compares
+// with is a threshold of the case table (tests/og_math_cases.py THRESHOLDS): add it there when adding one here.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -446,8 +452,9 @@ OG_HD double acos_(double x) {
 
 // ---------------------------------------------------------------- hyperbolic, other logarithms, roots
 // Built on exp_ / log_ above with the classical correction steps (W. Kahan's expm1 / log1p through the rounded
-// exp / 1 + x, fdlibm's formulae for sinh / cosh / tanh on top of expm1, one Newton step for cbrt): within 2 ulp of
-// NumPy's libm over the whole range (tests/test_og_math.py), and - what matters for parity - the SAME bits on the
+// exp / 1 + x, fdlibm's formulae for sinh / cosh / tanh on top of expm1, Newton steps for cbrt): within 1 ulp of NumPy's
+// libm for log2 / cbrt, 2 for log10 / cosh / log1p, 3 for expm1 / sinh / tanh (tests/test_og_math.py; within 1.2 - 1.8 ulp
+// of the true value over the whole range, profiles/og_math_edges.md), and - what matters for parity - the SAME bits on the
 // host twin and on gfx950, since they are made of the same bit-reproducible pieces.
 // sinh(h) / h and cosh(h) by their series in h^2, |h| <= 1 (term 12 is below 1e-23)
 OG_HD double sinhc_series(double h2) {
@@ -563,7 +570,12 @@ OG_HD double log10_(double x) {
 }
 OG_HD double cbrt_(double x) {
     if (isnan_(x) || x == 0.0 || x - x != 0.0) return x;       // NaN, +-0, +-inf
-    const double ax = fabs_(x);
+    double ax = fabs_(x), back = 1.0;
+    // The Newton step below forms t (t^3 - |x|), of the size of |x|^(4/3) 2^-52: it loses its bits to underflow for
+    // |x| < 2^-760 and overflows for |x| > 2^805.  Outside [2^-700, 2^700] the argument is therefore moved inside by
+    // 8^+-200 (exact, subnormals included) and the root moved back by 2^-+200 (exact); inside, nothing changes.
+    if (ax < 0x1p-700) { ax *= 0x1p+600; back = 0x1p-200; }
+    else if (ax > 0x1p+700) { ax *= 0x1p-600; back = 0x1p+200; }
     double t = exp_(log_(ax) * (1.0 / 3.0));
     // two Newton steps on t^3 = |x| in the form t -= t (t^3 - |x|) / (3 t^3): the first removes exp/log's few ulp,
     // the second confirms (a fixed point is within half an ulp of the root or next to it)
@@ -572,6 +584,7 @@ OG_HD double cbrt_(double x) {
         const double r = fma_(t2, t, -t3);                       // t^3 = t3 + r
         t -= t * ((t3 - ax) + r) / (3.0 * t3);
     }
+    t *= back;
     return x < 0.0 ? -t : t;
 }
 OG_HD double hypot_(double x, double y) {
@@ -622,18 +635,33 @@ OG_HD double pow_(double x, double y) {
             k >>= 1;
             if (k) base *= base;
         }
+        if (y < 0.0 && acc - acc != 0.0) {
+            // x^|y| overflowed, yet its reciprocal may still be a subnormal number (1e103 ** -3): not 1 / inf = 0
+            const double r = exp_(y * log_(fabs_(x)));
+            return acc < 0.0 ? -r : r;
+        }
         return y < 0.0 ? 1.0 / acc : acc;
     }
     if (x > 0.0) return exp_(y * log_(x));
     const double inf = from_bits(0x7ff0000000000000ULL);
-    const bool yint = fabs_(y) < 9.0e15 && (y == (double)(long long)y);
-    const bool yodd = yint && (((long long)y) & 1LL);
+    // x <= 0 from here on (x = -inf included), y != 0, neither a NaN: C99 pow's special cases (F.10.4.4), NumPy's
+    if (fabs_(y) == inf) {
+        if (fabs_(x) == 1.0) return 1.0;
+        return ((fabs_(x) < 1.0) == (y < 0.0)) ? inf : 0.0;
+    }
+    // every double of magnitude >= 2^53 is an even whole number; below, the cast is in range
+    const bool ybig = fabs_(y) >= 9007199254740992.0;
+    const bool yint = ybig || (y == (double)(long long)y);
+    const bool yodd = !ybig && yint && (((long long)y) & 1LL);
     if (x == 0.0) {
         const bool neg = (bits_of(x) >> 63) != 0 && yodd;
         return y > 0.0 ? (neg ? -0.0 : 0.0) : (neg ? -inf : inf);
     }
-    if (!yint) return (fabs_(y) == inf) ? ((fabs_(x) < 1.0) == (y < 0.0) ? inf : (fabs_(x) == 1.0 ? 1.0 : 0.0))
-                                        : from_bits(0x7ff8000000000000ULL);
+    if (x == -inf) {
+        const double r = y > 0.0 ? inf : 0.0;
+        return yodd ? -r : r;
+    }
+    if (!yint) return from_bits(0x7ff8000000000000ULL);
     const double r = exp_(y * log_(-x));
     return yodd ? -r : r;
 }
@@ -645,6 +673,8 @@ OG_HD double pow_(double x, double y) {
 // y = (y[i]-y[i-1])/(xg[i]-xg[i-1]) * (x - xg[i-1]) + y[i-1]; outside [xg[0], xg[n-1]] the
 // fill values replace it unless extrapolating.  mode 0: fill values; 1: extrapolate;
 // 2: the reference would raise ValueError (bounds_error=True) - a kernel cannot, it returns NaN.
+// Without extrapolation SciPy hands a 1-D float64 table to np.interp (_call_linear_np): the same formula between the
+// knots, and AT a knot the knot's own value, which slope * (x_hi - x_lo) + y_lo misses in the last bit now and then.
 OG_HD double interp_linear(const double* xg, const double* yg, const int n, const int mode,
                            const double fill_below, const double fill_above, const double x) {
     int lo = 0, hi = n;
@@ -657,6 +687,7 @@ OG_HD double interp_linear(const double* xg, const double* yg, const int n, cons
     const double slope = (y_hi - y_lo) / (x_hi - x_lo);
     double y = slope * (x - x_lo) + y_lo;
     if (mode != 1) {
+        if (x == x_hi) y = y_hi;              // np.interp, which serves these two modes, returns a knot's own value
         if (x < xg[0]) y = (mode == 0) ? fill_below : from_bits(0x7ff8000000000000ULL);
         if (x > xg[n - 1]) y = (mode == 0) ? fill_above : from_bits(0x7ff8000000000000ULL);
     }

@@ -62,6 +62,8 @@ class _Eval:
             slope = (yg[idx] - yg[idx - 1]) / (xg[idx] - xg[idx - 1])
             out = slope * (xn - xg[idx - 1]) + yg[idx - 1]
             if mode != 1:
+                knot = xn == xg[idx]                                        # np.interp (SciPy _call_linear_np)
+                out[knot] = yg[idx][knot]
                 flo = np.frombuffer(lo, dtype=np.float64)[0] if mode == 0 else np.nan
                 fhi = np.frombuffer(hi, dtype=np.float64)[0] if mode == 0 else np.nan
                 out[xn < xg[0]] = flo

@@ -708,7 +708,9 @@ def test_lgl_kernel_against_the_reference_golden(n):
 
 
 def test_hardware_probe():
-    """MFMA f64 = k-ordered fma chain; f64 div/sqrt/og_math bit-identical host vs device."""
+    """MFMA f64 = k-ordered fma chain; f64 div/sqrt/og_math bit-identical host vs device (eight functions on one
+    distribution, with timings; every function of og_math.h and og_dual.h at its branches and edges:
+    tests/test_og_math_gpu.py)."""
     import os
     import subprocess
     probe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),

@@ -1,6 +1,8 @@
-"""csrc/og_math.h on the host (g++): accuracy against NumPy and special values.  The same source
-is compiled for gfx950; bit-equality host<->device is checked on the GPU by tools/gpu_probe.hip
-(tests/test_gpu_parity.py::test_hardware_probe)."""
+"""csrc/og_math.h on the host (g++): accuracy against NumPy on random samples, and special values.  The branch
+thresholds, the exponent range and og_dual.h are checked against mpmath in tests/test_og_math_edges.py; the same source
+is compiled for gfx950, and bit-equality host<->device is checked on the GPU over that table and these samples by
+tests/test_og_math_gpu.py (and, for eight functions with timings, by tools/gpu_probe.hip:
+tests/test_gpu_parity.py::test_hardware_probe)."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +11,9 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+# the random distributions live next to the case table of the edge tests (tests/og_math_cases.py), which the GPU tests
+# run too: shared, so that the two cannot drift
+from og_math_cases import RANDOM_BASIC, RANDOM_WIDENED, random_atan2, random_hypot, random_mod, random_pow
 
 SRC = r"""
 #include "og_math.h"
@@ -55,25 +60,7 @@ def ulps(a, b):
     return np.abs(a - b) / np.spacing(np.abs(b))
 
 
-@pytest.mark.parametrize("name,ref,sample,tol", [
-    ("v_exp", np.exp, lambda r: r.uniform(-700, 700, 200000), 1.0),
-    ("v_exp", np.exp, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-12, 1, 200000), 1.0),
-    ("v_log", np.log, lambda r: np.exp(r.uniform(-700, 700, 200000)), 1.0),
-    ("v_sin", np.sin, lambda r: r.uniform(-100, 100, 200000), 1.0),
-    ("v_cos", np.cos, lambda r: r.uniform(-100, 100, 200000), 1.0),
-    ("v_sin", np.sin, lambda r: r.uniform(-1e5, 1e5, 200000), 1.0),
-    ("v_cos", np.cos, lambda r: r.uniform(-1e5, 1e5, 200000), 1.0),
-    # beyond the Cody-Waite range (2^20 * pi/2): the double-double reduction, up to 2^45
-    ("v_sin", np.sin, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.uniform(6.3, 13.5, 200000), 1.0),
-    ("v_cos", np.cos, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.uniform(6.3, 13.5, 200000), 1.0),
-    ("v_tan", np.tan, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.uniform(6.3, 13.5, 200000), 2.0),
-    ("v_tan", np.tan, lambda r: r.uniform(-1.5, 1.5, 200000), 2.0),
-    ("v_atan", np.arctan, lambda r: r.standard_normal(200000) * 10.0 ** r.integers(-10, 10, 200000), 1.0),
-    ("v_asin", np.arcsin, lambda r: r.uniform(-1, 1, 200000), 1.0),
-    ("v_acos", np.arccos, lambda r: r.uniform(-1, 1, 200000), 1.0),
-    ("v_asin", np.arcsin, lambda r: np.sign(r.uniform(-1, 1, 200000)) * (1 - 10.0 ** r.uniform(-12, -1, 200000)), 1.0),
-    ("v_acos", np.arccos, lambda r: np.sign(r.uniform(-1, 1, 200000)) * (1 - 10.0 ** r.uniform(-12, -1, 200000)), 1.0),
-])
+@pytest.mark.parametrize("name,ref,sample,tol", [("v_" + n, ref, sample, tol) for n, ref, sample, tol in RANDOM_BASIC])
 def test_within_one_ulp_of_numpy(lib, name, ref, sample, tol):
     x = sample(np.random.default_rng(0))
     got, want = call(lib, name, x), ref(x)
@@ -81,9 +68,7 @@ def test_within_one_ulp_of_numpy(lib, name, ref, sample, tol):
 
 
 def test_atan2_within_one_ulp_and_special_values(lib):
-    rng = np.random.default_rng(1)
-    y = rng.standard_normal(300000) * 10.0 ** rng.integers(-8, 8, 300000)
-    x = rng.standard_normal(300000) * 10.0 ** rng.integers(-8, 8, 300000)
+    y, x = random_atan2()
     yy, xx = np.ascontiguousarray(y), np.ascontiguousarray(x)
     out = np.empty_like(yy)
     dp = C.POINTER(C.c_double)
@@ -148,21 +133,11 @@ def call2(lib, name, a, b):
     return y
 
 
-@pytest.mark.parametrize("name,ref,sample,tol", [
-    ("v_expm1", np.expm1, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-12, 3, 200000), 3.0),
-    ("v_expm1", np.expm1, lambda r: r.uniform(-40, 700, 200000), 3.0),
-    ("v_log1p", np.log1p, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-12, 1, 200000), 2.0),
-    ("v_log1p", np.log1p, lambda r: np.exp(r.uniform(-30, 700, 200000)), 2.0),
-    ("v_sinh", np.sinh, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-10, 3, 200000), 3.0),
-    ("v_cosh", np.cosh, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-10, 3, 200000), 2.0),
-    ("v_tanh", np.tanh, lambda r: r.uniform(-1, 1, 200000) * 10.0 ** r.integers(-10, 2, 200000), 3.0),
-    ("v_log2", np.log2, lambda r: np.exp(r.uniform(-700, 700, 200000)), 1.0),
-    ("v_log10", np.log10, lambda r: np.exp(r.uniform(-700, 700, 200000)), 1.0),
-    ("v_cbrt", np.cbrt, lambda r: r.standard_normal(200000) * 10.0 ** r.integers(-100, 100, 200000), 1.0),
-])
+@pytest.mark.parametrize("name,ref,sample,tol", [("v_" + n, ref, sample, tol) for n, ref, sample, tol in RANDOM_WIDENED])
 def test_widened_function_set_within_a_few_ulp_of_numpy(lib, name, ref, sample, tol):
     """The functions the tracer gained in round 3 (tanh, sinh, cosh, log10, log2, log1p, expm1, cbrt): composed of
-    exp_ / log_ with classical correction steps - 1 ulp for log2 / log10 / cbrt, 2 for cosh / log1p, 3 for the expm1
+    exp_ / log_ with classical correction steps - 1 ulp for log2 / log10 / cbrt on these samples (log10: 2 over the whole
+    exponent range, profiles/og_math_edges.md), 2 for cosh / log1p, 3 for the expm1
     family (one rounded exp, two rounded products); bit-reproducible on the GPU for the same reason exp_ / log_ are."""
     x = sample(np.random.default_rng(0))
     with np.errstate(all="ignore"):
@@ -173,18 +148,17 @@ def test_widened_function_set_within_a_few_ulp_of_numpy(lib, name, ref, sample, 
 
 
 def test_hypot_pow_and_special_values_of_the_widened_set(lib):
-    r = np.random.default_rng(2)
-    a = r.standard_normal(300000) * 10.0 ** r.integers(-150, 150, 300000)
-    b = r.standard_normal(300000) * 10.0 ** r.integers(-150, 150, 300000)
+    r, (a, b), (_, b2) = random_hypot()
     assert np.max(ulps(call2(lib, "v_hypot", a, b), np.hypot(a, b))) <= 1.0
-    b = a * 10.0 ** r.uniform(-3, 3, a.size)
-    assert np.max(ulps(call2(lib, "v_hypot", a, b), np.hypot(a, b))) <= 1.0
+    assert np.max(ulps(call2(lib, "v_hypot", a, b2), np.hypot(a, b2))) <= 1.0
     # traced exponents: exp(y log x) - |y log x| ulp from libm's pow at worst (documented in og_math.h)
-    x, y = np.exp(r.uniform(-5, 5, 300000)), r.uniform(-4, 4, 300000)
+    x, y = random_pow(r)
     assert np.max(ulps(call2(lib, "v_pow", x, y), np.power(x, y)) / np.maximum(1.0, np.abs(y * np.log(x)))) <= 3.0
     with np.errstate(all="ignore"):
-        xs = np.array([0.0, -0.0, 0.0, -8.0, -8.0, 2.0, -2.0, 1.0, 5.0, np.nan, 0.5])
-        ys = np.array([2.0, 3.0, -1.0, 3.0, 0.5, 0.0, 2.0, np.nan, -np.inf, 0.0, np.inf])
+        xs = np.array([0.0, -0.0, 0.0, -8.0, -8.0, 2.0, -2.0, 1.0, 5.0, np.nan, 0.5, -2.0, -0.5, -1.0, -np.inf, -np.inf,
+                       -1.0, -3.0])
+        ys = np.array([2.0, 3.0, -1.0, 3.0, 0.5, 0.0, 2.0, np.nan, -np.inf, 0.0, np.inf, 1e16, 1e300, 1e300, 0.5, -0.5,
+                       np.inf, 2.0 ** 53 - 1.0])
         got, want = call2(lib, "v_pow", xs, ys), np.power(xs, ys)
     assert np.array_equal(np.isnan(got), np.isnan(want))
     plain = np.isfinite(want) & (want != 0)
@@ -208,10 +182,7 @@ def test_hypot_pow_and_special_values_of_the_widened_set(lib):
 def test_mod_and_fmod_are_numpys_bit_for_bit(lib):
     """np.remainder (= np.mod, Python's %: the divisor's sign) and np.fmod (the dividend's sign) are exact operations:
     the device functions must give NumPy's bits, signed zeros and special values included."""
-    rng = np.random.default_rng(5)
-    a = rng.uniform(-50, 50, 200000) * 10.0 ** rng.integers(-3, 6, 200000)
-    b = rng.uniform(-5, 5, 200000)
-    b[b == 0.0] = 1.0
+    a, b = random_mod()
     for name, ref in (("v_mod", np.remainder), ("v_fmod", np.fmod)):
         assert np.array_equal(call2(lib, name, a, b), ref(a, b))
         assert np.array_equal(call2(lib, name, np.round(a), np.round(b) + (np.round(b) == 0)),
