@@ -63,12 +63,30 @@ int og_problem_dims(og_handle h, int32_t* n, int32_t* m, int32_t* m_eq, int32_t*
 
 /* How og_fd_sweep(_dev) runs on this handle: 5 = evaluation and structured sweep in ONE launch (ogk_fused),
  * 1 = the same two kernels as two launches, 2 = evaluation + literal dense sweep (validation).  Chosen at
- * og_problem_create: OGPSX_SWEEP=fused|split|dense; the default is 5 at every size.  The one-launch form writes
+ * og_problem_create: OGPSX_SWEEP=fused|split|dense; the default is 5 at every size (og_one_launch: whether
+ * that is one launch on this handle).  The one-launch form writes
  * the non-zeros only, so it needs a persistent-zero output (og_jt_register_dev / _host; the host-pointer entry
  * points register their own staging buffer): a sweep into an unregistered device buffer runs as the two launches
  * of mode 1 from the same handle, with identical results.
  * No reference counterpart: SciPy's approx_derivative has one way to run (scipy/optimize/_numdiff.py:584-625). */
 int og_sweep_mode(og_handle h);
+
+/* The launch form og_sweep_mode == 5 actually takes on this handle: 1 = evaluation and sweep in ONE launch, 0 = two.
+ * The one-launch kernel keeps a tile's D panel, the operands and the base products of the longest phase in LDS: a
+ * module whose longest phase passes that window (ogk_info.fused_ok; opengoddard_amd.codegen.lds_window states the
+ * arithmetic: at 1 / 2 / 6 / 16 states per phase and no running cost the last node counts that fit are 452 / 408 /
+ * 292 / 168) keeps og_sweep_mode == 5 and runs every sweep as the two launches of mode 1, the registered host matrix
+ * as a full download, og_shard_sweep_dev as sweep + pack and a batch as one batched evaluation + one sweep per lane -
+ * with the same bits.  Also 0 under OGPSX_SWEEP=split|dense.  A captured graph of the two-launch form can be replayed
+ * like the one-launch form (the capture clears the count of non-finite rows itself).
+ * No reference counterpart (see og_sweep_mode). */
+int og_one_launch(og_handle h);
+
+/* *rows = the number of non-finite rows of F(x0) that the most recent evaluation, sweep or exact Jacobian enqueued on
+ * this handle counted (what makes a sweep fill those rows of J_T with NaN); waits for `hip_stream`, the stream that
+ * call was given.  After replays of a captured graph: the count of the last replay, if the captured call was the
+ * handle's most recent one.  No reference counterpart: SciPy's dense differences carry the NaN themselves. */
+int og_nonfinite_rows(og_handle h, void* hip_stream, int32_t* rows);
 
 /* ---- single evaluation ---------------------------------------------------------------------
  * F(x) = [cost | c_eq | c_ineq], m doubles.  Replaces one call each of cost_add, equality_add
@@ -139,7 +157,9 @@ int og_jt_register_host(og_handle h, double* JT, int32_t col_lo, int32_t col_hi)
 /* Which of the two serves og_fd_sweep into the registered host matrix JT: *path = 1 the mapped matrix (the launch writes
  * it over PCIe), 2 the packed copy + host scatter, 0 not decided yet (the first ten sweeps time both - two warm-ups and
  * three timed calls each - and keep the faster: what scattered device writes into host pages cost is the host's doing;
- * on every box of round 6 mapped won, 0.043-0.052 against 0.10-0.12 ms per sweep at C3), -1 JT is not registered.
+ * on every box of round 6 mapped won, 0.043-0.052 against 0.10-0.12 ms per sweep at C3), 3 neither: both belong to the
+ * one-launch form, and a handle without it (og_one_launch == 0) sweeps into its own device matrix and downloads the whole
+ * block, -1 JT is not registered.
  * OGPSX_HOST=mapped | staged in the environment decide without the trial.  No reference counterpart. */
 int og_jt_host_path(og_handle h, const double* JT, int32_t* path);
 /* Page-locked host memory from the HIP runtime (hipHostMalloc) for a matrix that is going to be registered with

@@ -883,9 +883,103 @@ def sparsity(P):
     return np.asarray(indptr, dtype=np.int64), np.asarray(rows, dtype=np.int32)
 
 
+LDS_BYTES = 64 * 1024    # the one-launch window: LDS of one ogk_fused workgroup, two of them resident per compute unit
+                         # (csrc/ogk_kernels.hip: ogk_get_info, ogk_launch)
+EVAL_LDS_BYTES = 160 * 1024     # LDS of a gfx950 compute unit: the most one workgroup can ask for (eval_lds_fits)
+MAX_PHASES = 32          # OGK_MAX_PHASE (csrc/ogk.h)
+MAX_STATES = 16          # rows of the MFMA A operand (_make_groups)
+TERM_CACHE_MAX = 2048    # sum terms a workgroup caches in LDS (csrc/ogk_kernels.hip: TERM_CACHE)
+
+
+class LimitError(_tr.TraceError):
+    """The traced program is beyond what a callback module can launch (``check_limits``)."""
+
+
+def eval_lds_bytes(P):
+    """Dynamic LDS of the evaluation kernels (modes 0, 2 and 12; ``defect_lds_bytes`` of csrc/ogk_kernels.hip) without
+    the cached sum terms: per defect group ``KS*64`` doubles of the D panel, ``MAX_NMV*KS*4`` of operands and 256 of
+    scratch, with ``KS = ceil(N/4)``."""
+    max_nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+    worst = 0
+    for g in P.groups:
+        if g.kind == "defect":
+            ks = (g.length + 3) >> 2
+            worst = max(worst, 8 * (ks * 64 + max_nmv * ks * 4 + 256))
+    return worst
+
+
+def max_phase_nodes(n_states):
+    """Largest node count of a phase with ``n_states`` states (the most of any phase of the problem) whose evaluation
+    kernel still fits ``EVAL_LDS_BYTES``: ``KS*(64 + 4*n_states) + 256 <= 20480`` doubles with ``KS = ceil(N/4)`` -
+    1188 / 840 / 632 nodes at 1 / 8 / 16 states."""
+    return 4 * ((EVAL_LDS_BYTES // 8 - 256) // (64 + 4 * max(int(n_states), 1)))
+
+
+def check_limits(P):
+    """Refuse, by name, a program no module can run: more than ``MAX_PHASES`` phases (``og_problem_create`` refuses
+    them too) or a phase so long that the evaluation kernel's dynamic LDS passes ``EVAL_LDS_BYTES`` - nothing in the
+    runtime would say so before the first launch.  ``emit_header`` calls this before it generates anything."""
+    if len(P.nodes) > MAX_PHASES:
+        raise LimitError("%d phases: more than %d phases (OGK_MAX_PHASE) are not supported" % (len(P.nodes), MAX_PHASES))
+    need = eval_lds_bytes(P)
+    if need > EVAL_LDS_BYTES:
+        nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+        raise LimitError("the evaluation kernel needs %d bytes of LDS, more than the %d bytes a workgroup has: with %d "
+                         "states per phase a phase can have at most %d nodes, the longest has %d"
+                         % (need, EVAL_LDS_BYTES, nmv, max_phase_nodes(nmv), max(g.length for g in P.groups if g.kind == "defect")))
+
+
+def lds_window(P):
+    """The LDS arithmetic of a callback module (csrc/ogk_kernels.hip: ``defect_lds_bytes``, ``FZ_LDS_BYTES``,
+    ``ROW_WORDS``, ``ogk_get_info``) restated from the traced program, so that a caller - and the tests - know before
+    anything is compiled on which side of the one-launch window a problem lies::
+
+        eval_bytes  = max(8*(KS*(64 + 4*MAX_NMV) + 256) over the defect groups, 8*TERM_DOUBLES)   KS = ceil(N/4)
+        fused_bytes = 8*((NP/4)*64 + MAX_NMV*(NP + MAX_NODES) + TERM_DOUBLES)                      NP = 4*ceil(MAX_NODES/4)
+        fill_bytes  = 4*ceil(M/32)
+        one_launch  = max(eval_bytes, fused_bytes, fill_bytes) <= 64 KiB
+        eval_fits   = eval_bytes <= 160 KiB
+
+    ``TERM_DOUBLES = N_TERMS + 16`` while ``0 < N_TERMS <= 2048`` (the cached terms of sequential sums: a running
+    cost), else 0; ``MAX_NMV`` is the largest number of collocation slots (states) of a phase; ``N_TERMS`` is
+    ``count_sum_terms``.  A module beyond the window sweeps in two launches (``og_one_launch``, include/ogpsx.h); ``eval_fits`` False is
+    what ``check_limits`` refuses."""
+    n_terms = count_sum_terms(P)
+    max_nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+    term_doubles = n_terms + 16 if 0 < n_terms <= TERM_CACHE_MAX else 0
+    eval_bytes = max(eval_lds_bytes(P), 8 * term_doubles)
+    max_nodes = max(P.nodes)
+    npad = 4 * ((max_nodes + 3) // 4)
+    fused_bytes = 8 * ((npad // 4) * 64 + max_nmv * (npad + max_nodes) + term_doubles)
+    fill_bytes = 4 * ((P.m + 31) // 32)
+    return {"eval_bytes": eval_bytes, "fused_bytes": fused_bytes, "fill_bytes": fill_bytes,
+            "max_nmv": max_nmv, "max_nodes": max_nodes, "n_terms": n_terms, "term_doubles": term_doubles,
+            "eval_fits": eval_bytes <= EVAL_LDS_BYTES,
+            "one_launch": max(eval_bytes, fused_bytes, fill_bytes) <= LDS_BYTES}
+
+
+def _emit_functions(em, P):
+    """The group functions and the operand function of the header; emitting them is what finds the sequential sums
+    (``em.term_blocks``)."""
+    L = []
+    for gi, g in enumerate(P.groups):
+        L += em.group_function(gi, g)
+        L.append("")
+    L += em.operand_function()
+    return L
+
+
+def count_sum_terms(P):
+    """``N_TERMS`` of the program's header: the terms of all sequential sums its group functions contain."""
+    em = _Emitter(P)
+    _emit_functions(em, P)
+    return sum(ln for ln, _ in em.term_blocks)
+
+
 def emit_header(P):
     """C++17 source of ``struct OgGen`` for this program (host+device, no includes of its own
-    beyond og_math.h)."""
+    beyond og_math.h).  Raises ``LimitError`` for a program beyond the limits of a module (``check_limits``)."""
+    check_limits(P)
     em = _Emitter(P)
     max_out = max(len(g.outputs) for g in P.groups)
     n_rowitems = sum(g.length for g in P.groups if g.kind == "rows")
@@ -994,10 +1088,7 @@ def emit_header(P):
     L += [_int_table("MV_Y0", y0_off),
           "    static constexpr int N_Y0 = %d;" % max(at, 1)]
     L.append("")
-    for gi, g in enumerate(P.groups):
-        L += em.group_function(gi, g)
-        L.append("")
-    L += em.operand_function()
+    L += _emit_functions(em, P)
     L.append("")
     L += em.term_functions()
     L.append("")

@@ -1787,6 +1787,12 @@ size_t defect_lds_bytes() {
     return worst > terms ? worst : terms;
 }
 
+// Modes 0, 2 and 12 ask for defect_lds_bytes() of dynamic LDS whatever the phase lengths are, also beyond the 64 KiB
+// of the one-launch window (launch4 on 341 nodes per phase: 68 096 bytes); a compute unit of gfx950 has 160 KiB.
+// codegen.emit_header refuses a program beyond that before it is compiled (codegen.check_limits); a module that was
+// built some other way answers hipErrorInvalidValue here instead of launching.
+bool eval_lds_fits() { return defect_lds_bytes() <= 160 * 1024; }
+
 size_t sweep_lds_bytes() { return (size_t)LIGHT_COLS * ROW_WORDS * sizeof(unsigned); }
 
 }  // namespace
@@ -1826,6 +1832,7 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
 #ifdef OGK_HAS_MAIN
     if (mode == 0) {
         const int eval_row_blocks = (OGT_N_ROWWAVES + SWEEP_WAVES - 1) / SWEEP_WAVES;
+        if (!eval_lds_fits()) return (int)hipErrorInvalidValue;
         if (ndef + eval_row_blocks > 0)
             hipLaunchKernelGGL(ogk_eval, dim3(ndef + eval_row_blocks), dim3(SWEEP_THREADS),
                                defect_lds_bytes(), stream, *args, ndef);
@@ -1908,6 +1915,7 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
     }
     if (mode == 2) {
         if (ncols <= 0) return 0;
+        if (!eval_lds_fits()) return (int)hipErrorInvalidValue;
         const int row_blocks = (OgGen::N_ROW_ITEMS + 255) / 256;
         const int defect_total = ndef * ((ncols + 63) / 64);
         const int rows_total = row_blocks * ((ncols + ROWS_COLS_PER_THREAD - 1) / ROWS_COLS_PER_THREAD);
@@ -1932,6 +1940,7 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
         return (int)hipGetLastError();
     }
     if (mode == 12) {
+        if (!eval_lds_fits()) return (int)hipErrorInvalidValue;
         if (ndef + eval_row_blocks > 0)
             hipLaunchKernelGGL(ogk_eval_batch, dim3(ndef + eval_row_blocks, b->count), dim3(SWEEP_THREADS),
                                defect_lds_bytes(), stream, (const ogk_args*)b->lanes, ndef);

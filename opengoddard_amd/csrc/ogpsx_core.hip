@@ -746,6 +746,19 @@ void og_problem_destroy(og_handle p) {
 
 int og_sweep_mode(og_handle p) { return p ? p->sweep_mode : 0; }
 
+int og_one_launch(og_handle p) { return (p && p->sweep_mode == 5 && p->fused_ok) ? 1 : 0; }
+
+int og_nonfinite_rows(og_handle p, void* hip_stream, int32_t* rows) {
+    if (!p || !rows) return fail(1, "og_nonfinite_rows: null argument");
+    if (!p->nf_read) return fail(1, "og_nonfinite_rows: nothing has been evaluated on this handle");
+    OG_HIP(hipSetDevice(p->device));
+    OG_HIP(hipStreamSynchronize((hipStream_t)hip_stream));
+    int count = 0;
+    OG_HIP(hipMemcpy(&count, p->nf_read, sizeof(int), hipMemcpyDeviceToHost));
+    *rows = count;
+    return 0;
+}
+
 int og_device_read(int32_t device, const void* d_src, void* dst, int64_t bytes) {
     if (!d_src || !dst || bytes < 0) return fail(1, "og_device_read: bad argument");
     OG_HIP(hipSetDevice(device));
@@ -884,7 +897,7 @@ int og_jt_host_path(og_handle p, const double* JT, int32_t* path) {
     if (!p || !path) return fail(1, "og_jt_host_path: null argument");
     *path = -1;
     for (auto& r : p->host_regs)
-        if (r.ptr == JT) *path = !r.mapped ? 2 : r.choice;
+        if (r.ptr == JT) *path = !(p->sweep_mode == 5 && p->fused_ok) ? 3 : !r.mapped ? 2 : r.choice;
     return 0;
 }
 
@@ -1065,6 +1078,22 @@ int og_problem_dims(og_handle p, int32_t* n, int32_t* m, int32_t* m_eq, int32_t*
     return 0;
 }
 
+// The two-launch forms count the non-finite rows of F(x0) into one of two words, in turn: outside a capture the
+// evaluation before this one has cleared the word this one counts into (ogk_eval: *nonfinite_next = 0).  A replayed
+// graph is its own predecessor: it would count on top of the count it left, and after one non-finite point every
+// later replay would fill with z, mark the buffer and report rows that are no longer there.  A capture therefore
+// clears its word itself, as a node of the graph.
+static int clear_count_in_a_capture(int* d_count, void* hip_stream) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)hip_stream, &capturing) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (capturing == hipStreamCaptureStatusActive)
+        OG_HIP(hipMemsetAsync(d_count, 0, sizeof(int), (hipStream_t)hip_stream));
+    return 0;
+}
+
 int og_eval_dev(og_handle p, const double* d_x, double* d_F, void* hip_stream) {
     if (!p || !d_x || !d_F) return fail(1, "og_eval_dev: null argument");
     ogk_args a;
@@ -1095,6 +1124,8 @@ int og_fd_sweep_dev(og_handle p, const double* d_x, const double* d_h, int32_t l
         a.nonfinite_next = p->d_flags + (p->flag_slot ^ 1);
         p->nf_read = a.nonfinite;
         a.jt_bump = a.jt_sparse;                    // F(x0) first: the sweep subtracts it; it also counts the launch
+        rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+        if (rc) return rc;
         rc = p->launch(&a, 0, hip_stream);
         if (!rc) rc = p->launch(&a, p->sweep_mode == 5 ? 1 : p->sweep_mode, hip_stream);
     }

@@ -180,18 +180,31 @@ class HipEngine:
     @property
     def host_path(self):
         """How ``sweep_persistent`` reaches the persistent host matrix (``og_jt_host_path``): "mapped" (the launch writes
-        it over PCIe), "staged" (packed copy + host scatter), "undecided" (the first six sweeps time both), None before
-        the first call."""
+        it over PCIe), "staged" (packed copy + host scatter), "undecided" (the first six sweeps time both), "download"
+        (the whole dense block: a handle without the one-launch form, :attr:`one_launch`), None before the first call."""
         if self._JT_host is None:
             return None
         path = C.c_int32(-1)
         _native.check(self._lib.og_jt_host_path(self._handle, _native.dptr(self._JT_host), C.byref(path)), "og_jt_host_path")
-        return {1: "mapped", 2: "staged", 0: "undecided"}.get(path.value)
+        return {1: "mapped", 2: "staged", 0: "undecided", 3: "download"}.get(path.value)
 
     @property
     def sweep_mode(self):
         """How ``sweep_dev`` runs (``og_sweep_mode``): "fused" (one launch), "split" or "dense"."""
         return {5: "fused", 1: "split", 2: "dense"}[self._lib.og_sweep_mode(self._handle)]
+
+    @property
+    def one_launch(self):
+        """Whether "fused" really is one launch on this module (``og_one_launch``): a module whose longest phase passes
+        the LDS window of the one-launch kernel (``codegen.lds_window``) keeps ``sweep_mode == "fused"`` and sweeps in
+        two launches, with the same bits."""
+        return bool(self._lib.og_one_launch(self._handle))
+
+    def nonfinite_rows(self, stream=0):
+        """Non-finite rows of F(x0) counted by the handle's most recent evaluation or sweep (``og_nonfinite_rows``)."""
+        rows = C.c_int32(-1)
+        _native.check(self._lib.og_nonfinite_rows(self._handle, stream, C.byref(rows)), "og_nonfinite_rows")
+        return int(rows.value)
 
     def exact_dev(self, d_x, col_lo, col_hi, d_JT, d_F0, stream=0):
         _native.check(self._lib.og_jacobian_exact_dev(self._handle, d_x, int(col_lo), int(col_hi), d_JT, d_F0,

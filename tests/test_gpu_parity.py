@@ -179,11 +179,13 @@ def test_structured_sweep_equals_dense_sweep(name, golden, monkeypatch):
 
 
 def test_launch_form(monkeypatch):
-    """og_fd_sweep(_dev) runs evaluation + structured sweep as ONE launch at every size when the output is a
-    registered persistent-zero buffer (the host-pointer entry points register their own); an unregistered
-    buffer gets the two-launch form from the same handle, with identical results (include/ogpsx.h
-    og_sweep_mode); OGPSX_SWEEP overrides."""
+    """og_fd_sweep(_dev) runs evaluation + structured sweep as ONE launch when the output is a registered
+    persistent-zero buffer (the host-pointer entry points register their own) and the module's longest phase fits the
+    LDS window of that launch (og_one_launch; every BASELINE configuration does, tests/test_module_limits.py visits
+    both sides of the window); an unregistered buffer gets the two-launch form from the same handle, with identical
+    results (include/ogpsx.h og_sweep_mode); OGPSX_SWEEP overrides."""
     import torch
+    from opengoddard_amd import codegen
     from opengoddard_amd.engine import HipEngine
     from oracle import np_path
     monkeypatch.delenv("OGPSX_SWEEP", raising=False)
@@ -191,6 +193,7 @@ def test_launch_form(monkeypatch):
         prob, obj = problems.build(name)
         eng = HipEngine(prob, obj)
         assert eng.sweep_mode == "fused"
+        assert eng.one_launch and codegen.lds_window(eng.program)["one_launch"]
         if name != "launch4":
             lb, ub = np_path.bounds_arrays(prob)
             x = np.clip(prob.p, lb, ub)
@@ -208,7 +211,7 @@ def test_launch_form(monkeypatch):
     monkeypatch.setenv("OGPSX_SWEEP", "split")
     prob, obj = problems.build("goddard")
     eng = HipEngine(prob, obj)
-    assert eng.sweep_mode == "split"
+    assert eng.sweep_mode == "split" and not eng.one_launch
     eng.close()
 
 

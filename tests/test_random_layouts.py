@@ -49,7 +49,10 @@ def _term(rng, x):
     return np.maximum(x, -0.25) * 0.7
 
 
-def make_problem(shape, seed):
+def make_problem(shape, seed, sqrt_term=False):
+    """``sqrt_term``: the last state of phase 0 gets the extra dynamics term ``0.1*sqrt(x_0 + 2)``, which is NaN where
+    state 0 is below -2 (its bounds are [-1, 1]): points with non-finite rows for tests/test_module_limits.py.  The
+    option draws no random number: without it a (shape, seed) pair keeps its program."""
     nodes, ns, nc, smooth = shape
     rng = np.random.default_rng(seed)
     S = len(nodes)
@@ -79,6 +82,8 @@ def make_problem(shape, seed):
             if r.integers(0, 3) == 0:
                 continue                                  # leave this state's rhs at its zero default
             dx[s] = acc
+        if sqrt_term and section == 0:
+            dx[ns[0] - 1] = 0.1 * np.sqrt(xs[0] + 2.0) + dx[ns[0] - 1]
         return dx()
 
     def equality(prob, obj):
