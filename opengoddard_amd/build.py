@@ -73,47 +73,41 @@ def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h")]
 
 
-def build_core(force=False):
-    if os.environ.get("OG_CORE_LIB"):                   # diagnostics: a build with other flags (tools/sanitize.sh)
-        return os.environ["OG_CORE_LIB"]
+def _build_library(lib, sources, override, force):
+    """One of the two fixed libraries, from ``sources[0]`` and the headers after it -> its path.  Rebuilt when the
+    content of the sources or the flags change (a stamp file next to it holds their digest).  ``override``: the
+    environment variable that names a build made elsewhere, with other flags, to use instead (diagnostics)."""
+    if os.environ.get(override):
+        return os.environ[override]
     os.makedirs(LIBDIR, exist_ok=True)
-    stamp_path = CORE_LIB + ".stamp"
-    want = _digest_files(_core_sources())
-    if not force and os.path.exists(CORE_LIB) and os.path.exists(stamp_path):
+    stamp_path = lib + ".stamp"
+    want = _digest_files(sources)
+    if not force and os.path.exists(lib) and os.path.exists(stamp_path):
         with open(stamp_path) as fh:
             if fh.read().strip() == want:
-                return CORE_LIB
-    tmp = CORE_LIB + ".tmp%d" % os.getpid()
-    _run([hipcc()] + HIP_FLAGS + [os.path.join(CSRC, "ogpsx_core.hip"), "-o", tmp, "-ldl"])
-    os.replace(tmp, CORE_LIB)
+                return lib
+    tmp = lib + ".tmp%d" % os.getpid()
+    _run([hipcc()] + HIP_FLAGS + [sources[0], "-o", tmp, "-ldl"])
+    os.replace(tmp, lib)
     with open(stamp_path, "w") as fh:
         fh.write(want)
-    return CORE_LIB
+    return lib
+
+
+def build_core(force=False):
+    """``lib/libogpsx.so`` (``OG_CORE_LIB``: tools/sanitize.sh)."""
+    return _build_library(CORE_LIB, _core_sources(), "OG_CORE_LIB", force)
 
 
 SQP_LIB = os.path.join(LIBDIR, "libogsqp.so")
 
 
 def build_sqp(force=False):
-    """``lib/libogsqp.so``: the QP subproblem / BFGS kernels of the SQP driver (``include/ogsqp.h``)."""
-    if os.environ.get("OG_SQP_LIB"):                    # diagnostics: a build with other flags (-DOGSQP_TRACE)
-        return os.environ["OG_SQP_LIB"]
-    os.makedirs(LIBDIR, exist_ok=True)
-    sources = [os.path.join(CSRC, "ogsqp.hip"), os.path.join(CSRC, "ogsqp_rows.h"), os.path.join(CSRC, "ogsqp_lq16.h"),
-               os.path.join(CSRC, "ogsqp_lqwide.h"), os.path.join(CSRC, "ogsqp_resident.h"),
-               os.path.join(HERE, "..", "include", "ogsqp.h")]
-    stamp_path = SQP_LIB + ".stamp"
-    want = _digest_files(sources)
-    if not force and os.path.exists(SQP_LIB) and os.path.exists(stamp_path):
-        with open(stamp_path) as fh:
-            if fh.read().strip() == want:
-                return SQP_LIB
-    tmp = SQP_LIB + ".tmp%d" % os.getpid()
-    _run([hipcc()] + HIP_FLAGS + [sources[0], "-o", tmp, "-ldl"])
-    os.replace(tmp, SQP_LIB)
-    with open(stamp_path, "w") as fh:
-        fh.write(want)
-    return SQP_LIB
+    """``lib/libogsqp.so``: the QP subproblem / BFGS kernels of the SQP driver (``include/ogsqp.h``; ``OG_SQP_LIB``:
+    a build with -DOGSQP_TRACE)."""
+    sources = [os.path.join(CSRC, f) for f in ("ogsqp.hip", "ogsqp_rows.h", "ogsqp_lq16.h", "ogsqp_lqwide.h",
+                                               "ogsqp_resident.h")] + [os.path.join(HERE, "..", "include", "ogsqp.h")]
+    return _build_library(SQP_LIB, sources, "OG_SQP_LIB", force)
 
 
 def module_digest(header_source):
@@ -130,6 +124,7 @@ def module_path(digest):
 # compiled as PARTS side by side (-DOGK_PART=k, csrc/ogk_kernels.hip): part 0 (evaluation, pattern, pack, unpack)
 # is <module>.so, the others <module>.p<k>.so next to it; the runtime loads what is there (ogpsx_core.hip:
 # ogk_module).  Wall-clock of a cold start = the slowest part.
+# (csrc/ogk.h names the values: OGK_PART_MAIN, OGK_PART_FUSED, OGK_PART_SWEEP, OGK_PART_AUX)
 MODULE_PARTS = (0, 2, 3, 1)     # OGK_PART of <module>.so, .p1.so, .p2.so, .p3.so: main, one-launch sweep, sweep, aux
 
 
@@ -137,7 +132,7 @@ def part_path(out, index):
     return out if index == 0 else out[:-3] + ".p%d.so" % index
 
 
-BATCH_PART = 4                  # OGK_PART of <module>.batch.so: the kernels of a batch of points (og_batch_*)
+BATCH_PART = 4                  # OGK_PART_BATCH, <module>.batch.so: the kernels of a batch of points (og_batch_*)
 
 
 def batch_part_path(out):
@@ -155,26 +150,30 @@ def _write_header(header_source, digest):
     return header
 
 
-def build_batch_part(header_source, force=False):
-    """Compile the batch kernels (``ogk_fused_batch`` / ``ogk_eval_batch``, csrc/ogk_kernels.hip, ``OGK_PART=4``)
-    against one generated header -> path of ``<module>.batch.so``, next to the module of the same digest and cached
-    like it.  Not one of ``MODULE_PARTS``: it is built when a batch is first asked for (``HipEngine.batch``), so that
-    ``build_module`` and the cold start of a user who never batches stay what they are."""
+def _build_on_demand_part(header_source, part, path_of, force):
+    """Compile one ``OGK_PART`` of csrc/ogk_kernels.hip that is none of ``MODULE_PARTS`` against one generated header
+    -> ``path_of(<module>.so)``, next to the module of the same digest and cached like it."""
     os.makedirs(JITDIR, exist_ok=True)
     digest = module_digest(header_source)
-    out = batch_part_path(module_path(digest))
+    out = path_of(module_path(digest))
     if not force and os.path.exists(out):
         return out
     header = _write_header(header_source, digest)
     tmp = out + ".tmp%d" % os.getpid()
-    _run([hipcc()] + HIP_FLAGS + MODULE_FLAGS + ["-DOGK_PART=%d" % BATCH_PART, "-I" + CSRC,
-                                                 "-DOG_GEN_HEADER=\"%s\"" % header,
+    _run([hipcc()] + HIP_FLAGS + MODULE_FLAGS + ["-DOGK_PART=%d" % part, "-I" + CSRC, "-DOG_GEN_HEADER=\"%s\"" % header,
                                                  os.path.join(CSRC, "ogk_kernels.hip"), "-o", tmp])
     os.replace(tmp, out)
     return out
 
 
-BATCH_EXACT_PART = 5            # OGK_PART of <module>.batchx.so: the exact Jacobian of a batch (og_jacobian_exact_batch*)
+def build_batch_part(header_source, force=False):
+    """The batch kernels (``ogk_fused_batch`` / ``ogk_eval_batch``, ``OGK_PART=4``) -> path of ``<module>.batch.so``.
+    Not one of ``MODULE_PARTS``: it is built when a batch is first asked for (``HipEngine.batch``), so that
+    ``build_module`` and the cold start of a user who never batches stay what they are."""
+    return _build_on_demand_part(header_source, BATCH_PART, batch_part_path, force)
+
+
+BATCH_EXACT_PART = 5            # OGK_PART_BATCH_EXACT, <module>.batchx.so: the exact Jacobian of a batch
 
 
 def batch_exact_part_path(out):
@@ -182,23 +181,11 @@ def batch_exact_part_path(out):
 
 
 def build_batch_exact_part(header_source, force=False):
-    """Compile ``ogk_exact_struct_batch`` (csrc/ogk_kernels.hip, ``OGK_PART=5``) against one generated header -> path
-    of ``<module>.batchx.so``, next to the module of the same digest and cached like it.  A part of its own, neither
-    one of ``MODULE_PARTS`` nor in the batch part: the kernel instantiates the callbacks on dual numbers, and a user
-    who batches evaluations or FD sweeps only builds and loads what they did before.  Built when an exact Jacobian of
-    a batch is first asked for (``BatchSweep.exact``)."""
-    os.makedirs(JITDIR, exist_ok=True)
-    digest = module_digest(header_source)
-    out = batch_exact_part_path(module_path(digest))
-    if not force and os.path.exists(out):
-        return out
-    header = _write_header(header_source, digest)
-    tmp = out + ".tmp%d" % os.getpid()
-    _run([hipcc()] + HIP_FLAGS + MODULE_FLAGS + ["-DOGK_PART=%d" % BATCH_EXACT_PART, "-I" + CSRC,
-                                                 "-DOG_GEN_HEADER=\"%s\"" % header,
-                                                 os.path.join(CSRC, "ogk_kernels.hip"), "-o", tmp])
-    os.replace(tmp, out)
-    return out
+    """``ogk_exact_struct_batch`` (``OGK_PART=5``) -> path of ``<module>.batchx.so``.  A part of its own, neither one
+    of ``MODULE_PARTS`` nor in the batch part: the kernel instantiates the callbacks on dual numbers, and a user who
+    batches evaluations or FD sweeps only builds and loads what they did before.  Built when an exact Jacobian of a
+    batch is first asked for (``BatchSweep.exact``)."""
+    return _build_on_demand_part(header_source, BATCH_EXACT_PART, batch_exact_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

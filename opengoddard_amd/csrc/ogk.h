@@ -26,14 +26,57 @@ static inline void ogk_frag_pack(int N, const double* D, double* frag) {
 
 #define OGK_OTHER_PART (-4242)   /* ogk_launch: this mode's kernels are in the other part of a two-part module */
 
+// The launch modes of ogk_launch / ogk_launch_batch (what each does: at the two declarations below).  The values of
+// OGK_FUSED, OGK_SWEEP and OGK_DENSE are public: og_sweep_mode (include/ogpsx.h) returns them.
+enum ogk_mode {
+    OGK_EVAL = 0,           // F(x0) and the scratch the sweeps reuse
+    OGK_SWEEP = 1,          // structured FD sweep (needs OGK_EVAL at the same x0)
+    OGK_DENSE = 2,          // dense FD sweep (validation)
+    OGK_EXACT_DENSE = 3,    // exact Jacobian, dense
+    OGK_EXACT = 4,          // exact Jacobian with the work lists of the structured sweep
+    OGK_FUSED = 5,          // OGK_EVAL + OGK_SWEEP in one launch
+    OGK_PATTERN_COUNT = 6,  // the static pattern: entries per column
+    OGK_PATTERN_ROWS = 7,   // the static pattern: row indices
+    OGK_PACK = 8,           // gather the pattern entries of a block of columns
+    OGK_UNPACK = 9,         // scatter packed values into a full matrix
+    OGK_COUNT_LAUNCH = 10,  // count one launch into *jt_launches
+    OGK_BATCH_FUSED = 11,   // OGK_FUSED for `count` lanes
+    OGK_BATCH_EVAL = 12,    // OGK_EVAL for `count` lanes
+    OGK_BATCH_BIND = 13,    // bind the caller's arrays to the lane records
+    OGK_BATCH_EXACT = 14    // OGK_EXACT for `count` lanes
+};
+
+// The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART).
+// Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
+#define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
+#define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
+#define OGK_PART_FUSED 2        /* <module>.p1.so: OGK_FUSED */
+#define OGK_PART_SWEEP 3        /* <module>.p2.so: OGK_SWEEP */
+#define OGK_PART_BATCH 4        /* <module>.batch.so, on demand: OGK_BATCH_FUSED, OGK_BATCH_EVAL, OGK_BATCH_BIND */
+#define OGK_PART_BATCH_EXACT 5  /* <module>.batchx.so, on demand: OGK_BATCH_EXACT */
+
+// The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
+enum ogk_flag {
+    OGK_FLAG_COUNT_A = 0,       // two counters of non-finite rows that the two-launch forms use alternately
+    OGK_FLAG_COUNT_B = 1,
+    OGK_FLAG_TICKET = 2,        // OGK_FUSED: evaluation workgroups that have finished
+    OGK_FLAG_FUSED_COUNT = 3,   // OGK_FUSED: non-finite rows of the running launch (zero between launches)
+    OGK_FLAG_FUSED_RESULT = 4,  // OGK_FUSED: where its last evaluation workgroup leaves the total
+    OGK_FLAG_WORDS = 8
+};
+
+#ifdef __cplusplus
+static_assert(OGK_FUSED == 5 && OGK_SWEEP == 1 && OGK_DENSE == 2, "og_sweep_mode's values are public (include/ogpsx.h)");
+#endif
+
 typedef struct ogk_info {
     int32_t abi;
     int32_t n, m, m_eq, m_ineq;
     int32_t n_phase, n_mv, n_groups, n_cvec;
     int32_t n_y0;           // doubles of scratch for the unperturbed collocation products
     int32_t phase_nodes[OGK_MAX_PHASE];
-    int32_t n_eval_blocks;  // evaluation workgroups of one launch (what the mode-5 ticket counts)
-    int32_t fused_ok;       // mode 5 runs as ONE launch on this module (its LDS fits); else the caller uses modes 0 + 1
+    int32_t n_eval_blocks;  // evaluation workgroups of one launch (what the OGK_FUSED ticket counts)
+    int32_t fused_ok;       // OGK_FUSED runs as ONE launch on this module (its LDS fits); else the caller uses OGK_EVAL + OGK_SWEEP
 } ogk_info;
 
 typedef struct ogk_args {
@@ -41,15 +84,15 @@ typedef struct ogk_args {
     const double* h;        // [n] signed FD steps (device; unused for a plain evaluation)
     const double* dfrag;    // packed D fragments of all phases (device)
     const double* cvec;     // constant table (device, may be NULL when n_cvec == 0)
-    double* f0;             // [m] F(x0): written by mode 0, read by modes 1 and 2
-    double* y0;             // [n_y0] base collocation products   (written by mode 0)
-    double* xop;            // [n_y0] base collocation operands   (written by mode 0)
-    double* t0;             // [m] base dynamics terms of defect rows (written by mode 0)
-    double* z;              // [m] F0 - F0: 0, or NaN for non-finite rows (written by mode 0)
-    int* nonfinite;         // number of non-finite rows of F(x0): counted by mode 0, read by mode 1
-    int* nonfinite_next;    // the slot the *next* evaluation counts into (mode 0 zeroes it)
-    unsigned* ready;        // mode 5: ticket the evaluation workgroups count into; the last one resets it
-    double* jt;             // [(col_hi-col_lo) * m] transposed Jacobian rows (mode 1)
+    double* f0;             // [m] F(x0): written by OGK_EVAL, read by OGK_SWEEP and OGK_DENSE
+    double* y0;             // [n_y0] base collocation products   (written by OGK_EVAL)
+    double* xop;            // [n_y0] base collocation operands   (written by OGK_EVAL)
+    double* t0;             // [m] base dynamics terms of defect rows (written by OGK_EVAL)
+    double* z;              // [m] F0 - F0: 0, or NaN for non-finite rows (written by OGK_EVAL)
+    int* nonfinite;         // number of non-finite rows of F(x0): counted by OGK_EVAL, read by OGK_SWEEP
+    int* nonfinite_next;    // the slot the *next* evaluation counts into (OGK_EVAL zeroes it)
+    unsigned* ready;        // OGK_FUSED: ticket the evaluation workgroups count into; the last one resets it
+    double* jt;             // [(col_hi-col_lo) * m] transposed Jacobian rows (OGK_SWEEP)
     // Persistent-zero output (og_jt_register_dev, include/ogpsx.h).  jt_sparse != 0: the structural zeros of
     // `jt` are known to hold zeros already, so the sweep writes ONLY the positions that can be non-zero (row
     // items and collocation tiles).  The exception is kept on the device, because the asynchronous entry
@@ -58,26 +101,27 @@ typedef struct ogk_args {
     // buffer; a sweep whose F(x0) has non-finite rows fills its rows completely (NaN where dense FD gives NaN)
     // and stores its own launch number into *jt_state; the next sweep finds *jt_state == its number - 1 and
     // fills completely once more (zeros), which cleans the buffer.  Who counts: the last evaluation workgroup
-    // of a mode-5 launch (one thread); thread 0 of a mode-0 launch when jt_bump is set (the evaluation that
-    // precedes a mode 1 / 2 / 4 launch); a one-thread kernel (mode 10) before a lone mode-1 launch.
+    // of an OGK_FUSED launch (one thread); thread 0 of an OGK_EVAL launch when jt_bump is set (the evaluation that
+    // precedes an OGK_SWEEP / OGK_DENSE / OGK_EXACT launch); a one-thread kernel (OGK_COUNT_LAUNCH) before a lone
+    // OGK_SWEEP launch.
     int32_t jt_sparse;
-    int32_t jt_bump;        // mode 0: count one launch into *jt_launches; mode 9 (unpack of a rank that owns no
+    int32_t jt_bump;        // OGK_EVAL: count one launch into *jt_launches; OGK_UNPACK (of a rank that owns no
                             // columns): mark a NaN fill in *jt_state when F(x0) had non-finite rows
     uint32_t* jt_launches;  // launches into the registered buffer so far
     uint32_t* jt_state;     // number of the last launch into the buffer that left NaN fill behind
-    // mode 5 counts the non-finite rows of F(x0) in *nonfinite (zero between launches: its last evaluation
+    // OGK_FUSED counts the non-finite rows of F(x0) in *nonfinite (zero between launches: its last evaluation
     // workgroup moves the total to *nonfinite_result and clears the counter)
     int* nonfinite_result;
     int32_t col_lo, col_hi; // FD columns handled by this launch
-    // Packed non-zeros (modes 6-9).  The static pattern of J_T is the tracer's: column j can be non-zero in
-    // the collocation block its state slice owns (N consecutive rows) and at its row items, in that order.
-    const int64_t* poff;    // [n] offset of column j's entries in the packed array (modes 7-9)
-    const int64_t* pind;    // [n+1] the pattern's own prefix sums (modes 8, 9): column j has pind[j+1]-pind[j] entries
-    const int32_t* prow;    // [nnz] row index of every pattern entry, flat (modes 8, 9): no table walks there
-    int32_t* pint;          // mode 6: [n] entries per column (out); mode 7: row index of every packed entry (out)
-    double* pvals;          // packed values: mode 8 writes them, mode 9 reads them
-    double* ptail;          // mode 8: m + 1 doubles that receive F(x0) and the count of non-finite rows, or NULL
-    int32_t ulo, uhi;       // mode 9: columns to scatter; those inside [col_lo, col_hi) are this rank's own: skipped
+    // Packed non-zeros (OGK_PATTERN_COUNT to OGK_UNPACK).  The static pattern of J_T is the tracer's: column j can be
+    // non-zero in the collocation block its state slice owns (N consecutive rows) and at its row items, in that order.
+    const int64_t* poff;    // [n] offset of column j's entries in the packed array (OGK_PATTERN_ROWS, OGK_PACK, OGK_UNPACK)
+    const int64_t* pind;    // [n+1] the pattern's own prefix sums (OGK_PACK, OGK_UNPACK): column j has pind[j+1]-pind[j] entries
+    const int32_t* prow;    // [nnz] row index of every pattern entry, flat (OGK_PACK, OGK_UNPACK): no table walks there
+    int32_t* pint;          // OGK_PATTERN_COUNT: [n] entries per column (out); OGK_PATTERN_ROWS: row index of every packed entry (out)
+    double* pvals;          // packed values: OGK_PACK writes them, OGK_UNPACK reads them
+    double* ptail;          // OGK_PACK: m + 1 doubles that receive F(x0) and the count of non-finite rows, or NULL
+    int32_t ulo, uhi;       // OGK_UNPACK: columns to scatter; those inside [col_lo, col_hi) are this rank's own: skipped
     double* trace;          // -DOGK_TRACE builds: [workgroup][8 wavefronts][8] phase stamps (else unused)
     int64_t dfrag_off[OGK_MAX_PHASE];
 } ogk_args;
@@ -86,23 +130,23 @@ typedef struct ogk_args {
 // ogk_args record in a device table that the runtime writes when the batch is created: its own scratch, ticket,
 // counters and persistent-zero jt with its own jt_state / jt_launches words; dfrag, cvec and the pattern tables are
 // the handle's.  The table holds OGK_BATCH_SETS record sets of `capacity` lanes each: set 0 is what the one-launch
-// sweep (mode 11) runs; sets 1 and 2 are what the evaluation (mode 12) runs, with jt_bump = 0 and 1.  What changes
-// from call to call - where the caller's X, H, F0 and packed values are - is written into the records by mode 13
-// (one thread per record) ahead of EVERY mode 11 / 12 launch, stream-ordered before it, so that those launches take
-// the table and the lane count only and a captured graph carries its own binding.  Mode 13 also zeroes the non-finite
+// sweep (OGK_BATCH_FUSED) runs; sets 1 and 2 are what the evaluation (OGK_BATCH_EVAL) runs, with jt_bump = 0 and 1.  What changes
+// from call to call - where the caller's X, H, F0 and packed values are - is written into the records by OGK_BATCH_BIND
+// (one thread per record) ahead of EVERY OGK_BATCH_FUSED / OGK_BATCH_EVAL launch, stream-ordered before it, so that those launches take
+// the table and the lane count only and a captured graph carries its own binding.  OGK_BATCH_BIND also zeroes the non-finite
 // counter of the lanes an evaluation is about to run (a lane's count stays where it is while launches run without it).
 #define OGK_BATCH_SETS 3
 typedef struct ogk_batch_args {
-    ogk_args* lanes;        // modes 11, 12: the record set to run ([capacity] records); mode 13: the whole table
+    ogk_args* lanes;        // OGK_BATCH_FUSED, OGK_BATCH_EVAL: the record set to run ([capacity] records); OGK_BATCH_BIND: the whole table
     int32_t count;          // lanes of this launch (<= capacity)
     int32_t capacity;
-    // mode 13: lane k reads X + k * n (and H + k * n), writes F0 + k * m (and vals + k * nnz; vals may be NULL)
+    // OGK_BATCH_BIND: lane k reads X + k * n (and H + k * n), writes F0 + k * m (and vals + k * nnz; vals may be NULL)
     const double* X;
     const double* H;
     double* F0;
     double* vals;
     int64_t nnz;
-    int32_t clear_set;      // mode 13: zero *nonfinite of the first `count` records of this set (-1: none)
+    int32_t clear_set;      // OGK_BATCH_BIND: zero *nonfinite of the first `count` records of this set (-1: none)
 } ogk_batch_args;
 
 #ifdef __cplusplus
@@ -110,22 +154,23 @@ extern "C" {
 #endif
 // exported by every callback module
 int ogk_get_info(ogk_info* out);
-// mode 0: evaluate F(x0) into f0 (+ scratch y0/t0/z).  mode 1: structured FD sweep over
-// [col_lo, col_hi) into jt (needs mode 0's outputs at the same x0).  mode 2: dense FD sweep.
-// mode 3 / 4: exact Jacobian, dense / structured (needs mode 0).  mode 5: modes 0 + 1 in one launch.
-// mode 6 / 7: the static pattern (entries per column / row indices).  mode 8: gather the pattern entries of
-// the columns [col_lo, col_hi) of `jt` into pvals.  mode 9: scatter pvals into the rows [ulo, uhi) of a full
-// matrix `jt` (row 0 = column 0), filling those rows from z first when F(x0) has non-finite rows or the
-// previous step left such a fill behind.  mode 10: count one launch into *jt_launches.
+// OGK_EVAL: evaluate F(x0) into f0 (+ scratch y0/t0/z).  OGK_SWEEP: structured FD sweep over
+// [col_lo, col_hi) into jt (needs OGK_EVAL's outputs at the same x0).  OGK_DENSE: dense FD sweep.
+// OGK_EXACT_DENSE / OGK_EXACT: exact Jacobian, dense / structured (needs OGK_EVAL).  OGK_FUSED: OGK_EVAL + OGK_SWEEP
+// in one launch.  OGK_PATTERN_COUNT / OGK_PATTERN_ROWS: the static pattern (entries per column / row indices).
+// OGK_PACK: gather the pattern entries of the columns [col_lo, col_hi) of `jt` into pvals.  OGK_UNPACK: scatter pvals
+// into the rows [ulo, uhi) of a full matrix `jt` (row 0 = column 0), filling those rows from z first when F(x0) has
+// non-finite rows or the previous step left such a fill behind.  OGK_COUNT_LAUNCH: count one launch into *jt_launches.
 // Only enqueues kernels on `stream`; returns a hipError_t value (0 = success).
 int ogk_launch(const ogk_args* args, int mode, void* stream);
-// exported by the batch part of a module only (OGK_PART == 4, built when a batch is first asked for).
-// mode 11: ogk_fused over all n columns for `count` lanes in one launch.  mode 12: ogk_eval for `count` lanes.
-// mode 13: bind the caller's arrays to the records (see above).
-// The exact batch part (OGK_PART == 5, <module>.batchx.so, built when a batched exact Jacobian is first asked for)
-// exports the same name for its one mode, and ogk_get_info.  mode 14: ogk_exact_struct over all n columns for `count`
-// lanes in one launch, on record set 2 after a mode-12 launch on the same set (which counts the launch into each
-// lane's *jt_launches); every value also goes to its place in the lane's packed array when the record's pvals is set.
+// exported by the batch part of a module only (OGK_PART_BATCH, built when a batch is first asked for).
+// OGK_BATCH_FUSED: ogk_fused over all n columns for `count` lanes in one launch.  OGK_BATCH_EVAL: ogk_eval for `count`
+// lanes.  OGK_BATCH_BIND: bind the caller's arrays to the records (see above).
+// The exact batch part (OGK_PART_BATCH_EXACT, <module>.batchx.so, built when a batched exact Jacobian is first asked
+// for) exports the same name for its one mode, and ogk_get_info.  OGK_BATCH_EXACT: ogk_exact_struct over all n columns
+// for `count` lanes in one launch, on record set 2 after an OGK_BATCH_EVAL launch on the same set (which counts the
+// launch into each lane's *jt_launches); every value also goes to its place in the lane's packed array when the
+// record's pvals is set.
 int ogk_launch_batch(const ogk_batch_args* args, int mode, void* stream);
 #ifdef __cplusplus
 }

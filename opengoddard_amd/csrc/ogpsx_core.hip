@@ -111,15 +111,15 @@ struct og_problem_s {
     double* d_xop = nullptr;
     double* d_t0 = nullptr;
     double* d_z = nullptr;
-    int* d_flags = nullptr;             // two non-finite-row counters used alternately, then the ticket of the
-    int flag_slot = 0;                  // fused launch (evaluation workgroups that have finished, ever)
+    int* d_flags = nullptr;             // OGK_FLAG_WORDS ints (ogk.h: enum ogk_flag)
+    int flag_slot = 0;                  // which of OGK_FLAG_COUNT_A / _B the latest two-launch evaluation counted into
     int n_eval_blocks = 0;
     double* d_trace = nullptr;          // phase stamps of -DOGK_TRACE kernel builds (tools/trace_fused.py)
-    // how og_fd_sweep_dev runs: 5 evaluation + structured sweep in one launch (default), 1 the same as two
-    // launches (OGPSX_SWEEP=split), 2 evaluation + dense sweep (OGPSX_SWEEP=dense).  og_fd_columns_dev (the
-    // sweep alone, F(x0) supplied) uses 1 or 2.
-    int sweep_mode = 5;
-    int exact_mode = 4;                 // 4 structured (default), 3 dense (OGPSX_SWEEP=dense)
+    // how og_fd_sweep_dev runs: OGK_FUSED evaluation + structured sweep in one launch (default), OGK_SWEEP the same
+    // as two launches (OGPSX_SWEEP=split), OGK_DENSE evaluation + dense sweep (OGPSX_SWEEP=dense).  og_fd_columns_dev
+    // (the sweep alone, F(x0) supplied) uses OGK_SWEEP or OGK_DENSE: columns_mode().
+    int sweep_mode = OGK_FUSED;
+    int exact_mode = OGK_EXACT;         // structured (default), OGK_EXACT_DENSE (OGPSX_SWEEP=dense)
     hipStream_t stream = nullptr;
     // persistent-zero output buffers (og_jt_register_dev): the sweep writes only what can be non-zero.  Each
     // registration owns one word of d_state (ogk.h: jt_state); word 0 is the stand-in for unregistered buffers.
@@ -167,10 +167,23 @@ struct og_problem_s {
         // without the trial).
         int choice = 0;                 // 0 undecided, 1 mapped, 2 staged
         int calls = 0;
-        double t_mapped = 0.0, t_staged = 0.0;
         bool last_staged = false;       // the last call scattered on the host (a NaN fill of its is the host's to clean)
         bool registered_here = false;   // hipHostRegister was this library's doing (memory from og_pinned_alloc needs none)
         double best_mapped = 1e30, best_staged = 1e30;
+        // does this call of og_fd_sweep take the mapped launch?  (forced: OGPSX_HOST decides without the trial)
+        bool take_mapped(bool forced) {
+            if (forced) choice = 1;
+            return choice == 1 || (choice == 0 && calls < 5);
+        }
+        // a call of the trial took dt seconds: calls 0-1 mapped (warm-up), 2-4 mapped timed, 5-6 packed (warm-up: pattern,
+        // staging, its device buffer), 7-9 packed timed; the FASTEST call of each decides (a mean would carry one-time
+        // costs of the first calls)
+        void trial_call(double dt) {
+            const int c = calls++;
+            if (c >= 2 && c <= 4) best_mapped = std::min(best_mapped, dt);
+            if (c >= 7 && c <= 9) best_staged = std::min(best_staged, dt);
+            if (calls >= 10) choice = best_mapped <= best_staged ? 1 : 2;
+        }
     };
     std::vector<host_reg> host_regs;
     // column sharding (og_shard_plan)
@@ -192,6 +205,19 @@ static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups 
 
 namespace {
 
+// evaluation + sweep really are ONE launch on this handle (asked for, and the module's LDS window allows it)
+bool one_launch(const og_problem_s* p) { return p->sweep_mode == OGK_FUSED && p->fused_ok; }
+
+// the sweep as a launch of its own (F(x0) is there already): the structured kernel unless the dense one is asked for
+int columns_mode(const og_problem_s* p) { return p->sweep_mode == OGK_FUSED ? OGK_SWEEP : p->sweep_mode; }
+
+// the registration of exactly this block of columns at this address as a persistent-zero buffer, or nullptr
+og_problem_s::jt_reg* find_jt_reg(og_problem_s* p, const double* jt, int lo, int hi) {
+    for (auto& r : p->regs)
+        if (r.ptr == jt && r.lo == lo && r.hi == hi) return &r;
+    return nullptr;
+}
+
 void fill_args(og_problem_s* p, ogk_args* a, const double* x, const double* h, double* f0,
                double* jt, int lo, int hi, bool new_launch = true) {
     memset(a, 0, sizeof *a);
@@ -206,7 +232,7 @@ void fill_args(og_problem_s* p, ogk_args* a, const double* x, const double* h, d
     a->z = p->d_z;
     a->nonfinite = p->d_flags + p->flag_slot;
     a->nonfinite_next = p->d_flags + (p->flag_slot ^ 1);
-    a->ready = reinterpret_cast<unsigned*>(p->d_flags + 2);
+    a->ready = reinterpret_cast<unsigned*>(p->d_flags + OGK_FLAG_TICKET);
     a->trace = p->d_trace;
     a->jt = jt;
     a->col_lo = lo;
@@ -217,23 +243,32 @@ void fill_args(og_problem_s* p, ogk_args* a, const double* x, const double* h, d
     a->jt_bump = 0;
     a->jt_state = p->d_state;
     a->jt_launches = p->d_state + 1;
-    a->nonfinite_result = p->d_flags + 4;
+    a->nonfinite_result = p->d_flags + OGK_FLAG_FUSED_RESULT;
     if (!new_launch && p->nf_read) a->nonfinite = p->nf_read;     // pack / unpack: the count the last evaluation left
-    if (jt)
-        for (size_t i = 0; i < p->regs.size(); ++i) {
-            auto& r = p->regs[i];
-            if (r.ptr == jt && r.lo == lo && r.hi == hi) {
-                a->jt_sparse = 1;
-                a->jt_state = p->d_state + 2 * r.slot;
-                a->jt_launches = a->jt_state + 1;
-                break;
-            }
-        }
+    if (const og_problem_s::jt_reg* r = jt ? find_jt_reg(p, jt, lo, hi) : nullptr) {
+        a->jt_sparse = 1;
+        a->jt_state = p->d_state + 2 * r->slot;
+        a->jt_launches = a->jt_state + 1;
+    }
     memcpy(a->dfrag_off, p->dfrag_off, sizeof(a->dfrag_off));
 }
 
-int launch_failed(og_problem_s*, int rc, const char* where) {
-    return fail(100 + rc, std::string(where) + ": " + hipGetErrorString((hipError_t)rc));
+// The one-launch form (OGK_FUSED) counts non-finite rows in a word of its own, which its last evaluation workgroup
+// moves to the result word and clears: the launch arguments depend on nothing but the pointers (a captured graph can
+// be replayed).  `a` comes from fill_args.
+void one_launch_args(og_problem_s* p, ogk_args* a) {
+    a->nonfinite = p->d_flags + OGK_FLAG_FUSED_COUNT;
+    p->nf_read = a->nonfinite_result;
+}
+
+// the pattern tables of a pack / unpack launch; poff: where column j's entries start in the packed array
+void pattern_args(og_problem_s* p, ogk_args* a, const int64_t* poff) {
+    a->poff = poff, a->pind = p->d_indptr, a->prow = p->d_rows;
+}
+
+// a launcher's code -> 0, or this library's error for it
+int launched(int rc, const char* where) {
+    return rc ? fail(100 + rc, std::string(where) + ": " + hipGetErrorString((hipError_t)rc)) : 0;
 }
 
 // the handle's own Jacobian buffer (host-pointer entry points): sized for this block of columns and
@@ -250,13 +285,12 @@ int own_jt(og_problem_s* p, int lo, int hi) {
         OG_HIP(hipMalloc(&p->d_jt, sizeof(double) * need));
         p->jt_capacity = need;
     }
-    for (auto& r : p->regs)
-        if (r.ptr == p->d_jt && r.lo == lo && r.hi == hi) return 0;
+    if (find_jt_reg(p, p->d_jt, lo, hi)) return 0;
     return og_jt_register_dev(p, p->d_jt, lo, hi, p->stream);
 }
 
-// the static pattern, once per handle: entries per column from the module (mode 6), prefix sums here, row
-// indices from the module again (mode 7)
+// the static pattern, once per handle: entries per column from the module (OGK_PATTERN_COUNT), prefix sums here,
+// row indices from the module again (OGK_PATTERN_ROWS)
 int ensure_pattern(og_problem_s* p) {
     if (p->have_pattern) return 0;
     OG_HIP(hipSetDevice(p->device));
@@ -266,7 +300,7 @@ int ensure_pattern(og_problem_s* p) {
     ogk_args a;
     fill_args(p, &a, nullptr, nullptr, nullptr, nullptr, 0, 0, false);
     a.pint = d_cnt;
-    int rc = p->launch(&a, 6, p->stream);
+    int rc = p->launch(&a, OGK_PATTERN_COUNT, p->stream);
     std::vector<int32_t> cnt((size_t)n);
     hipError_t e = rc ? (hipError_t)rc : hipMemcpyAsync(cnt.data(), d_cnt, sizeof(int32_t) * (size_t)n,
                                                         hipMemcpyDeviceToHost, p->stream);
@@ -282,7 +316,7 @@ int ensure_pattern(og_problem_s* p) {
     OG_HIP(hipMalloc(&d_rows, sizeof(int32_t) * (nnz ? nnz : 1)));
     a.pint = d_rows;
     a.poff = p->d_indptr;
-    rc = p->launch(&a, 7, p->stream);
+    rc = p->launch(&a, OGK_PATTERN_ROWS, p->stream);
     p->rows.assign(nnz, 0);
     e = rc ? (hipError_t)rc : hipMemcpyAsync(p->rows.data(), d_rows, sizeof(int32_t) * nnz, hipMemcpyDeviceToHost,
                                              p->stream);
@@ -396,13 +430,11 @@ int download_block(og_problem_s* p, int lo, int hi, double* JT, double* F0, cons
     if (!already_packed) {              // (the one-launch sweep of og_fd_sweep wrote d_down itself)
         ogk_args a;
         fill_args(p, &a, p->d_x, p->d_h, p->d_f0, const_cast<double*>(d_src), lo, hi, false);
-        a.poff = p->d_indptr;
-        a.pind = p->d_indptr;
-        a.prow = p->d_rows;
+        pattern_args(p, &a, p->d_indptr);
         a.pvals = p->d_down - first;
         a.ptail = p->d_down + nnz;
-        rc = p->launch(&a, 8, p->stream);
-        if (rc) return fail(100 + rc, std::string("og_fd_sweep: pack: ") + hipGetErrorString((hipError_t)rc));
+        rc = p->launch(&a, OGK_PACK, p->stream);
+        if (rc) return launched(rc, "og_fd_sweep: pack");
     }
     // The packed block comes down in up to four pieces, each with an event behind it, and the host scatters piece c
     // while piece c + 1 crosses PCIe (round 6; measured before, C3: 39 us waiting for upload + launch + ONE copy, then
@@ -475,6 +507,80 @@ int download_block(og_problem_s* p, int lo, int hi, double* JT, double* F0, cons
     }
     g_host_clock.done();
     return 0;
+}
+
+// The three forms of og_fd_sweep (which decides; p->d_jt is registered for [lo, hi) by then).
+
+// Mapped host matrix: ONE launch writes the non-zeros into the caller's matrix and F(x0) + the count of non-finite rows
+// into the pinned staging buffer, both over PCIe; the host waits for the launch and is done.  in_place: the launch
+// reads x | h out of mapped host memory too and p->d_x | p->d_h are left as they were.
+int sweep_mapped(og_problem_s* p, og_problem_s::host_reg* reg, const double* x, const double* hstep, int lo, int hi,
+                 double* JT, double* F0, bool in_place) {
+    int rc = in_place ? 0 : upload_point(p, x, hstep);
+    if (rc) return rc;
+    g_host_clock.mark(0);
+    rc = ensure_staging(p, (size_t)p->m + 1);
+    if (rc) return rc;
+    if (reg->dirty && reg->last_staged) {        // (a NaN block the packed path downloaded: not the device's to clean)
+        memset(JT, 0, sizeof(double) * (size_t)(hi - lo) * (size_t)p->m);
+        reg->dirty = false;
+    }
+    reg->last_staged = false;
+    void* tail = nullptr;
+    OG_HIP(hipHostGetDevicePointer(&tail, p->h_down, 0));
+    const double *kx = p->d_x, *kh = p->d_h;
+    if (in_place) {
+        if (!p->h_xh) OG_HIP(hipHostMalloc(&p->h_xh, sizeof(double) * 2 * (size_t)p->n, hipHostMallocNonCoherent | hipHostMallocMapped));
+        memcpy(p->h_xh, x, sizeof(double) * (size_t)p->n);
+        memcpy(p->h_xh + p->n, hstep, sizeof(double) * (size_t)p->n);
+        void* dxh = nullptr;
+        OG_HIP(hipHostGetDevicePointer(&dxh, p->h_xh, 0));
+        kx = (const double*)dxh;
+        kh = kx + p->n;
+    }
+    ogk_args a;
+    fill_args(p, &a, kx, kh, (double*)tail, reg->mapped, lo, hi);
+    one_launch_args(p, &a);
+    a.ptail = (double*)tail;
+    rc = p->launch(&a, OGK_FUSED, p->stream);
+    if (rc) return launched(rc, "og_fd_sweep");
+    g_host_clock.mark(1);
+    OG_HIP(hipStreamSynchronize(p->stream));
+    g_host_clock.mark(3);
+    if (F0) memcpy(F0, p->h_down, sizeof(double) * (size_t)p->m);
+    // (rows of NaN in every column were written by the launch itself and the next sweep cleans them, as in a
+    // device buffer; a packed download into this matrix in between - the exact mode - zeroes it first)
+    reg->dirty = p->h_down[(size_t)p->m] != 0.0;
+    g_host_clock.mark(4);
+    g_host_clock.done();
+    return 0;
+}
+
+// Registered host matrix, packed: ONE launch into the handle's own buffer leaves the packed non-zeros, F(x0) and the
+// count of non-finite rows contiguous in the staging buffer, one pinned copy brings them down, the host scatters
+int sweep_packed(og_problem_s* p, int lo, int hi, double* JT, double* F0) {
+    int rc = ensure_pattern(p);
+    if (rc) return rc;
+    const int64_t first = p->indptr[(size_t)lo], nnz = p->indptr[(size_t)hi] - first;
+    rc = ensure_staging(p, (size_t)nnz + (size_t)p->m + 1);
+    if (rc) return rc;
+    ogk_args a;
+    fill_args(p, &a, p->d_x, p->d_h, p->d_down + nnz, p->d_jt, lo, hi);
+    one_launch_args(p, &a);
+    a.poff = p->d_indptr;
+    a.pvals = p->d_down - first;
+    a.ptail = p->d_down + nnz;
+    rc = p->launch(&a, OGK_FUSED, p->stream);
+    if (rc) return launched(rc, "og_fd_sweep");
+    g_host_clock.mark(1);
+    return download_block(p, lo, hi, JT, F0, nullptr, true);
+}
+
+// Anything else (an unregistered matrix, a handle without the one-launch form): the sweep as og_fd_sweep_dev runs it,
+// then the block comes down - packed for a registered matrix, dense otherwise
+int sweep_download(og_problem_s* p, int lo, int hi, double* JT, double* F0) {
+    const int rc = og_fd_sweep_dev(p, p->d_x, p->d_h, lo, hi, p->d_jt, p->d_f0, p->stream);
+    return rc ? rc : download_block(p, lo, hi, JT, F0);
 }
 
 }  // namespace
@@ -673,9 +779,8 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
     if (e == hipSuccess) e = hipMalloc(&p->d_xop, sizeof(double) * (size_t)(info.n_y0 > 0 ? info.n_y0 : 1));
     if (e == hipSuccess) e = hipMalloc(&p->d_t0, sizeof(double) * (size_t)p->m);
     if (e == hipSuccess) e = hipMalloc(&p->d_z, sizeof(double) * (size_t)p->m);
-    // {non-finite counters of the two-launch form (alternating), ticket, counter of the one-launch form, its result}
-    if (e == hipSuccess) e = hipMalloc(&p->d_flags, 8 * sizeof(int));
-    if (e == hipSuccess) e = hipMemset(p->d_flags, 0, 8 * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&p->d_flags, OGK_FLAG_WORDS * sizeof(int));
+    if (e == hipSuccess) e = hipMemset(p->d_flags, 0, OGK_FLAG_WORDS * sizeof(int));
     if (e == hipSuccess && getenv("OGPSX_TRACE")) {
         e = hipMalloc(&p->d_trace, sizeof(double) * OG_TRACE_DOUBLES);
         if (e == hipSuccess) e = hipMemset(p->d_trace, 0, sizeof(double) * OG_TRACE_DOUBLES);
@@ -692,11 +797,11 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
     // measured against the two-launch form with such a buffer (bench step, us, one launch / two): C2 4.8 / 8.1,
     // C3 7.6 / 12.4, C4 13.9 / 22.6, C5 23.9 / 33.0.  An unregistered buffer always takes two launches (the
     // module decides: the one-launch form never fills).
-    p->sweep_mode = 5;
-    if (mode_env && std::string(mode_env) == "dense") p->sweep_mode = 2, p->exact_mode = 3;
-    if (mode_env && std::string(mode_env) == "split") p->sweep_mode = 1;
-    if (mode_env && std::string(mode_env) == "fused") p->sweep_mode = 5;
-    if (p->n_eval_blocks <= 0 && p->sweep_mode == 5) p->sweep_mode = 1;
+    p->sweep_mode = OGK_FUSED;
+    if (mode_env && std::string(mode_env) == "dense") p->sweep_mode = OGK_DENSE, p->exact_mode = OGK_EXACT_DENSE;
+    if (mode_env && std::string(mode_env) == "split") p->sweep_mode = OGK_SWEEP;
+    if (mode_env && std::string(mode_env) == "fused") p->sweep_mode = OGK_FUSED;
+    if (p->n_eval_blocks <= 0 && p->sweep_mode == OGK_FUSED) p->sweep_mode = OGK_SWEEP;
     if (e == hipSuccess) e = hipStreamCreate(&p->stream);
     if (e != hipSuccess) {
         og_problem_destroy(p);
@@ -746,7 +851,7 @@ void og_problem_destroy(og_handle p) {
 
 int og_sweep_mode(og_handle p) { return p ? p->sweep_mode : 0; }
 
-int og_one_launch(og_handle p) { return (p && p->sweep_mode == 5 && p->fused_ok) ? 1 : 0; }
+int og_one_launch(og_handle p) { return (p && one_launch(p)) ? 1 : 0; }
 
 int og_nonfinite_rows(og_handle p, void* hip_stream, int32_t* rows) {
     if (!p || !rows) return fail(1, "og_nonfinite_rows: null argument");
@@ -839,7 +944,7 @@ int og_jt_register_host(og_handle p, double* JT, int32_t lo, int32_t hi) {
     double* mapped = nullptr;
     bool registered_here = false;
     static const bool staged = [] { const char* e = getenv("OGPSX_HOST"); return e && std::string(e) == "staged"; }();
-    if (!staged && p->sweep_mode == 5 && p->fused_ok) {
+    if (!staged && one_launch(p)) {
         OG_HIP(hipSetDevice(p->device));
         void* dev = nullptr;
         // memory that came from og_pinned_alloc / hipHostMalloc is mapped already (and in the driver's own large fragments:
@@ -897,7 +1002,7 @@ int og_jt_host_path(og_handle p, const double* JT, int32_t* path) {
     if (!p || !path) return fail(1, "og_jt_host_path: null argument");
     *path = -1;
     for (auto& r : p->host_regs)
-        if (r.ptr == JT) *path = !(p->sweep_mode == 5 && p->fused_ok) ? 3 : !r.mapped ? 2 : r.choice;
+        if (r.ptr == JT) *path = !one_launch(p) ? 3 : !r.mapped ? 2 : r.choice;
     return 0;
 }
 
@@ -937,13 +1042,10 @@ int og_pack_dev(og_handle p, const double* d_JT, int32_t lo, int32_t hi, double*
     if (rc) return rc;
     ogk_args a;
     fill_args(p, &a, nullptr, nullptr, p->d_f0, const_cast<double*>(d_JT), lo, hi, false);
-    a.poff = p->d_indptr;
-    a.pind = p->d_indptr;
-    a.prow = p->d_rows;
+    pattern_args(p, &a, p->d_indptr);
     a.pvals = d_vals - p->indptr[(size_t)lo];
-    rc = p->launch(&a, 8, hip_stream);
-    if (rc) return fail(100 + rc, std::string("og_pack_dev: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    rc = p->launch(&a, OGK_PACK, hip_stream);
+    return launched(rc, "og_pack_dev");
 }
 
 int og_unpack_dev(og_handle p, const double* d_vals, int32_t lo, int32_t hi, double* d_JT, void* hip_stream) {
@@ -955,15 +1057,12 @@ int og_unpack_dev(og_handle p, const double* d_vals, int32_t lo, int32_t hi, dou
     fill_args(p, &a, nullptr, nullptr, p->d_f0, nullptr, lo, lo, false);
     a.jt = d_JT - (size_t)lo * (size_t)p->m;       // the kernel indexes rows by absolute column
     a.jt_sparse = 0;                               // plain scatter: no fill
-    a.poff = p->d_indptr;
-    a.pind = p->d_indptr;
-    a.prow = p->d_rows;
+    pattern_args(p, &a, p->d_indptr);
     a.pvals = const_cast<double*>(d_vals) - p->indptr[(size_t)lo];
     a.ulo = lo;
     a.uhi = hi;
-    rc = p->launch(&a, 9, hip_stream);
-    if (rc) return fail(100 + rc, std::string("og_unpack_dev: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    rc = p->launch(&a, OGK_UNPACK, hip_stream);
+    return launched(rc, "og_unpack_dev");
 }
 
 int og_shard_plan(og_handle p, int32_t world, int32_t* block_cols, int64_t* block_vals) {
@@ -1002,13 +1101,10 @@ int og_shard_pack_dev(og_handle p, int32_t rank, const double* d_JT_block, doubl
     const int lo = std::min(n, rank * B), hi = std::min(n, lo + B);
     ogk_args a;
     fill_args(p, &a, nullptr, nullptr, p->d_f0, const_cast<double*>(d_JT_block), lo, hi, false);
-    a.poff = p->d_shard_off;
-    a.pind = p->d_indptr;
-    a.prow = p->d_rows;
+    pattern_args(p, &a, p->d_shard_off);
     a.pvals = d_send - (int64_t)rank * p->shard_block_vals;
-    int rc = p->launch(&a, 8, hip_stream);
-    if (rc) return fail(100 + rc, std::string("og_shard_pack_dev: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    int rc = p->launch(&a, OGK_PACK, hip_stream);
+    return launched(rc, "og_shard_pack_dev");
 }
 
 int og_shard_sweep_dev(og_handle p, int32_t rank, const double* d_x, const double* d_h, double* d_JT_block,
@@ -1021,15 +1117,12 @@ int og_shard_sweep_dev(og_handle p, int32_t rank, const double* d_x, const doubl
     if (hi <= lo) return og_eval_dev(p, d_x, d_F0, hip_stream);        // more ranks than columns: F(x0) only
     ogk_args a;
     fill_args(p, &a, d_x, d_h, d_F0, d_JT_block, lo, hi);
-    if (p->sweep_mode == 5 && p->fused_ok && a.jt_sparse) {
+    if (one_launch(p) && a.jt_sparse) {
         // ONE launch: F(x0), the block's non-zeros into J_T and, the same values, into this rank's message
-        a.nonfinite = p->d_flags + 3;
-        p->nf_read = a.nonfinite_result;
+        one_launch_args(p, &a);
         a.poff = p->d_shard_off;
         a.pvals = d_send - (int64_t)rank * p->shard_block_vals;
-        const int rc = p->launch(&a, 5, hip_stream);
-        if (rc) return launch_failed(p, rc, "og_shard_sweep_dev");
-        return 0;
+        return launched(p->launch(&a, OGK_FUSED, hip_stream), "og_shard_sweep_dev");
     }
     const int rc = og_fd_sweep_dev(p, d_x, d_h, lo, hi, d_JT_block, d_F0, hip_stream);
     return rc ? rc : og_shard_pack_dev(p, rank, d_JT_block, d_send, hip_stream);
@@ -1049,9 +1142,7 @@ int og_shard_unpack_dev(og_handle p, int32_t rank, const double* d_recv, double*
         return fail(1, "og_shard_unpack_dev: this rank's block of the replica is not a registered buffer");
     a.jt = d_JT_full;
     a.jt_sparse = 1;
-    a.poff = p->d_shard_off;
-    a.pind = p->d_indptr;
-    a.prow = p->d_rows;
+    pattern_args(p, &a, p->d_shard_off);
     a.pvals = const_cast<double*>(d_recv);
     a.ulo = 0;
     a.uhi = n;
@@ -1062,11 +1153,10 @@ int og_shard_unpack_dev(og_handle p, int32_t rank, const double* d_recv, double*
         a.jt_state = p->d_state + 2 * (OG_MAX_JT_REGS + 1);
         a.jt_launches = a.jt_state + 1;
         a.jt_bump = 1;
-        rc = p->launch(&a, 10, hip_stream);
+        rc = p->launch(&a, OGK_COUNT_LAUNCH, hip_stream);
     }
-    if (!rc) rc = p->launch(&a, 9, hip_stream);
-    if (rc) return fail(100 + rc, std::string("og_shard_unpack_dev: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    if (!rc) rc = p->launch(&a, OGK_UNPACK, hip_stream);
+    return launched(rc, "og_shard_unpack_dev");
 }
 
 int og_problem_dims(og_handle p, int32_t* n, int32_t* m, int32_t* m_eq, int32_t* m_ineq) {
@@ -1100,9 +1190,8 @@ int og_eval_dev(og_handle p, const double* d_x, double* d_F, void* hip_stream) {
     p->flag_slot ^= 1;                      // this evaluation counts non-finite rows into a fresh slot
     fill_args(p, &a, d_x, nullptr, d_F, nullptr, 0, 0);
     p->nf_read = a.nonfinite;
-    int rc = p->launch(&a, 0, hip_stream);
-    if (rc) return fail(100 + rc, std::string("og_eval_dev: ") + hipGetErrorString((hipError_t)rc));
-    return 0;
+    int rc = p->launch(&a, OGK_EVAL, hip_stream);
+    return launched(rc, "og_eval_dev");
 }
 
 int og_fd_sweep_dev(og_handle p, const double* d_x, const double* d_h, int32_t lo, int32_t hi,
@@ -1112,12 +1201,10 @@ int og_fd_sweep_dev(og_handle p, const double* d_x, const double* d_h, int32_t l
     ogk_args a;
     fill_args(p, &a, d_x, d_h, d_F0, d_JT, lo, hi);
     int rc;
-    if (p->sweep_mode == 5 && p->fused_ok && a.jt_sparse && hi > lo) {
-        // ONE launch.  Its arguments depend on nothing but the pointers: the count of non-finite rows, the ticket
-        // and the buffer's launch number are kept by the kernel itself (a captured graph can be replayed)
-        a.nonfinite = p->d_flags + 3;
-        p->nf_read = a.nonfinite_result;
-        rc = p->launch(&a, 5, hip_stream);
+    if (one_launch(p) && a.jt_sparse && hi > lo) {
+        // ONE launch: the ticket and the buffer's launch number, too, are kept by the kernel itself
+        one_launch_args(p, &a);
+        rc = p->launch(&a, OGK_FUSED, hip_stream);
     } else {
         p->flag_slot ^= 1;
         a.nonfinite = p->d_flags + p->flag_slot;
@@ -1126,11 +1213,10 @@ int og_fd_sweep_dev(og_handle p, const double* d_x, const double* d_h, int32_t l
         a.jt_bump = a.jt_sparse;                    // F(x0) first: the sweep subtracts it; it also counts the launch
         rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
         if (rc) return rc;
-        rc = p->launch(&a, 0, hip_stream);
-        if (!rc) rc = p->launch(&a, p->sweep_mode == 5 ? 1 : p->sweep_mode, hip_stream);
+        rc = p->launch(&a, OGK_EVAL, hip_stream);
+        if (!rc) rc = p->launch(&a, columns_mode(p), hip_stream);
     }
-    if (rc) return launch_failed(p, rc, "og_fd_sweep_dev");
-    return 0;
+    return launched(rc, "og_fd_sweep_dev");
 }
 
 int og_fd_columns_dev(og_handle p, const double* d_x, const double* d_h, int32_t lo, int32_t hi,
@@ -1139,10 +1225,9 @@ int og_fd_columns_dev(og_handle p, const double* d_x, const double* d_h, int32_t
     if (lo < 0 || hi > p->n || lo > hi) return fail(1, "og_fd_columns_dev: bad column range");
     ogk_args a;
     fill_args(p, &a, d_x, d_h, const_cast<double*>(d_F0), d_JT, lo, hi);
-    int rc = a.jt_sparse ? p->launch(&a, 10, hip_stream) : 0;       // count this launch into the registered buffer
-    if (!rc) rc = p->launch(&a, p->sweep_mode == 5 ? 1 : p->sweep_mode, hip_stream);
-    if (rc) return launch_failed(p, rc, "og_fd_columns_dev");
-    return 0;
+    int rc = a.jt_sparse ? p->launch(&a, OGK_COUNT_LAUNCH, hip_stream) : 0;     // (into the registered buffer)
+    if (!rc) rc = p->launch(&a, columns_mode(p), hip_stream);
+    return launched(rc, "og_fd_columns_dev");
 }
 
 int og_jacobian_exact_dev(og_handle p, const double* d_x, int32_t lo, int32_t hi, double* d_JT, double* d_F0,
@@ -1154,10 +1239,9 @@ int og_jacobian_exact_dev(og_handle p, const double* d_x, int32_t lo, int32_t hi
     fill_args(p, &a, d_x, nullptr, d_F0, d_JT, lo, hi);
     p->nf_read = a.nonfinite;
     a.jt_bump = a.jt_sparse;
-    int rc = p->launch(&a, 0, hip_stream);          // F(x0) and the base collocation products
+    int rc = p->launch(&a, OGK_EVAL, hip_stream);   // F(x0) and the base collocation products
     if (!rc) rc = p->launch(&a, p->exact_mode, hip_stream);   // forward-mode derivatives, column by column
-    if (rc) return launch_failed(p, rc, "og_jacobian_exact_dev");
-    return 0;
+    return launched(rc, "og_jacobian_exact_dev");
 }
 
 int og_eval(og_handle p, const double* x, double* F) {
@@ -1178,116 +1262,39 @@ int og_fd_sweep(og_handle p, const double* x, const double* hstep, int32_t lo, i
     if (!p || !x || !hstep || !JT) return fail(1, "og_fd_sweep: null argument");
     if (lo < 0 || hi > p->n || lo > hi) return fail(1, "og_fd_sweep: bad column range");
     OG_HIP(hipSetDevice(p->device));
-    const size_t need = (size_t)(hi - lo) * (size_t)p->m;
-    if (need == 0) {                     // empty column range: only F(x) is produced
+    if ((size_t)(hi - lo) * (size_t)p->m == 0) {        // empty column range: only F(x) is produced
         if (!F0) return 0;
         return og_eval(p, x, F0);
     }
-    {
-        const int rcj = own_jt(p, lo, hi);
-        if (rcj) return rcj;
-    }
+    int rc = own_jt(p, lo, hi);
+    if (rc) return rc;
     g_host_clock.start();
     // (mapped matrix: the launch also reads x | h in place, out of a pinned buffer of their own - non-coherent host memory,
     // cached in L2 for the launch and visible at its boundary - instead of waiting for their copy: 5 us of a call.
     // OGPSX_HOST=copyx keeps the copy.)
     static const bool readx_mode = [] { const char* e = getenv("OGPSX_HOST"); return !(e && std::string(e) == "copyx"); }();
-    og_problem_s::host_reg* mreg = find_host_reg(p, JT, lo, hi);
+    og_problem_s::host_reg* reg = find_host_reg(p, JT, lo, hi);
     static const int forced = [] {
         const char* e = getenv("OGPSX_HOST");
         return (e && (std::string(e) == "mapped" || std::string(e) == "copyx")) ? 1 : 0;
     }();
-    bool use_mapped = mreg && mreg->mapped && p->sweep_mode == 5 && p->fused_ok;
-    if (use_mapped && forced) mreg->choice = 1;
-    const bool trial = use_mapped && mreg->choice == 0 && !forced;
-    if (use_mapped && !forced) use_mapped = mreg->choice == 1 || (mreg->choice == 0 && mreg->calls < 5);
+    // Which form this call takes.  The mapped launch needs the matrix mapped AND its mapped address registered on the
+    // device for exactly this block; while the trial runs (host_reg) a call that could take it may be sent down the
+    // packed form instead.  Everything that is not the mapped launch reads p->d_x | p->d_h and therefore starts with
+    // upload_point: no path reaches them with what an in-place call before left there.
+    const bool mappable = reg && reg->mapped && one_launch(p) && find_jt_reg(p, reg->mapped, lo, hi);
+    const bool mapped = mappable && reg->take_mapped(forced != 0);
+    const bool trial = mappable && reg->choice == 0;
     const double t_call = trial ? host_clock::now() : 0.0;
-    auto trial_done = [&] {
-        // calls 0-1 mapped (warm-up), 2-4 mapped timed, 5-6 packed (warm-up: pattern, staging, its device buffer), 7-9 packed
-        // timed; the FASTEST call of each decides (a mean would carry one-time costs of the first calls)
-        if (!trial) return;
-        const double dt = host_clock::now() - t_call;
-        const int c = mreg->calls++;
-        if (c >= 2 && c <= 4) mreg->best_mapped = std::min(mreg->best_mapped, dt);
-        if (c >= 7 && c <= 9) mreg->best_staged = std::min(mreg->best_staged, dt);
-        mreg->t_mapped = mreg->best_mapped;
-        mreg->t_staged = mreg->best_staged;
-        if (mreg->calls >= 10) mreg->choice = mreg->best_mapped <= mreg->best_staged ? 1 : 2;
-    };
-    const bool in_place = readx_mode && use_mapped;
-    int rc = in_place ? 0 : upload_point(p, x, hstep);
-    if (rc) return rc;
-    g_host_clock.mark(0);
-    if (og_problem_s::host_reg* reg = mreg; use_mapped) {
-        // mapped host matrix: ONE launch writes the non-zeros into the caller's matrix and F(x0) + the count of non-finite
-        // rows into the pinned staging buffer, both over PCIe; the host waits for the launch and is done
-        rc = ensure_staging(p, (size_t)p->m + 1);
-        if (rc) return rc;
-        if (reg->dirty && reg->last_staged) {        // (a NaN block the packed path downloaded: not the device's to clean)
-            memset(JT, 0, sizeof(double) * (size_t)(hi - lo) * (size_t)p->m);
-            reg->dirty = false;
-        }
-        reg->last_staged = false;
-        void* tail = nullptr;
-        OG_HIP(hipHostGetDevicePointer(&tail, p->h_down, 0));
-        const double *kx = p->d_x, *kh = p->d_h;
-        if (in_place) {
-            if (!p->h_xh) OG_HIP(hipHostMalloc(&p->h_xh, sizeof(double) * 2 * (size_t)p->n, hipHostMallocNonCoherent | hipHostMallocMapped));
-            memcpy(p->h_xh, x, sizeof(double) * (size_t)p->n);
-            memcpy(p->h_xh + p->n, hstep, sizeof(double) * (size_t)p->n);
-            void* dxh = nullptr;
-            OG_HIP(hipHostGetDevicePointer(&dxh, p->h_xh, 0));
-            kx = (const double*)dxh;
-            kh = kx + p->n;
-        }
-        ogk_args a;
-        fill_args(p, &a, kx, kh, (double*)tail, reg->mapped, lo, hi);
-        if (a.jt_sparse) {
-            a.nonfinite = p->d_flags + 3;
-            p->nf_read = a.nonfinite_result;
-            a.ptail = (double*)tail;
-            rc = p->launch(&a, 5, p->stream);
-            if (rc) return launch_failed(p, rc, "og_fd_sweep");
-            g_host_clock.mark(1);
-            OG_HIP(hipStreamSynchronize(p->stream));
-            g_host_clock.mark(3);
-            if (F0) memcpy(F0, p->h_down, sizeof(double) * (size_t)p->m);
-            // (rows of NaN in every column were written by the launch itself and the next sweep cleans them, as in a
-            // device buffer; a packed download into this matrix in between - the exact mode - zeroes it first)
-            reg->dirty = p->h_down[(size_t)p->m] != 0.0;
-            g_host_clock.mark(4);
-            g_host_clock.done();
-            trial_done();
-            return 0;
-        }
+    if (mapped) {
+        rc = sweep_mapped(p, reg, x, hstep, lo, hi, JT, F0, readx_mode);
+    } else {
+        rc = upload_point(p, x, hstep);
+        g_host_clock.mark(0);
+        if (!rc) rc = reg && one_launch(p) ? sweep_packed(p, lo, hi, JT, F0) : sweep_download(p, lo, hi, JT, F0);
     }
-    if (find_host_reg(p, JT, lo, hi) && p->sweep_mode == 5 && p->fused_ok) {
-        // registered host matrix: ONE launch leaves the packed non-zeros, F(x0) and the count of non-finite rows
-        // contiguous in the staging buffer, one pinned copy brings them down
-        rc = ensure_pattern(p);
-        if (rc) return rc;
-        const int64_t first = p->indptr[(size_t)lo], nnz = p->indptr[(size_t)hi] - first;
-        rc = ensure_staging(p, (size_t)nnz + (size_t)p->m + 1);
-        if (rc) return rc;
-        ogk_args a;
-        fill_args(p, &a, p->d_x, p->d_h, p->d_down + nnz, p->d_jt, lo, hi);
-        if (a.jt_sparse) {
-            a.nonfinite = p->d_flags + 3;
-            p->nf_read = a.nonfinite_result;
-            a.poff = p->d_indptr;
-            a.pvals = p->d_down - first;
-            a.ptail = p->d_down + nnz;
-            rc = p->launch(&a, 5, p->stream);
-            if (rc) return launch_failed(p, rc, "og_fd_sweep");
-            g_host_clock.mark(1);
-            rc = download_block(p, lo, hi, JT, F0, nullptr, true);
-            trial_done();
-            return rc;
-        }
-    }
-    rc = og_fd_sweep_dev(p, p->d_x, p->d_h, lo, hi, p->d_jt, p->d_f0, p->stream);
-    if (rc) return rc;
-    return download_block(p, lo, hi, JT, F0);
+    if (!rc && trial) reg->trial_call(host_clock::now() - t_call);
+    return rc;
 }
 
 int og_jacobian_exact(og_handle p, const double* x, int32_t lo, int32_t hi, double* JT, double* F0) {
@@ -1328,10 +1335,11 @@ struct og_batch_s {
     double* d_jt = nullptr;                 // [capacity][n][m]
     double* d_scratch = nullptr;            // per lane: y0 | xop | t0 | z
     size_t scratch_lane = 0, n_y0 = 0;
-    int* d_flags = nullptr;                 // [capacity][8]: as og_problem_s::d_flags
+    int* d_flags = nullptr;                 // [capacity][OGK_FLAG_WORDS]: as og_problem_s::d_flags
     uint32_t* d_state = nullptr;            // [capacity][2]: jt_state, jt_launches
-    // per lane: the word of its d_flags that holds the count of non-finite rows at its most recent point (0 after an
-    // evaluation launch, 4 after a one-launch sweep) - a lane keeps it while later launches run fewer lanes
+    // per lane: the word of its d_flags that holds the count of non-finite rows at its most recent point (OGK_FLAG_COUNT_A
+    // after an evaluation launch, OGK_FLAG_FUSED_RESULT after a one-launch sweep) - a lane keeps it while later launches
+    // run fewer lanes
     std::vector<int> nf_word;
     hipStream_t last_stream = nullptr;      // of the most recent launch (og_batch_lane_dev waits for this one only)
     // host-pointer entry points: device arrays [X | H], F, packed values and their pinned images
@@ -1364,7 +1372,14 @@ int batch_check(og_batch b, int32_t count, const char* who) {
     return 0;
 }
 
-ogk_args* batch_set(og_batch_s* b, int set) { return b->d_table + (size_t)set * (size_t)b->capacity; }
+ogk_batch_args batch_args(og_batch_s* b, int set, int count) {
+    ogk_batch_args ba;
+    memset(&ba, 0, sizeof ba);
+    ba.lanes = b->d_table + (size_t)set * (size_t)b->capacity;
+    ba.count = count;
+    ba.capacity = b->capacity;
+    return ba;
+}
 
 // Where this call's arrays are, written into the lane records by a one-thread-per-record launch ahead of EVERY batched
 // launch: the records are device state that a replayed graph rewrites behind the host's back, so the host keeps no
@@ -1372,16 +1387,113 @@ ogk_args* batch_set(og_batch_s* b, int set) { return b->d_table + (size_t)set * 
 // run (clear_set: the record set of that evaluation, or -1).
 int batch_bind(og_batch_s* b, int count, const double* X, const double* H, double* F, double* vals, int clear_set,
                hipStream_t s, const char* who) {
-    ogk_batch_args ba;
-    memset(&ba, 0, sizeof ba);
-    ba.lanes = b->d_table;
-    ba.count = count;
-    ba.capacity = b->capacity;
+    ogk_batch_args ba = batch_args(b, 0, count);        // (the whole table)
     ba.X = X, ba.H = H, ba.F0 = F, ba.vals = vals, ba.nnz = b->nnz;
     ba.clear_set = clear_set;
-    const int rc = b->p->batch_launch(&ba, 13, s);
-    if (rc) return launch_failed(b->p, rc, who);
+    const int rc = b->p->batch_launch(&ba, OGK_BATCH_BIND, s);
+    if (rc) return launched(rc, who);
     b->last_stream = s;
+    return 0;
+}
+
+// One batched launch of `count` lanes on a record set -> the launcher's code.  An evaluation or a one-launch sweep also
+// moves the lanes' counts of non-finite rows (og_batch_s::nf_word).
+int batch_run(og_batch_s* b, int set, int mode, int count, hipStream_t s) {
+    const ogk_batch_args ba = batch_args(b, set, count);
+    if (mode == OGK_BATCH_EXACT) return b->p->batch_exact_launch(&ba, mode, s);
+    std::fill_n(b->nf_word.begin(), count, mode == OGK_BATCH_FUSED ? (int)OGK_FLAG_FUSED_RESULT : (int)OGK_FLAG_COUNT_A);
+    return b->p->batch_launch(&ba, mode, s);
+}
+
+// The validation forms of a batch: after the batched evaluation on record set 2, the handle's own kernel `mode` lane
+// by lane on that lane's record, and the pack where packed values are asked for -> the launcher's code
+int batch_lanes_run(og_batch_s* b, int count, int mode, const double* d_X, const double* d_H, double* d_F0,
+                    double* d_vals, hipStream_t s) {
+    og_problem_s* p = b->p;
+    int rc = 0;
+    for (int k = 0; !rc && k < count; ++k) {
+        ogk_args a = b->table[2 * (size_t)b->capacity + (size_t)k];
+        a.x0 = d_X + (size_t)k * (size_t)p->n;
+        if (d_H) a.h = d_H + (size_t)k * (size_t)p->n;
+        a.f0 = d_F0 + (size_t)k * (size_t)p->m;
+        rc = p->launch(&a, mode, s);
+        if (!rc && d_vals) {
+            a.pind = p->d_indptr;
+            a.prow = p->d_rows;
+            a.pvals = d_vals + (size_t)k * (size_t)b->nnz;
+            rc = p->launch(&a, OGK_PACK, s);
+        }
+    }
+    return rc;
+}
+
+// An on-demand part of the handle's module (`what`: the batch part, the exact batch part): open it and check that it
+// was compiled from the same generated header as the module
+int load_module_part(og_problem_s* p, const char* path, const std::string& who, const std::string& what, void** handle,
+                     ogk_launch_batch_fn* launch) {
+    if (!path) return fail(4, who + ": the module's " + what + " is not loaded and no path was given");
+    void* mod = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+    if (!mod) return fail(4, who + ": dlopen of the " + what + " failed: " + dlerror());
+    ogk_get_info_fn get_info = (ogk_get_info_fn)dlsym(mod, "ogk_get_info");
+    ogk_launch_batch_fn fn = (ogk_launch_batch_fn)dlsym(mod, "ogk_launch_batch");
+    ogk_info info;
+    memset(&info, 0, sizeof info);
+    if (get_info && fn) get_info(&info);
+    if (!get_info || !fn || info.abi != OGK_ABI || info.n != p->n || info.m != p->m || info.m_eq != p->m_eq ||
+        info.n_eval_blocks != p->n_eval_blocks) {
+        dlclose(mod);
+        return fail(5, who + ": the " + what + " does not belong to the handle's module");
+    }
+    *handle = mod;
+    *launch = fn;
+    return 0;
+}
+
+// The host-pointer entry points of a batch.  X (and H) of `c` lanes go up through the pinned buffer: the device arrays
+// are [capacity][n] each, so [X | H] is one copy when the batch is full and two otherwise
+int batch_upload(og_batch_s* b, size_t c, const double* X, const double* H) {
+    const size_t n = (size_t)b->p->n, cap = (size_t)b->capacity;
+    hipStream_t s = b->p->stream;
+    memcpy(b->h_up, X, sizeof(double) * c * n);
+    if (H) memcpy(b->h_up + cap * n, H, sizeof(double) * c * n);
+    if (H && c == cap) {
+        OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * 2 * cap * n, hipMemcpyHostToDevice, s));
+        return 0;
+    }
+    OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, s));
+    if (H) OG_HIP(hipMemcpyAsync(b->d_xh + cap * n, b->h_up + cap * n, sizeof(double) * c * n, hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+// F0 and vals in page-locked memory the device can address (og_pinned_alloc, hipHostRegister): the launch writes them
+// over PCIe as it goes -> true and their device addresses; else false and the batch's own device arrays
+bool batch_targets(og_batch_s* b, double* F0, double* vals, double** d_f, double** d_vals) {
+    void *m_f = nullptr, *m_vals = nullptr;
+    const bool mapped = hipHostGetDevicePointer(&m_f, F0, 0) == hipSuccess &&
+                        hipHostGetDevicePointer(&m_vals, vals, 0) == hipSuccess && m_f && m_vals;
+    if (!mapped) (void)hipGetLastError();
+    *d_f = mapped ? (double*)m_f : b->d_f;
+    *d_vals = mapped ? (double*)m_vals : b->d_vals;
+    return mapped;
+}
+
+// The results of `c` lanes to the caller: the lanes' flag blocks for the counts of non-finite rows and, unless the
+// launch wrote F0 and vals in place, the two arrays through the pinned buffer
+int batch_results(og_batch_s* b, size_t c, bool in_place, double* F0, double* vals, int32_t* nonfinite) {
+    const size_t m = (size_t)b->p->m, cap = (size_t)b->capacity, nnz = (size_t)b->nnz;
+    hipStream_t s = b->p->stream;
+    if (!in_place) {
+        if (nnz) OG_HIP(hipMemcpyAsync(b->h_down, b->d_vals, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, s));
+        OG_HIP(hipMemcpyAsync(b->h_down + cap * nnz, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, s));
+    }
+    OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * OGK_FLAG_WORDS * c, hipMemcpyDeviceToHost, s));
+    OG_HIP(hipStreamSynchronize(s));
+    if (!in_place) {
+        if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
+        memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
+    }
+    if (nonfinite)
+        for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[OGK_FLAG_WORDS * k + (size_t)b->nf_word[k]];
     return 0;
 }
 
@@ -1421,24 +1533,9 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
     if (!p || !out) return fail(1, "og_batch_create: null argument");
     if (capacity < 1 || capacity > 65535) return fail(1, "og_batch_create: capacity must be in [1, 65535]");
     OG_HIP(hipSetDevice(p->device));
-    if (!p->batch_launch) {
-        if (!batch_part_path) return fail(4, "og_batch_create: the module's batch part is not loaded and no path was given");
-        void* mod = dlopen(batch_part_path, RTLD_NOW | RTLD_LOCAL);
-        if (!mod) return fail(4, std::string("og_batch_create: dlopen of the batch part failed: ") + dlerror());
-        ogk_get_info_fn get_info = (ogk_get_info_fn)dlsym(mod, "ogk_get_info");
-        ogk_launch_batch_fn fn = (ogk_launch_batch_fn)dlsym(mod, "ogk_launch_batch");
-        ogk_info info;
-        memset(&info, 0, sizeof info);
-        if (get_info && fn) get_info(&info);
-        if (!get_info || !fn || info.abi != OGK_ABI || info.n != p->n || info.m != p->m || info.m_eq != p->m_eq ||
-            info.n_eval_blocks != p->n_eval_blocks) {
-            dlclose(mod);
-            return fail(5, "og_batch_create: the batch part does not belong to the handle's module");
-        }
-        p->batch_module = mod;
-        p->batch_launch = fn;
-    }
-    int rc = ensure_pattern(p);
+    int rc = p->batch_launch ? 0 : load_module_part(p, batch_part_path, "og_batch_create", "batch part",
+                                                    &p->batch_module, &p->batch_launch);
+    if (!rc) rc = ensure_pattern(p);
     if (rc) return rc;
     ogk_info info;
     memset(&info, 0, sizeof info);
@@ -1450,7 +1547,7 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
     b->nnz = p->indptr[(size_t)p->n];
     b->n_y0 = (size_t)(info.n_y0 > 0 ? info.n_y0 : 1);
     b->scratch_lane = 2 * b->n_y0 + 2 * (size_t)p->m;
-    b->nf_word.assign((size_t)capacity, 4);
+    b->nf_word.assign((size_t)capacity, OGK_FLAG_FUSED_RESULT);
     {
         std::lock_guard<std::mutex> guard(g_batches_lock);
         g_batches.push_back(b);
@@ -1461,8 +1558,8 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
     hipError_t e = hipMalloc(&b->d_jt, sizeof(double) * cap * n * m);
     if (e == hipSuccess) e = hipMemsetAsync(b->d_jt, 0, sizeof(double) * cap * n * m, p->stream);
     if (e == hipSuccess) e = hipMalloc(&b->d_scratch, sizeof(double) * cap * b->scratch_lane);
-    if (e == hipSuccess) e = hipMalloc(&b->d_flags, sizeof(int) * 8 * cap);
-    if (e == hipSuccess) e = hipMemsetAsync(b->d_flags, 0, sizeof(int) * 8 * cap, p->stream);
+    if (e == hipSuccess) e = hipMalloc(&b->d_flags, sizeof(int) * OGK_FLAG_WORDS * cap);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_flags, 0, sizeof(int) * OGK_FLAG_WORDS * cap, p->stream);
     if (e == hipSuccess) e = hipMalloc(&b->d_state, sizeof(uint32_t) * 2 * cap);
     if (e == hipSuccess) e = hipMalloc(&b->d_table, sizeof(ogk_args) * OGK_BATCH_SETS * cap);
     if (e == hipSuccess) e = hipMalloc(&b->d_xh, sizeof(double) * 2 * cap * n);
@@ -1470,7 +1567,7 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
     if (e == hipSuccess) e = hipMalloc(&b->d_vals, sizeof(double) * cap * nnz);
     if (e == hipSuccess) e = hipHostMalloc(&b->h_up, sizeof(double) * 2 * cap * n, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc(&b->h_down, sizeof(double) * cap * (nnz + m), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&b->h_flags, sizeof(int) * 8 * cap, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc(&b->h_flags, sizeof(int) * OGK_FLAG_WORDS * cap, hipHostMallocDefault);
     if (e == hipSuccess) {
         // per lane {state: no NaN fill, launches so far: 0}
         std::vector<uint32_t> st(2 * cap);
@@ -1484,7 +1581,7 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
                 ogk_args& a = b->table[(size_t)set * cap + k];
                 fill_args(p, &a, nullptr, nullptr, nullptr, nullptr, 0, p->n);
                 double* scr = b->d_scratch + k * b->scratch_lane;
-                int* fl = b->d_flags + 8 * k;
+                int* fl = b->d_flags + OGK_FLAG_WORDS * k;
                 a.y0 = scr;
                 a.xop = scr + b->n_y0;
                 a.t0 = scr + 2 * b->n_y0;
@@ -1494,17 +1591,17 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
                 a.jt_sparse = 1;
                 a.jt_state = b->d_state + 2 * k;
                 a.jt_launches = a.jt_state + 1;
-                a.ready = reinterpret_cast<unsigned*>(fl + 2);
-                a.nonfinite_result = fl + 4;
+                a.ready = reinterpret_cast<unsigned*>(fl + OGK_FLAG_TICKET);
+                a.nonfinite_result = fl + OGK_FLAG_FUSED_RESULT;
                 a.poff = p->d_indptr;
                 if (set == 0) {
-                    a.nonfinite = fl + 3;
-                    a.nonfinite_next = fl + 3;
+                    a.nonfinite = fl + OGK_FLAG_FUSED_COUNT;
+                    a.nonfinite_next = fl + OGK_FLAG_FUSED_COUNT;
                 } else {
-                    // an evaluation counts into word 0, which the bind launch ahead of it zeroes for the lanes that run;
-                    // the kernel's own "clear the other counter" goes to a word nobody reads
-                    a.nonfinite = fl;
-                    a.nonfinite_next = fl + 1;
+                    // an evaluation counts into the first counter, which the bind launch ahead of it zeroes for the lanes
+                    // that run; the kernel's own "clear the other counter" goes to a word nobody reads
+                    a.nonfinite = fl + OGK_FLAG_COUNT_A;
+                    a.nonfinite_next = fl + OGK_FLAG_COUNT_B;
                     a.jt_bump = set - 1;
                 }
             }
@@ -1529,15 +1626,8 @@ int og_batch_eval_dev(og_batch b, int32_t count, const double* d_X, double* d_F,
     hipStream_t s = (hipStream_t)hip_stream;
     rc = batch_bind(b, count, d_X, nullptr, d_F, nullptr, 1, s, "og_batch_eval_dev");
     if (rc) return rc;
-    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
-    ogk_batch_args ba;
-    memset(&ba, 0, sizeof ba);
-    ba.lanes = batch_set(b, 1);
-    ba.count = count;
-    ba.capacity = b->capacity;
-    rc = b->p->batch_launch(&ba, 12, s);
-    if (rc) return launch_failed(b->p, rc, "og_batch_eval_dev");
-    return 0;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    return launched(rc, "og_batch_eval_dev");
 }
 
 int og_batch_fd_sweep_dev(og_batch b, int32_t count, const double* d_X, const double* d_H, double* d_F0,
@@ -1547,42 +1637,18 @@ int og_batch_fd_sweep_dev(og_batch b, int32_t count, const double* d_X, const do
     if (!d_X || !d_H || !d_F0) return fail(1, "og_batch_fd_sweep_dev: null argument");
     og_problem_s* p = b->p;
     hipStream_t s = (hipStream_t)hip_stream;
-    const bool one_launch = p->sweep_mode == 5 && p->fused_ok;
-    rc = batch_bind(b, count, d_X, d_H, d_F0, d_vals, one_launch ? -1 : 2, s, "og_batch_fd_sweep_dev");
+    rc = batch_bind(b, count, d_X, d_H, d_F0, d_vals, one_launch(p) ? -1 : 2, s, "og_batch_fd_sweep_dev");
     if (rc) return rc;
-    ogk_batch_args ba;
-    memset(&ba, 0, sizeof ba);
-    ba.count = count;
-    ba.capacity = b->capacity;
-    if (one_launch) {
+    if (one_launch(p)) {
         // ONE launch for all lanes; its arguments are the table and the lane count
-        ba.lanes = batch_set(b, 0);
-        for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 4;
-        rc = p->batch_launch(&ba, 11, s);
-        if (rc) return launch_failed(p, rc, "og_batch_fd_sweep_dev");
-        return 0;
+        rc = batch_run(b, 0, OGK_BATCH_FUSED, count, s);
+    } else {
+        // the validation forms (OGPSX_SWEEP=split | dense, or a module whose one-launch form does not fit): one batched
+        // evaluation, then the handle's own sweep kernel lane by lane
+        rc = batch_run(b, 2, OGK_BATCH_EVAL, count, s);
+        if (!rc) rc = batch_lanes_run(b, count, columns_mode(p), d_X, d_H, d_F0, d_vals, s);
     }
-    // the validation forms (OGPSX_SWEEP=split | dense, or a module whose one-launch form does not fit): one batched
-    // evaluation, then the handle's own sweep kernel lane by lane
-    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
-    const int set = 2;
-    ba.lanes = batch_set(b, set);
-    rc = p->batch_launch(&ba, 12, s);
-    for (int k = 0; !rc && k < count; ++k) {
-        ogk_args a = b->table[(size_t)set * (size_t)b->capacity + (size_t)k];
-        a.x0 = d_X + (size_t)k * (size_t)p->n;
-        a.h = d_H + (size_t)k * (size_t)p->n;
-        a.f0 = d_F0 + (size_t)k * (size_t)p->m;
-        rc = p->launch(&a, p->sweep_mode == 5 ? 1 : p->sweep_mode, s);
-        if (!rc && d_vals) {
-            a.pind = p->d_indptr;
-            a.prow = p->d_rows;
-            a.pvals = d_vals + (size_t)k * (size_t)b->nnz;
-            rc = p->launch(&a, 8, s);
-        }
-    }
-    if (rc) return launch_failed(p, rc, "og_batch_fd_sweep_dev");
-    return 0;
+    return launched(rc, "og_batch_fd_sweep_dev");
 }
 
 int og_batch_lane_dev(og_batch b, int32_t lane, double** d_JT, int32_t* nonfinite_rows) {
@@ -1593,7 +1659,7 @@ int og_batch_lane_dev(og_batch b, int32_t lane, double** d_JT, int32_t* nonfinit
     if (nonfinite_rows) {
         // stream-ordered after the batch's most recent launch: waits for that stream, not for the whole device
         OG_HIP(hipSetDevice(b->p->device));
-        OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags + 8 * (size_t)lane + b->nf_word[(size_t)lane], sizeof(int),
+        OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags + OGK_FLAG_WORDS * (size_t)lane + b->nf_word[(size_t)lane], sizeof(int),
                               hipMemcpyDeviceToHost, b->last_stream));
         OG_HIP(hipStreamSynchronize(b->last_stream));
         *nonfinite_rows = b->h_flags[0];
@@ -1607,10 +1673,9 @@ int og_batch_eval(og_batch b, int32_t count, const double* X, double* F) {
     if (!X || !F) return fail(1, "og_batch_eval: null argument");
     og_problem_s* p = b->p;
     OG_HIP(hipSetDevice(p->device));
-    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count;
-    memcpy(b->h_up, X, sizeof(double) * c * n);
-    OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
-    rc = og_batch_eval_dev(b, count, b->d_xh, b->d_f, p->stream);
+    const size_t m = (size_t)p->m, c = (size_t)count;
+    rc = batch_upload(b, c, X, nullptr);
+    if (!rc) rc = og_batch_eval_dev(b, count, b->d_xh, b->d_f, p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(b->h_down, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
@@ -1625,45 +1690,12 @@ int og_batch_fd_sweep(og_batch b, int32_t count, const double* X, const double* 
     if (!X || !H || !F0 || !vals) return fail(1, "og_batch_fd_sweep: null argument");
     og_problem_s* p = b->p;
     OG_HIP(hipSetDevice(p->device));
-    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
-    const size_t nnz = (size_t)b->nnz;
-    // [X | H] up in one copy when the batch is full, in two otherwise (the device arrays are [capacity][n] each)
-    memcpy(b->h_up, X, sizeof(double) * c * n);
-    memcpy(b->h_up + cap * n, H, sizeof(double) * c * n);
-    if (c == cap) {
-        OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * 2 * cap * n, hipMemcpyHostToDevice, p->stream));
-    } else {
-        OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
-        OG_HIP(hipMemcpyAsync(b->d_xh + cap * n, b->h_up + cap * n, sizeof(double) * c * n, hipMemcpyHostToDevice,
-                              p->stream));
-    }
-    // F0 and vals in page-locked memory the device can address (og_pinned_alloc, hipHostRegister): the launch writes
-    // them over PCIe as it goes, and only the lanes' counts of non-finite rows are left to fetch
-    void *m_f = nullptr, *m_vals = nullptr;
-    if (hipHostGetDevicePointer(&m_f, F0, 0) != hipSuccess || hipHostGetDevicePointer(&m_vals, vals, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        m_f = m_vals = nullptr;
-    }
-    if (m_f && m_vals) {
-        rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + cap * n, (double*)m_f, (double*)m_vals, p->stream);
-        if (rc) return rc;
-        OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
-        OG_HIP(hipStreamSynchronize(p->stream));
-        if (nonfinite)
-            for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
-        return 0;
-    }
-    rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + cap * n, b->d_f, b->d_vals, p->stream);
+    double *d_f, *d_vals;
+    const bool in_place = batch_targets(b, F0, vals, &d_f, &d_vals);
+    rc = batch_upload(b, (size_t)count, X, H);
+    if (!rc) rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + (size_t)b->capacity * (size_t)p->n, d_f, d_vals, p->stream);
     if (rc) return rc;
-    if (nnz) OG_HIP(hipMemcpyAsync(b->h_down, b->d_vals, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, p->stream));
-    OG_HIP(hipMemcpyAsync(b->h_down + cap * nnz, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
-    OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
-    OG_HIP(hipStreamSynchronize(p->stream));
-    if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
-    memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
-    if (nonfinite)
-        for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
-    return 0;
+    return batch_results(b, (size_t)count, in_place, F0, vals, nonfinite);
 }
 
 // ---- the exact Jacobian of a batch (include/ogpsx.h) ----
@@ -1672,23 +1704,8 @@ int og_jacobian_exact_batch_load(og_batch b, const char* exact_part_path) {
     if (!live_batch(b)) return fail(1, "og_jacobian_exact_batch_load: the batch or its handle has been destroyed");
     og_problem_s* p = b->p;
     if (p->batch_exact_launch) return 0;
-    if (!exact_part_path)
-        return fail(4, "og_jacobian_exact_batch_load: the module's exact batch part is not loaded and no path was given");
-    void* mod = dlopen(exact_part_path, RTLD_NOW | RTLD_LOCAL);
-    if (!mod) return fail(4, std::string("og_jacobian_exact_batch_load: dlopen of the exact batch part failed: ") + dlerror());
-    ogk_get_info_fn get_info = (ogk_get_info_fn)dlsym(mod, "ogk_get_info");
-    ogk_launch_batch_fn fn = (ogk_launch_batch_fn)dlsym(mod, "ogk_launch_batch");
-    ogk_info info;
-    memset(&info, 0, sizeof info);
-    if (get_info && fn) get_info(&info);
-    if (!get_info || !fn || info.abi != OGK_ABI || info.n != p->n || info.m != p->m || info.m_eq != p->m_eq ||
-        info.n_eval_blocks != p->n_eval_blocks) {
-        dlclose(mod);
-        return fail(5, "og_jacobian_exact_batch_load: the exact batch part does not belong to the handle's module");
-    }
-    p->batch_exact_module = mod;
-    p->batch_exact_launch = fn;
-    return 0;
+    return load_module_part(p, exact_part_path, "og_jacobian_exact_batch_load", "exact batch part", &p->batch_exact_module,
+                            &p->batch_exact_launch);
 }
 
 int og_jacobian_exact_batch_dev(og_batch b, int32_t count, const double* d_X, double* d_F0, double* d_vals,
@@ -1697,39 +1714,21 @@ int og_jacobian_exact_batch_dev(og_batch b, int32_t count, const double* d_X, do
     if (rc) return rc;
     if (!d_X || !d_F0) return fail(1, "og_jacobian_exact_batch_dev: null argument");
     og_problem_s* p = b->p;
-    const bool dense = p->exact_mode == 3;
+    const bool dense = p->exact_mode == OGK_EXACT_DENSE;
     if (!dense && !p->batch_exact_launch)
         return fail(4, "og_jacobian_exact_batch_dev: the module's exact batch part is not loaded "
                        "(og_jacobian_exact_batch_load)");
     hipStream_t s = (hipStream_t)hip_stream;
     // record set 2: the evaluation counts one launch into every lane's *jt_launches, as the evaluation of
     // og_jacobian_exact_dev does for a registered buffer
-    const int set = 2;
-    rc = batch_bind(b, count, d_X, nullptr, d_F0, d_vals, set, s, "og_jacobian_exact_batch_dev");
+    rc = batch_bind(b, count, d_X, nullptr, d_F0, d_vals, 2, s, "og_jacobian_exact_batch_dev");
     if (rc) return rc;
-    for (int k = 0; k < count; ++k) b->nf_word[(size_t)k] = 0;
-    ogk_batch_args ba;
-    memset(&ba, 0, sizeof ba);
-    ba.lanes = batch_set(b, set);
-    ba.count = count;
-    ba.capacity = b->capacity;
-    rc = p->batch_launch(&ba, 12, s);               // F(X[k]) and the base collocation products of every lane
-    if (!rc && !dense) rc = p->batch_exact_launch(&ba, 14, s);      // every lane's derivatives and packed values
-    // the validation form (OGPSX_SWEEP=dense): the handle's dense exact kernel and the pack, lane by lane
-    for (int k = 0; dense && !rc && k < count; ++k) {
-        ogk_args a = b->table[(size_t)set * (size_t)b->capacity + (size_t)k];
-        a.x0 = d_X + (size_t)k * (size_t)p->n;
-        a.f0 = d_F0 + (size_t)k * (size_t)p->m;
-        rc = p->launch(&a, 3, s);
-        if (!rc && d_vals) {
-            a.pind = p->d_indptr;
-            a.prow = p->d_rows;
-            a.pvals = d_vals + (size_t)k * (size_t)b->nnz;
-            rc = p->launch(&a, 8, s);
-        }
-    }
-    if (rc) return launch_failed(p, rc, "og_jacobian_exact_batch_dev");
-    return 0;
+    rc = batch_run(b, 2, OGK_BATCH_EVAL, count, s);     // F(X[k]) and the base collocation products of every lane
+    // every lane's derivatives and packed values; or the validation form (OGPSX_SWEEP=dense): the handle's dense exact
+    // kernel and the pack, lane by lane
+    if (!rc) rc = dense ? batch_lanes_run(b, count, OGK_EXACT_DENSE, d_X, nullptr, d_F0, d_vals, s)
+                        : batch_run(b, 2, OGK_BATCH_EXACT, count, s);
+    return launched(rc, "og_jacobian_exact_batch_dev");
 }
 
 int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* F0, double* vals,
@@ -1739,33 +1738,13 @@ int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* 
     if (!X || !F0 || !vals) return fail(1, "og_jacobian_exact_batch: null argument");
     og_problem_s* p = b->p;
     OG_HIP(hipSetDevice(p->device));
-    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
-    const size_t nnz = (size_t)b->nnz;
-    memcpy(b->h_up, X, sizeof(double) * c * n);
-    OG_HIP(hipMemcpyAsync(b->d_xh, b->h_up, sizeof(double) * c * n, hipMemcpyHostToDevice, p->stream));
-    // F0 and vals in page-locked memory the device can address: written in place, as og_batch_fd_sweep does
-    void *m_f = nullptr, *m_vals = nullptr;
-    if (hipHostGetDevicePointer(&m_f, F0, 0) != hipSuccess || hipHostGetDevicePointer(&m_vals, vals, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        m_f = m_vals = nullptr;
-    }
-    const bool in_place = m_f && m_vals;
-    rc = og_jacobian_exact_batch_dev(b, count, b->d_xh, in_place ? (double*)m_f : b->d_f,
-                                     in_place ? (double*)m_vals : b->d_vals, p->stream);
+    // F0 and vals in memory the device can address are written in place, as og_batch_fd_sweep does
+    double *d_f, *d_vals;
+    const bool in_place = batch_targets(b, F0, vals, &d_f, &d_vals);
+    rc = batch_upload(b, (size_t)count, X, nullptr);
+    if (!rc) rc = og_jacobian_exact_batch_dev(b, count, b->d_xh, d_f, d_vals, p->stream);
     if (rc) return rc;
-    if (!in_place) {
-        if (nnz) OG_HIP(hipMemcpyAsync(b->h_down, b->d_vals, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, p->stream));
-        OG_HIP(hipMemcpyAsync(b->h_down + cap * nnz, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
-    }
-    OG_HIP(hipMemcpyAsync(b->h_flags, b->d_flags, sizeof(int) * 8 * c, hipMemcpyDeviceToHost, p->stream));
-    OG_HIP(hipStreamSynchronize(p->stream));
-    if (!in_place) {
-        if (nnz) memcpy(vals, b->h_down, sizeof(double) * c * nnz);
-        memcpy(F0, b->h_down + cap * nnz, sizeof(double) * c * m);
-    }
-    if (nonfinite)
-        for (size_t k = 0; k < c; ++k) nonfinite[k] = b->h_flags[8 * k + (size_t)b->nf_word[k]];
-    return 0;
+    return batch_results(b, (size_t)count, in_place, F0, vals, nonfinite);
 }
 
 }  // extern "C"

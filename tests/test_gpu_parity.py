@@ -434,6 +434,50 @@ def test_registered_host_matrix_receives_the_packed_nonzeros(name, state):
     eng.close()
 
 
+def test_host_matrix_trial_hands_over_to_the_chosen_form(monkeypatch):
+    """og_fd_sweep into a registered host matrix times both of its forms before it settles: calls 0-4 write the mapped
+    matrix, calls 5-9 take the packed one-launch form, the faster one serves from call 10 on.  Thirteen calls cross both
+    hand-overs with a non-finite point in each stretch (calls 2, 5, 8, 11); every call gives the matrix of the dense
+    transfer, and an exact Jacobian into the same matrix follows.  A runtime that maps no host memory serves every call
+    staged, with the same results."""
+    from opengoddard_amd.engine import HipEngine
+    from oracle import np_path
+    monkeypatch.delenv("OGPSX_HOST", raising=False)
+    prob, obj = problems.build("goddard")
+    lb, ub = np_path.bounds_arrays(prob)
+    eng = HipEngine(prob, obj)
+    x_ok = np.clip(prob.p, lb, ub)
+    x_bad = x_ok.copy()
+    x_bad[prob.index_states(2, 0, 7)] = 0.0
+    rng = np.random.default_rng(9)
+    x_other = np.clip(x_ok + 1e-3 * rng.standard_normal(eng.n), lb, ub)
+    paths = []                                          # the form call i takes: host_path as call i finds it
+    for call in range(13):
+        x = (x_ok, x_other, x_bad)[call % 3]
+        h = _native.fd_step(x, lb, ub)
+        F_want, JT_want = eng.sweep_stacked(x, h)
+        assert np.isfinite(F_want).all() == (x is not x_bad)
+        if call:
+            paths.append(eng.host_path)
+        F_got, JT_got = eng.sweep_persistent(x, h)
+        if not call:
+            paths.append(eng.host_path)                 # (no matrix before the first call; one call decides nothing)
+        assert JT_got is eng._JT_host
+        assert np.array_equal(F_got, F_want, equal_nan=True), "F at call %d" % call
+        assert np.array_equal(JT_got, JT_want, equal_nan=True), "J_T at call %d" % call
+    paths.append(eng.host_path)
+    if paths[0] == "staged":                            # no pinned, mapped matrix on this runtime: no trial
+        assert paths == ["staged"] * 14
+    else:
+        assert paths[:10] == ["undecided"] * 10
+        assert paths[10] in ("mapped", "staged") and paths[10:] == [paths[10]] * 4
+    Fe, JTe = eng.exact_stacked(x_other)
+    Fp, JTp = eng.sweep_persistent(x_other, _native.fd_step(x_other, lb, ub), exact=True)
+    assert JTp is eng._JT_host
+    assert np.array_equal(Fp, Fe) and np.array_equal(JTp, JTe)
+    eng.close()
+
+
 @pytest.mark.parametrize("gather,devices", [("peer", [0, 0]), ("peer", [0, 0, 0]), ("peer", [0] * 8), ("rccl", [0])])
 @pytest.mark.parametrize("name,state", [("goddard", 2), ("polar_tsto", 4)])
 def test_multi_device_handle_reassembles_the_jacobian(name, state, gather, devices, monkeypatch):
