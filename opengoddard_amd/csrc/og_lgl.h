@@ -35,6 +35,34 @@ OG_HD double legendre(int n, double x) {
     return a;
 }
 
+// P_{N-1} at a node of the N-point rule, for the weights and D.  Two forms of one recurrence:
+//   Bonnet's, above, up to DIFFERENCE_FORM_ABOVE nodes;
+//   beyond, in the differences d_j = P_j - P_{j-1} and s = |x| - 1:
+//       (j+1) d_{j+1} = (2j+1) s P_j + j d_j,   P_{j+1} = P_j + d_{j+1}.
+// Next to the ends (1 - |x| ~ 1e-5 at N = 632) Bonnet's (2j+1) x P_j - j P_{j-1} cancels two nearly equal numbers at
+// every step, and the loss grows with N: the weights there are <= 2.0e-13 off up to N = 341 (the reference's own
+// construction: <= 1.4e-13), 1.3e-12 at N = 632 (4 times the reference's), 1.5e-12 at 1187.  The difference form has no
+// such cancellation: <= 1.5e-14 up to N = 1188 (tests/test_lgl_and_layout.py, profiles/exact_surface.md).
+// Why not the difference form everywhere: it moves the last bits of w and D, and every iterate of a solve with them.
+// Up to 341 nodes per phase those bits are pinned - by the reference's goldens (tests/golden/lgl.npz, N <= 200), by the
+// shipped configurations, and by the recorded first iterations of launch4 on 208 and on 341 nodes per phase
+// (tests/test_gpu_solve.py; 4 x 341 is the longest equal-phase form of that problem the SQP core takes) - and Bonnet's
+// form is within the bound there.  Above, nothing is pinned but device == host == twin, which holds in either form.
+// Parity: P_n(-x) = (-1)^n P_n(x), exact in floating point, so the rule stays symmetric to the bit.
+constexpr int DIFFERENCE_FORM_ABOVE = 341;
+
+OG_HD double legendre_at_node(int N, double x) {
+    const int n = N - 1;
+    if (N <= DIFFERENCE_FORM_ABOVE) return legendre(n, x);
+    const double s = ogm::fabs_(x) - 1.0;
+    double p = 1.0 + s, d = s;                 // P_1 = |x|, d_1 = P_1 - P_0
+    for (int j = 1; j < n; ++j) {
+        d = ((double)(2 * j + 1) * s * p + (double)j * d) / (double)(j + 1);
+        p = p + d;
+    }
+    return (x < 0.0 && (n & 1)) ? -p : p;
+}
+
 // k-th LGL node of an N-point rule (0 <= k < N), ascending.  Antisymmetric by construction:
 // node(N-1-k) == -node(k) bit for bit, centre node of an odd rule == 0.
 OG_HD double node(int N, int k) {

@@ -44,7 +44,7 @@ __global__ void lgl_nodes_kernel(int N, double* tau, double* w, double* pval) {
     const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (k >= N) return;
     const double t = oglgl::node(N, k);
-    const double p = oglgl::legendre(N - 1, t);
+    const double p = oglgl::legendre_at_node(N, t);
     tau[k] = t;
     pval[k] = p;
     w[k] = oglgl::weight(N, p);
@@ -612,7 +612,7 @@ int og_lgl(int32_t N, double* tau, double* w, double* D) {
     std::vector<double> p(N);
     for (int k = 0; k < N; ++k) tau[k] = oglgl::node(N, k);
     for (int k = 0; k < N; ++k) {
-        p[k] = oglgl::legendre(N - 1, tau[k]);
+        p[k] = oglgl::legendre_at_node(N, tau[k]);
         w[k] = oglgl::weight(N, p[k]);
     }
     for (int k = 0; k < N; ++k)

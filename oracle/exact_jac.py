@@ -17,6 +17,7 @@ import numpy as np
 from . import program_eval
 
 EPS = 1e-30
+CHUNK = 256          # columns evaluated together
 
 
 def _re(v):
@@ -64,9 +65,24 @@ def _mod(a, b, which):
 
 
 class _ComplexEval(program_eval._Eval):
+    """``x`` is ``[n, C]``: C perturbed copies of the point, one per column of the Jacobian, evaluated together.  A
+    vector element is ``[length, C]``, a scalar one ``[C]``; every operation is elementwise, so column c is exactly the
+    evaluation of ``x[:, c]`` alone."""
+
     def __init__(self, P, x, D):
-        super().__init__(P, np.real(x), D)
+        super().__init__(P, np.real(x[:, 0]), D)
         self.x = np.asarray(x, dtype=complex)
+        self.C = self.x.shape[1]
+
+    def mv(self, slot):
+        # D is real: two real products (the real part is then the real interpreter's own, and a complex product with a
+        # matrix converted on every call costs many times as much)
+        if slot not in self.yvec:
+            s = self.P.mv[slot]
+            operand = np.broadcast_to(self.elem(s.operand, s.length, {}), (s.length, self.C))
+            D = self.D[s.phase]
+            self.yvec[slot] = D.dot(np.real(operand)) + 1j * D.dot(np.imag(operand))
+        return self.yvec[slot]
 
     def elem(self, eid, length, memo):
         hit = memo.get(eid)
@@ -80,6 +96,8 @@ class _ComplexEval(program_eval._Eval):
         elif tag == "Y":
             y = self.mv(node[1])
             out = y[node[2] + node[3] * k] if node[3] else y[node[2]]
+        elif tag == "CV" and node[3]:       # a constant vector: along the element axis
+            out = self.P.cvec[self.P.cvec_off[node[1]] + node[2] + node[3] * k][:, None]
         elif tag == "un" and node[1] == "abs":
             out = _abs(self.elem(node[2], length, memo))
         elif tag == "un" and node[1] == "cbrt":
@@ -114,7 +132,7 @@ class _ComplexEval(program_eval._Eval):
         elif tag == "sum":
             total = 0j
             for ln, body in node[1]:
-                vec = np.broadcast_to(self.elem(body, ln, {}), (ln,))
+                vec = np.broadcast_to(self.elem(body, ln, {}), (ln, self.C))
                 for v in vec:
                     total = total + v
             out = total
@@ -128,13 +146,15 @@ def jacobian(program, prob, x, columns=None):
     """``JT[r, :] = dF/dx_columns[r]`` (F = [cost | c_eq | c_ineq]) by complex-step differentiation."""
     x = np.asarray(x, dtype=float)
     columns = range(x.size) if columns is None else columns
+    columns = [int(j) for j in columns]
     JT = np.empty((len(columns), program.m))
-    for r, j in enumerate(columns):
-        z = x.astype(complex)
-        z[j] += 1j * EPS
+    for r0 in range(0, len(columns), CHUNK):
+        chunk = columns[r0:r0 + CHUNK]
+        z = np.repeat(x.astype(complex)[:, None], len(chunk), axis=1)
+        z[chunk, np.arange(len(chunk))] += 1j * EPS
         ev = _ComplexEval(program, z, prob.D)
-        F = np.full(program.m, np.nan, dtype=complex)
+        F = np.full((program.m, len(chunk)), np.nan, dtype=complex)
         for row, ln, eid, _kind in program.pieces:
             F[row:row + ln] = ev.elem(eid, ln, {})
-        JT[r] = np.imag(F) / EPS
+        JT[r0:r0 + len(chunk)] = np.imag(F).T / EPS
     return JT

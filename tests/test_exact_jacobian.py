@@ -149,6 +149,11 @@ def test_gpu_exact_jacobian_against_complex_step_at_baseline_sizes(name, count):
     mask = np.zeros(JE.shape, dtype=bool)
     mask[np.repeat(np.arange(n), np.diff(indptr)), rows] = True
     assert not np.any(JE[~mask])
+    # (the structured kernel writes pattern entries only, so the line above holds by construction: what can fail is
+    # the pattern itself - the complex step, which knows nothing of it, has no non-zero outside it on its columns)
+    outside = np.argwhere((JC != 0) & ~mask[cols])
+    assert outside.size == 0, "F[%d] depends on x[%d], which og_pattern leaves out" % (
+        outside[0][1] if outside.size else -1, cols[outside[0][0]] if outside.size else -1)
     eng.close()
 
 

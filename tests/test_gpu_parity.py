@@ -713,7 +713,9 @@ def test_lgl_kernel_matches_host_bitwise():
     import torch
     lib = _native.lib()
     dev = torch.device("cuda", 0)
-    for n in (3, 4, 5, 20, 50, 80, 128, 200):
+    # (above 200: the partial last wavefront of lgl_nodes_kernel and the (N + 63) / 64 by N grid of lgl_dmat_kernel at
+    # sizes up to the longest phase the engine accepts, and og_lgl.h's difference form of P_{N-1} from 453 on)
+    for n in (3, 4, 5, 20, 50, 80, 128, 200, 201, 257, 453, 633, 840, 1188):
         tau, w, D = _native.lgl(n)
         d_tau = torch.empty(n, dtype=torch.float64, device=dev)
         d_w = torch.empty(n, dtype=torch.float64, device=dev)
@@ -752,6 +754,26 @@ def test_lgl_kernel_against_the_reference_golden(n):
     assert np.array_equal(D == 0, ~nz)
     assert np.max(np.abs(D[nz] / rD[nz] - 1.0)) <= 1e-12
     assert D[0, 0] == -n * (n - 1) * 0.25 and D[-1, -1] == n * (n - 1) * 0.25
+
+
+@pytest.mark.parametrize("n", (453, 1188))
+def test_lgl_kernel_against_the_true_rule(n):
+    """``tests/test_lgl_and_layout.test_lgl_against_the_true_rule`` on the DEVICE kernels' output (``og_lgl_dev``), beyond
+    the reference's float64 goldens: the true rule from tests/golden/lgl_hp.npz, the reference's own recorded error as
+    the yardstick."""
+    import ctypes as C
+    import os
+    import torch
+    from test_lgl_and_layout import check_lgl_against_truth
+    G = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lgl_hp.npz"))
+    lib = _native.lib()
+    dev = torch.device("cuda", 0)
+    d_tau = torch.empty(n, dtype=torch.float64, device=dev)
+    d_w = torch.empty(n, dtype=torch.float64, device=dev)
+    d_D = torch.empty((n, n), dtype=torch.float64, device=dev)
+    _native.check(lib.og_lgl_dev(n, C.c_void_p(d_tau.data_ptr()), C.c_void_p(d_w.data_ptr()),
+                                 C.c_void_p(d_D.data_ptr()), None), "og_lgl_dev")
+    check_lgl_against_truth(n, d_tau.cpu().numpy(), d_w.cpu().numpy(), d_D.cpu().numpy(), G)
 
 
 def test_hardware_probe():

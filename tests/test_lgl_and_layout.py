@@ -1,6 +1,7 @@
 """Host logic vs the reference's goldens: LGL construction (og_lgl through the C ABI), the
 decision-vector layout / getters / index helpers with their quirks, unit scaling, Guess."""
 import json
+import math
 import os
 
 import numpy as np
@@ -11,6 +12,23 @@ from opengoddard_amd import _native
 from opengoddard_amd.optimize import Condition, Dynamics, Guess, Problem
 
 LGL_SIZES = (3, 4, 5, 10, 20, 25, 30, 40, 50, 80, 100, 128, 200)
+# above the reference's float64 goldens, up to codegen.max_phase_nodes(1): tests/golden/lgl_hp.npz (tools/make_golden_lgl_hp.py)
+LGL_HP_SIZES = (201, 255, 256, 257, 341, 452, 453, 632, 633, 840, 1187, 1188)
+
+
+def lgl_sample(n):
+    """``(rows, cols)`` of the entries of D that are compared one by one: every entry with ``|k - l| <= 3``, the first
+    and last two rows and columns, the centre row, and 2000 seeded random entries."""
+    k = np.arange(n)
+    pick = np.zeros((n, n), dtype=bool)
+    pick[np.abs(k[:, None] - k[None, :]) <= 3] = True
+    for edge in (0, 1, n - 2, n - 1):
+        pick[edge, :] = True
+        pick[:, edge] = True
+    pick[n // 2, :] = True
+    rng = np.random.default_rng(n)
+    pick[rng.integers(0, n, 2000), rng.integers(0, n, 2000)] = True
+    return np.nonzero(pick)
 
 
 @pytest.mark.parametrize("n", LGL_SIZES)
@@ -43,6 +61,117 @@ def test_lgl_known_values_and_errors():
         _native.lgl(2)
     with pytest.raises(ValueError):
         Problem([0.0, 1.0], [2], [1], [1])                      # quirk Q2
+
+
+def _hp(pair):
+    """A double-double pair as one high-precision array: ``np.longdouble`` where it has at least 64 significant bits
+    (x86-64: 64, aarch64: 113), else mpmath numbers in an object array."""
+    if np.finfo(np.longdouble).eps < 2e-19:
+        return pair[0].astype(np.longdouble) + pair[1].astype(np.longdouble)
+    import mpmath
+    return np.array([mpmath.mpf(float(a)) + mpmath.mpf(float(b)) for a, b in zip(pair[0], pair[1])], dtype=object)
+
+
+def _hp_of(values):
+    """float64 numbers in the arithmetic of ``_hp`` (exactly)."""
+    if np.finfo(np.longdouble).eps < 2e-19:
+        return np.asarray(values, dtype=np.float64).astype(np.longdouble)
+    import mpmath
+    return np.array([mpmath.mpf(float(v)) for v in np.ravel(values)], dtype=object).reshape(np.shape(values))
+
+
+def _whole(n, half, sign):
+    """The whole symmetric rule from its non-negative half (the centre node first when ``n`` is odd)."""
+    upper = half[1:] if n % 2 else half
+    centre = half[:1] if n % 2 else half[:0]
+    return np.concatenate([sign * upper[::-1], centre, upper])
+
+
+def lgl_truth(n, G):
+    """``(tau, P_{N-1}(tau))`` of the true rule in high precision, from tests/golden/lgl_hp.npz."""
+    return _whole(n, _hp(G["tau_%d" % n]), -1), _whole(n, _hp(G["p_%d" % n]), -1 if (n - 1) % 2 else 1)
+
+
+def lgl_rows(n):
+    """The whole rows of D that the ``D @ v`` checks use."""
+    return (0, 1, n // 2, n - 2, n - 1)
+
+
+def lgl_errors(n, tau, w, D, G):
+    """What ``(tau, w, D)`` is off by against the truth - worst absolute node error, worst relative weight error,
+    worst relative error of D over ``lgl_sample`` - and, for ``v = tau ** 3`` and ``v = 1`` on the rows ``lgl_rows``,
+    the worst ``|D @ v - v'|`` of this D beside the float64 sum's own bound with the true D."""
+    tt, pt = lgl_truth(n, G)
+    node = float(np.max(np.abs(_hp_of(tau) - tt)))
+    wt = 2 / (n * (n - 1) * pt * pt)
+    weight = float(np.max(np.abs(_hp_of(w) / wt - 1)))
+    rows, cols = lgl_sample(n)
+    off = rows != cols
+    rows, cols = rows[off], cols[off]
+    Dt = pt[rows] / pt[cols] / (tt[rows] - tt[cols])
+    dmat = float(np.max(np.abs(_hp_of(D[rows, cols]) / Dt - 1)))
+    eps = np.finfo(float).eps
+    out = {"node": node, "weight": weight, "D": dmat}
+    for name, v, dv in (("cubic", tau ** 3, 3 * tau ** 2), ("constant", np.ones(n), np.zeros(n))):
+        got, allowed = 0.0, 0.0
+        for r in lgl_rows(n):
+            gap = tt[r] - tt
+            gap[r] = 1
+            row = pt[r] / pt / gap
+            row[r] = D[r, r]                                        # (the diagonal is exact by construction)
+            true_row = np.array([float(x) for x in row])            # the true D rounded to float64
+            got = max(got, abs(float(D[r] @ v) - dv[r]))
+            # what a float64 dot product of N terms may be off by (n eps sum |D_rl v_l|), the true row's own residual
+            # on these float64 nodes, and the entries' allowed relative error times the same sum
+            mass = float(np.abs(true_row) @ np.abs(v))
+            allowed = max(allowed, abs(float(true_row @ v) - dv[r]) + n * eps * mass)
+            out[name + "_mass"] = max(out.get(name + "_mass", 0.0), mass)
+        out[name], out[name + "_true"] = got, allowed
+    return out
+
+
+def check_lgl_against_truth(n, tau, w, D, G, report=None):
+    """The assertions of ``test_lgl_against_the_true_rule`` on one ``(tau, w, D)``: the host's or the device's."""
+    assert tau.shape == (n,) and w.shape == (n,) and D.shape == (n, n)
+    assert np.all(np.diff(tau) > 0) and tau[0] == -1.0 and tau[-1] == 1.0
+    assert np.array_equal(tau, -tau[::-1])                                       # antisymmetric to the bit
+    k = np.arange(n)
+    assert np.array_equal(D == 0, (k[:, None] == k[None, :]) & (k[:, None] > 0) & (k[:, None] < n - 1))
+    assert D[0, 0] == -n * (n - 1) * 0.25 and D[-1, -1] == n * (n - 1) * 0.25
+    ref_node, ref_weight, ref_D = (float(v) for v in G["ref_%d" % n])
+    E = lgl_errors(n, tau, w, D, G)
+    if report is not None:
+        report(n, E, (ref_node, ref_weight, ref_D))
+    assert E["node"] <= 4 * ref_node, (n, E["node"], ref_node)
+    assert E["weight"] <= 4 * ref_weight, (n, E["weight"], ref_weight)
+    assert E["D"] <= 4 * ref_D, (n, E["D"], ref_D)
+    assert abs(math.fsum(w) - 2.0) <= n * np.spacing(2.0)                        # quadrature: within N ulp
+    for name in ("cubic", "constant"):
+        assert E[name] <= E[name + "_true"] + 4 * ref_D * E[name + "_mass"], (n, name, E)
+
+
+@pytest.fixture(scope="module")
+def lgl_hp():
+    return np.load(os.path.join(GOLDEN, "lgl_hp.npz"))
+
+
+@pytest.mark.parametrize("n", LGL_HP_SIZES)
+def test_lgl_against_the_true_rule(n, lgl_hp, capsys):
+    """Above the reference's float64 goldens, up to the longest phase the engine accepts: ``oglgl::node``'s Newton
+    iteration and ``P_{N-1}``'s recurrence against the true rule (mpmath, tests/golden/lgl_hp.npz).  Allowed: 4 times
+    what the reference's own float64 construction is off by at that N - not 1, because both constructions round the
+    same ill-conditioned quotient ``1 / (t_k - t_l)``, and which way a node's last bit falls is chance.  ``D @ tau ** 3``
+    and ``D @ 1`` on whole rows: within what the same float64 sum with the true D rounded to float64 leaves (its own
+    residual plus N eps sum |D_rl v_l|) plus the entries' allowed relative error times sum |D_rl v_l|.
+    Measured and allowed figures per N: profiles/exact_surface.md."""
+    def report(n, E, ref):
+        if os.environ.get("OG_SURFACE_REPORT"):
+            with capsys.disabled():
+                print("lgl %5d node %.2e (ref %.2e) w %.2e (ref %.2e) D %.2e (ref %.2e) cubic %.2e (true D %.2e) "
+                      "constant %.2e (true D %.2e)" % ((n, E["node"], ref[0], E["weight"], ref[1], E["D"], ref[2],
+                                                        E["cubic"], E["cubic_true"], E["constant"], E["constant_true"])))
+    tau, w, D = _native.lgl(n)
+    check_lgl_against_truth(n, tau, w, D, lgl_hp, report)
 
 
 def _load_layout():
