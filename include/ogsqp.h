@@ -120,7 +120,8 @@ int og_qp_resident_stats(og_qp_handle qp, int64_t* launches, int64_t* changes);
 
 /* Powell-damped BFGS (slsqp label 260-320) on the factor: s = step, eta = change of the
  * Lagrangian gradient, Bs = B s.  *reset_needed = 1 when the update is undefined (s'Bs or the
- * damped s'eta not positive) and the factor was left unchanged. */
+ * damped s'eta not positive, or s'eta or s'Bs not finite - looked at before the damping, which would
+ * replace s'eta = -inf by 0.2 s'Bs) and the factor was left unchanged. */
 int og_qp_bfgs(og_qp_handle qp, const double* s, const double* eta, const double* Bs,
                int32_t* reset_needed);
 

@@ -3699,13 +3699,16 @@ int og_qp_bfgs(og_qp_handle qp, const double* s, const double* eta, const double
         h1 += s[i] * eta[i];
         h2 += s[i] * Bs[i];
     }
+    // (the sums are looked at before the damping replaces h1: s'eta = -inf would come out of it as 0.2 h2, theta = 0, and
+    // r = 0 * eta + Bs would carry the NaN of 0 * inf into every column of Z)
+    const bool finite = std::isfinite(h1) && std::isfinite(h2);
     const double h3 = 0.2 * h2;
     double theta = 1.0;
     if (h1 < h3) {
         theta = (h2 - h3) / (h2 - h1);
         h1 = h3;
     }
-    if (!(h1 > 0.0 && h2 > 0.0) || !std::isfinite(h1) || !std::isfinite(h2)) {
+    if (!finite || !(h1 > 0.0 && h2 > 0.0)) {
         *reset_needed = 1;
         return 0;
     }

@@ -331,6 +331,8 @@ def bfgs_factor_update(Z, s, eta, Bs):
     Returns the new factor, or ``None`` when the update is undefined (caller resets)."""
     h1 = float(s @ eta)
     h2 = float(s @ Bs)
+    if not (np.isfinite(h1) and np.isfinite(h2)):           # (before the damping: it would turn h1 = -inf into 0.2 h2)
+        return None
     h3 = 0.2 * h2
     r = eta
     if h1 < h3:
