@@ -2364,6 +2364,86 @@ __global__ void k_rank1(double* Z, int ld, int n, const double* s, const double*
     if (k < n) Z[(long)i * ld + k] -= s[i] * (vz[k] * inv_alpha);
 }
 
+size_t gi_lds_bytes(int nr, int qcap) {
+    return (size_t)(2 * nr + 6 * qcap + 64) * sizeof(double);
+}
+
+size_t rows_lds_bytes(int nr, int qcap) {          // k_rows_decide: the incoming normal, the dual direction, a reflector
+    return (size_t)(nr + 2 * qcap + 16) * sizeof(double);
+}
+
+// What selects the launch form of every stage of a subproblem.  The handle holds the record forms_from_env() made when
+// it was created; an attempt (qp_solve_attempt) reads the record it is given and nothing else: the handle's, or
+// forms_without_waits() of it after a wait gave up.  A new form that waits for other workgroups is declared HERE.
+struct QpForms {
+    bool resident = true;      // round 6: the active-set loop as ONE launch with every row of W and of the inverse in
+                               // registers (k_rows_resident, ogsqp_resident.h) where they fit the chip - up to 3840 rows
+                               // of up to 1024 null-space coordinates: C3, C4; OGSQP_RESIDENT=0: the two-launch form
+    bool warm_spread = true;   // removals of the warm start: both products with the inverse spread over the grid of
+                               // k_rows_decide (OGSQP_WARM_SPREAD=0: by one workgroup, rounds 3-4)
+    bool lq16 = true;          // OGSQP_LQ=8: the sweep of 8-reflector panels only
+    bool lq_ahead = true;      // OGSQP_LQ=16: panel and trailing update as separate launches
+    // rows longer than one workgroup's registers (n + 1 > LQW_SLAB): column-split panels, 64-reflector blocks, GEMMs
+    bool lq_wide = false;      // (ogsqp_lqwide.h; OGSQP_LQ=8 / 16 and OGSQP_WIDE=0 turn it off)
+    bool wide_ahead = false;   // ... its block reflectors applied on two streams of their own (OGSQP_WIDE_AHEAD=0: not)
+    bool wide_inblock = false; // OGSQP_WIDE_INBLOCK=1: the later rows of a block get a panel's reflectors in ONE launch
+                               // (k_wy_inblock) instead of three (product over slices, finish, update) - same bits;
+                               // measured at C5: 7.00 instead of 7.07 s over 121 subproblems, not worth a kernel that
+                               // waits for its neighbours: off by default
+    int trsv_mode = 0;         // OGSQP_TRSV: 0 one chained launch, 1 ("block") a launch per block, 2 ("single")
+    int gi_mode = 0;           // 0 rows (k_rows_decide / k_rows_apply, the default), 1 the two older kernels
+    int rows_r4 = 0;           // rounds 3-4's register form of the pass (k_rows_apply_r4): 0 for rows of up to 512
+                               // coordinates, where it measured faster (C3: 6.8-7.0 against 8.0 us; C4's 589
+                               // coordinates: 10.9 against 9.0 us for round 5's form), 1 (OGSQP_ROWS=r4) up to 1024,
+                               // -1 (=lds) never
+    int rows_stage = 0;        // ... their second pass out of LDS instead of the caches: only when forced (1)
+    bool rows_stream = true;   // rows of more than 1024 null-space coordinates are streamed (k_rows_apply_stream);
+                               // OGSQP_ROWS=reg: the register kernels k_rows_apply<TAIL> for every length
+    bool warm_enabled = true;  // start the active-set method from the previous subproblem's active rows (OGSQP_WARM=0)
+};
+
+bool env_is(const char* name, const char* value) {
+    const char* v = getenv(name);
+    return v && std::string(v) == value;
+}
+
+// The forms of a handle for n1 = n + 1 columns and a null space of at most qcap coordinates, from the OGSQP_*
+// variables.  (OGSQP_GI also sets og_qp_s::coop_mode, OGSQP_SPIN_LIMIT the bound of the waits.)
+QpForms forms_from_env(size_t n1, int qcap) {
+    QpForms f;
+    f.resident = !env_is("OGSQP_RESIDENT", "0");
+    f.warm_spread = !env_is("OGSQP_WARM_SPREAD", "0");
+    f.lq16 = !env_is("OGSQP_LQ", "8");
+    f.lq_ahead = !env_is("OGSQP_LQ", "16");
+    // the wide sweep when the default kernels are selected (OGSQP_WIDE=0: round 2's 8-reflector kernels serve the long
+    // rows, as before round 4)
+    f.lq_wide = f.lq16 && f.lq_ahead && n1 > (size_t)LQW_SLAB && n1 <= (size_t)LQW_SLAB * LQW_MAX && !env_is("OGSQP_WIDE", "0");
+    f.wide_ahead = f.lq_wide && !env_is("OGSQP_WIDE_AHEAD", "0");
+    f.wide_inblock = f.lq_wide && env_is("OGSQP_WIDE_INBLOCK", "1");
+    f.trsv_mode = env_is("OGSQP_TRSV", "block") ? 1 : env_is("OGSQP_TRSV", "single") ? 2 : 0;
+    // the default is the row-parallel method in rotated coordinates (ogsqp_rows.h); "single" / "coop" / "old" select
+    // the two older kernels (kept for comparison; they need their own, smaller, LDS budget)
+    f.gi_mode = (env_is("OGSQP_GI", "single") || env_is("OGSQP_GI", "coop") || env_is("OGSQP_GI", "old")) &&
+                        gi_lds_bytes(qcap, qcap) <= LDS_LIMIT ? 1 : 0;
+    f.rows_r4 = env_is("OGSQP_ROWS", "r4") ? 1 : env_is("OGSQP_ROWS", "lds") ? -1 : 0;
+    f.rows_stage = env_is("OGSQP_ROWS", "stage") ? 1 : env_is("OGSQP_ROWS", "nostage") ? -1 : 0;
+    f.rows_stream = !env_is("OGSQP_ROWS", "reg");
+    f.warm_enabled = !env_is("OGSQP_WARM", "0");
+    return f;
+}
+
+// The same forms with every wait of one workgroup for another taken out: what a subproblem is solved with again after
+// a bounded wait gave up (og_qp_solve_dev).  The kernel that waits, form by form:
+QpForms forms_without_waits(QpForms f) {
+    f.resident = false;                  // k_rows_resident: every workgroup waits for every other, each change
+    f.warm_spread = false;               // k_rows_decide: between the two products of a removal of the warm start
+    f.lq_ahead = false;                  // k_lq_step16: the panel workgroup waits for the head workgroups
+    f.lq_wide = false;                   // k_lq_panel16_wide (and k_wy_inblock): the column slices wait for each other;
+                                         // round 2's kernels serve the long rows
+    if (f.trsv_mode == 0) f.trsv_mode = 1;   // k_trsv_chain: a block row waits for the one before it
+    return f;
+}
+
 }  // namespace
 
 struct og_qp_s {
@@ -2380,26 +2460,14 @@ struct og_qp_s {
     CoopPartial* cpart = nullptr;
     unsigned* bar = nullptr;
     int* abort_flag = nullptr;
-    int gi_mode = 0;                   // 0 rows (k_rows_decide / k_rows_apply, the default), 1 the two older kernels
-    int rows_r4 = 0;                   // rounds 3-4's register form of the pass (k_rows_apply_r4): 0 for rows of up to 512
-                                       // coordinates, where it measured faster (C3: 6.8-7.0 against 8.0 us; C4's 589 coordinates:
-                                       // 10.9 against 9.0 us for this round's form), 1 (OGSQP_ROWS=r4) up to 1024, -1 (=lds) never
-    int rows_stage = 0;                // ... their second pass out of LDS instead of the caches: only when forced (1)
-    bool rows_stream = true;           // rows of more than 1024 null-space coordinates are streamed (k_rows_apply_stream);
-                                       // OGSQP_ROWS=reg: the register kernels k_rows_apply<TAIL> for every length
-    bool warm_enabled = true;          // start the active-set method from the previous subproblem's active rows
-    std::vector<int> warm;             // ... in the canonical numbering of og_qp_get_active
+    QpForms forms;                     // which launch forms this handle's subproblems take (fixed by og_qp_create)
+    std::vector<int> warm;             // the previous subproblem's active rows, in the canonical numbering of og_qp_get_active
     bool warm_use = true;              // ... when the last two solutions shared most of their active rows (early in an
                                        // SQP run they do not: taking the stale rows out again costs more than it saves)
     double *dots = nullptr, *dvec = nullptr, *rvec = nullptr, *uval = nullptr;
-    bool warm_spread = true;           // removals of the warm start: both products with the inverse spread over the grid of
-                                       // k_rows_decide (OGSQP_WARM_SPREAD=0: by one workgroup, rounds 3-4)
     GiPartial *price = nullptr, *ratio = nullptr;
     RowsDecision* rec = nullptr;
-    bool resident = true;              // round 6: the active-set loop as ONE launch with every row of W and of the inverse in
-                                       // registers (k_rows_resident, ogsqp_resident.h) where they fit the chip - up to 3840
-                                       // rows of up to 1024 null-space coordinates: C3, C4; OGSQP_RESIDENT=0: the two-launch form
-    unsigned long long* res_mail = nullptr;   // its mailbox (self-validating records) ...
+    unsigned long long* res_mail = nullptr;   // the resident launch's mailbox (self-validating records) ...
     size_t res_mail_bytes = 0;
     int res_wg_alloc = 0;                     // ... sized for this many workgroups: no launch of more
     unsigned* res_seq = nullptr;              // ... and the exchange counters that go on counting from launch to launch
@@ -2415,16 +2483,12 @@ struct og_qp_s {
     double* V16b = nullptr;            // ... of the panel the look-ahead factors during the trailing update
     Lq16Panel* panel16b = nullptr;
     // rows longer than one workgroup's registers (n + 1 > 2048): column-split panels, 64-reflector blocks, GEMMs (ogsqp_lqwide.h)
-    bool lq_wide = false;              // (on from og_qp_create when n + 1 > LQW_SLAB; OGSQP_LQ=8 / 16 and OGSQP_WIDE=0 turn it off)
     double* Vall = nullptr;            // reflector vectors of the whole sweep, row k = reflector k (zero left of its panel)
     Lq16Panel* panelw = nullptr;       // T of the panel being applied inside a block
     LqWideMail* wide_mail = nullptr;
     unsigned* wide_count = nullptr;    // monotone count of the panel workgroups' steps, ever
     unsigned wide_token = 0u;
-    bool wide_inblock = false;         // OGSQP_WIDE_INBLOCK=1: the later rows of a block get a panel's reflectors in ONE
-    unsigned wide_in_token = 0u;       // launch (k_wy_inblock) instead of three (product over slices, finish, update) - same
-                                       // bits; measured at C5: 7.00 instead of 7.07 s over 121 subproblems, not worth a
-                                       // kernel that waits for its neighbours: off by default
+    unsigned wide_in_token = 0u;       // (k_wy_inblock's exchange count)
     double* wy_part = nullptr;         // column slices of a product (k_wy_w with blockIdx.y > 0), summed by k_wy_sum
     size_t wy_part_cap = 0;
     double *wy_w = nullptr, *wy_m = nullptr, *wy_t = nullptr, *wy_small = nullptr;   // 2 x (rows x 64) coefficients, M, T = M^-1 (one per block of a sweep), 2 x (64 x 16)
@@ -2434,19 +2498,15 @@ struct og_qp_s {
         hipStream_t s = nullptr;       // lane 0: the stream of the call
         double *w = nullptr, *part = nullptr;
     } lane[3];
-    bool wide_ahead = false;
     std::vector<hipEvent_t> ev_t, ev_tc;   // per block: T is there (caller's stream) / the rest of C Z has it applied (lane 1)
     hipEvent_t ev_join[2] = {nullptr, nullptr};
     int spin_limit = 1 << 19;          // bound of the inter-workgroup waits: polls of ~1.5 us each, i.e. about a second (2^25 - a
                                        // minute per lost wait - until round 5); OGSQP_SPIN_LIMIT: tests force a loss with 1
     int spin_default = 1 << 19;        // ... as og_qp_create set it (og_qp_set_spin_limit changes it for a while)
     int recoveries = 0;                // subproblems re-run with the separate-launch forms after a wait gave up
-    bool lq_ahead = true;              // OGSQP_LQ=16: panel and trailing update as separate launches
-    int trsv_mode = 0;                 // OGSQP_TRSV: 0 one chained launch, 1 ("block") a launch per block, 2 ("single")
     unsigned* lq_go = nullptr;         // look-ahead: head workgroups that have finished the next panel's rows, ever
     unsigned lq_token = 0u;            // ... and what the count will be after the launch being enqueued
     double* lq_wpart = nullptr;        // the head workgroups' partial products (LQ_HEADS x 64 x 4)
-    bool lq16 = true;                  // OGSQP_LQ=8: the sweep of 8-reflector panels only
     int coop_mode = 1;                 // 0 never, 1 by size, 2 always (when it fits)
     int last_iters = 1000;             // active-set changes of the previous subproblem on this handle (a solve starts with many)
     double *d = nullptr, *bm = nullptr, *tvec = nullptr, *rhs = nullptr, *lam = nullptr, *vz = nullptr;
@@ -2492,24 +2552,136 @@ bool debug_stages() {
         if (rc_) return rc_;  \
     } while (0)
 
-// L x = scale * rhs (or L' x): block by block over the whole chip (k_trsv_block); OGSQP_TRSV=single: the one-workgroup
-// kernel.  `scal` is a device scalar of scratch.
-int launch_trsv(og_qp_s* qp, int ldw, int meq, int transposed, double scale_rhs, const double* rhs, double* x,
-                hipStream_t s);
-int launch_gemm(og_qp_s* qp, const AView& A, int col0, int rows, int nq, int ldw, double* out, const int* sel,
-                hipStream_t s);
+// The arguments of og_qp_solve_dev, as the caller gave them.
+struct QpCall {
+    const double* d_jt; int64_t ld; const double *g, *c, *dl, *du; int32_t augmented; double rho;
+    double *d, *mult, *bound_mult; int32_t *status, *iterations; void* hip_stream;
+};
 
-size_t gi_lds_bytes(int nr, int qcap) {
-    return (size_t)(2 * nr + 6 * qcap + 64) * sizeof(double);
+// One attempt at a subproblem: its sizes, and what its stages hand to the ones after them.
+struct QpAttempt {
+    hipStream_t s = nullptr;
+    int n = 0, n1 = 0, ldw = 0, meq = 0, mg = 0, m = 0;
+    int nq = 0, nr = 0;                // columns of this subproblem (n, or n + 1 when relaxed), null-space coordinates
+    AView A{};
+    int nwarm = 0, msweep = 0;         // rows of the warm start, rows the sweep makes triangular (meq + nwarm)
+    GiArgs ga{};                       // (ldp_setup)
+    int hflag[4] = {0, 0, 0, 0};       // qp->flag as fetch_status() saw it last: [0] a contradicting equality row, [1] a
+                                       // row nothing can fix, [2] / [3] a wait of the sweep / of another kernel gave up
+    GiState hst{};                     // the active-set loop's state, likewise
+    bool res_launched = false;         // a resident launch ran: its mailbox may hold records of a launch that stopped
+    bool* lost = nullptr;              // -> true: a wait gave up, the attempt is void (nothing of the handle's state changed)
+    bool over = false;                 // no later stage is to run: lost, or *status holds the verdict
+};
+
+// a stage of an attempt: on an error or when the attempt is over, so is the caller
+#define OG_RUN(stage) do { int rc_ = (stage); if (rc_ || at.over) return rc_; } while (0)
+
+// The flag words, and with `state` the active-set loop's GiState, in ONE synchronise of the attempt's stream.
+int fetch_status(og_qp_s* qp, QpAttempt& at, bool state, bool flags = true) {
+    if (state) OG_HIP(hipMemcpyAsync(&at.hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, at.s));
+    if (flags) OG_HIP(hipMemcpyAsync(at.hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, at.s));
+    OG_HIP(hipStreamSynchronize(at.s));
+    return 0;
 }
 
-size_t rows_lds_bytes(int nr, int qcap) {          // k_rows_decide: the incoming normal, the dual direction, a reflector
-    return (size_t)(nr + 2 * qcap + 16) * sizeof(double);
+// The mailbox of the resident launch is zeroed when one ran in an attempt that ends early.  The launch may have
+// stopped half way: its workgroups published records under exchange numbers that were never written back to res_seq,
+// and the next launch on the handle counts through the same numbers again and would take those records for its own
+// (valid numbers start at 1: a zeroed record matches none).
+int clear_mail(og_qp_s* qp, const QpAttempt& at) {
+    if (at.res_launched) OG_HIP(hipMemsetAsync(qp->res_mail, 0, qp->res_mail_bytes, at.s));
+    return 0;
 }
 
-}  // namespace
+int give_up(og_qp_s* qp, QpAttempt& at) {                 // the attempt is lost: og_qp_solve_dev runs it again
+    *at.lost = at.over = true;
+    return clear_mail(qp, at);
+}
 
-namespace {
+// A look-ahead workgroup of the sweep, a block of the chained solve or a workgroup of the active-set kernels gave up
+// waiting (the flags as fetch_status() saw them): whatever came after it ran on garbage, and the attempt is given up.
+int give_up_if_wait_lost(og_qp_s* qp, QpAttempt& at) { return at.hflag[2] || at.hflag[3] ? give_up(qp, at) : 0; }
+
+// -DOGSQP_TRACE: what the kernels' own clocks recorded, on stderr
+#ifdef OGSQP_TRACE
+int trace_panel16(hipStream_t s, int k, int len16, const Lq16Panel* panel) {
+    Lq16Panel hp;
+    OG_HIP(hipMemcpyAsync(&hp, panel, sizeof(Lq16Panel), hipMemcpyDeviceToHost, s));
+    OG_HIP(hipStreamSynchronize(s));
+    fprintf(stderr, "[ogsqp trace] panel16 at k = %d (len %d) ticks (wavefront 0): load %lld first reflector %lld waits for the flag %lld vector %lld row in line %lld other row %lld store %lld\n",
+            k, len16, hp.tr[0], hp.tr[5], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[6]);
+    return 0;
+}
+
+// (`next`: the panel the look-ahead factored on the side, null without it)
+int trace_apply16(hipStream_t s, int len16, int rpg, const Lq16Panel* next) {
+    long long tr[8];
+    OG_HIP(hipStreamSynchronize(s));
+    OG_HIP(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_apply16_trace), sizeof tr));
+    fprintf(stderr, "[ogsqp trace] apply16 at k = 0 (len %d, %d rows per workgroup), 10 ns ticks: header %lld loads %lld "
+                    "product-1 %lld barrier %lld products-2,3 %lld stores %lld\n", len16, rpg, tr[0], tr[1], tr[2],
+            tr[3], tr[4], tr[5]);
+    if (next) {
+        Lq16Panel hp;
+        OG_HIP(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_head16_trace), sizeof tr));
+        OG_HIP(hipMemcpy(&hp, next, sizeof(Lq16Panel), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[ogsqp trace] head workgroup 0, 10 ns ticks: header %lld loads %lld product-1 %lld barrier %lld "
+                        "exchange %lld products-2,3 + stores issued %lld drain %lld; its panel (shader clocks, wavefront 0): load %lld "
+                        "first reflector %lld waits for the flag %lld vector %lld row in line %lld other row %lld store %lld\n", tr[0], tr[1],
+                tr[2], tr[3], tr[6], tr[4], tr[5], hp.tr[0], hp.tr[5], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[6]);
+    }
+    return 0;
+}
+
+// (`len`: the length of the first panel's rows; -1: the last panel of the sweep)
+int trace_panel8(hipStream_t s, const LqPanel* panel, int len) {
+    LqPanel hp;
+    OG_HIP(hipMemcpyAsync(&hp, panel, sizeof(LqPanel), hipMemcpyDeviceToHost, s));
+    OG_HIP(hipStreamSynchronize(s));
+    const std::string which = len < 0 ? "last panel kernel" : "first panel kernel (len " + std::to_string(len) + ")";
+    fprintf(stderr, "[ogsqp trace] %s ticks: load %lld products %lld reduction %lld update %lld gram %lld gram-red %lld store %lld\n",
+            which.c_str(), hp.tr[0], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[5], hp.tr[6]);
+    return 0;
+}
+
+void trace_cooperative(const GiState& hst, int coop_G) {
+    static const char* nm[12] = {"pricing", "barrier 1", "projections 1", "barrier 2", "gather a, z1", "barrier 2b",
+                                 "projections 2", "barrier 3", "gather a2, z2, r", "barrier 4", "updates",
+                                 "barrier 5"};
+    fprintf(stderr, "[ogsqp trace] cooperative: %d iterations, G = %d\n", hst.iters, coop_G);
+    for (int e = 0; e < 12; ++e)
+        fprintf(stderr, "[ogsqp trace]   %-18s %8.0f ticks per iteration\n", nm[e],
+                hst.iters ? (double)hst.tr[e] / hst.iters : 0.0);
+}
+
+void trace_active_set(const GiState& hst, bool rows_mode, bool res_trace) {
+    static const char* names_iter[9] = {"phase A + wait", "election", "load normal", "projections", "z update",
+                                        "r + ratio test", "u,y update", "append", "removal"};
+    static const char* names_rows[9] = {"state word", "who comes in", "normal in LDS", "norms", "inverse rows x d1",
+                                        "stores + ticket", "others' r, ratio", "u, y", "reflector, lists"};
+    static const char* names_res[16] = {"price, workgroup's best", "publish + poll + election", "winner's row", "(2) row from its owner", "norms",
+                                        "r: product, publish", "r: poll", "ratio test", "step, u, y, |y|", "row joins", "row leaves",
+                                        "pass over rows", "closing barrier", "(wave 15) pass over y", "-", "-"};
+    const char* const* names = rows_mode ? names_rows : names_iter;
+    fprintf(stderr, "[ogsqp trace] %d iterations, %lld passes, %lld removals, %d active at the end\n", hst.iters,
+            hst.tr[10], hst.tr[11], hst.q);
+    for (int e = 0; e < 9; ++e)
+        fprintf(stderr, "[ogsqp trace]   %-16s %8.2f us per iteration\n", names[e],
+                hst.iters ? 0.01 * (double)hst.tr[e] / hst.iters : 0.0);
+    if (res_trace)
+        for (int e = 0; e < 14; ++e)
+            fprintf(stderr, "[ogsqp trace]   resident: %-22s %8.2f us per change (%lld changes, %lld partial)\n", names_res[e],
+                    hst.tr[38] ? 0.01 * (double)hst.tr[16 + e] / hst.tr[38] : 0.0, hst.tr[38], hst.tr[39]);
+}
+#else
+template <typename... T> int trace_panel16(T&&...) { return 0; }
+template <typename... T> int trace_apply16(T&&...) { return 0; }
+template <typename... T> int trace_panel8(T&&...) { return 0; }
+template <typename... T> void trace_cooperative(T&&...) {}
+template <typename... T> void trace_active_set(T&&...) {}
+#endif
+
 // column slices of a product with `rows` rows of length L: enough workgroups for every SIMD of the chip (a workgroup of
 // k_wy_w is two wavefronts that issue 16 MFMAs per 2 KB of A); few rows: at most 32 slices - the kernels that add the
 // slices up walk them one after the other.  (k_wy_inblock uses the SAME slices: its sums are these sums.)
@@ -2574,10 +2746,10 @@ void wy_apply_block(og_qp_s* qp, const og_qp_s::WyLane& ln, double* A, int ld, i
 
 // The sweep over rows longer than LQW_SLAB entries, from reflector k on, in blocks of LQW_BLOCK reflectors: returns the
 // first reflector it did not handle (rows short enough for the look-ahead kernels, or msweep).
-int lq_sweep_wide(og_qp_s* qp, int msweep, int nq, int ldw, int k, hipStream_t s, int* done) {
+int lq_sweep_wide(og_qp_s* qp, const QpForms& f, int msweep, int nq, int ldw, int k, hipStream_t s, int* done) {
     og_qp_s::WyLane& l0 = qp->lane[0];
     l0.s = s, l0.w = qp->wy_w, l0.part = qp->wy_part;
-    const bool ahead = qp->wide_ahead;
+    const bool ahead = f.wide_ahead;
     int rc = 0, b = 0;
     // (a failing runtime call ends the loop through rc instead of returning: the exit below joins the lanes first)
 #define WIDE_HIP(expr)                                                                                   \
@@ -2602,7 +2774,7 @@ int lq_sweep_wide(og_qp_s* qp, int msweep, int nq, int ldw, int k, hipStream_t s
                 double* A = qp->Tc + (size_t)(kk + nb16) * ldw + kk;
                 int nsplit = 1, kb_per = 1;
                 wy_split(qp, rest, len, &nsplit, &kb_per);
-                if (qp->wide_inblock && rest <= 16 * WIB_WAVES && kb_per <= WIB_KB) {
+                if (f.wide_inblock && rest <= 16 * WIB_WAVES && kb_per <= WIB_KB) {
                     // one launch: the slices' workgroups exchange their shares of the products (k_wy_inblock)
                     qp->wide_in_token += (unsigned)nsplit;
                     hipLaunchKernelGGL(k_wy_inblock, dim3(nsplit), dim3(64 * WIB_WAVES), 0, s, A, ldw, rest, len,
@@ -2681,9 +2853,11 @@ int launch_gemm(og_qp_s* qp, const AView& A, int col0, int rows, int nq, int ldw
     return 0;
 }
 
-int launch_trsv(og_qp_s* qp, int ldw, int meq, int transposed, double scale_rhs, const double* rhs, double* x,
-                hipStream_t s) {
-    if (qp->trsv_mode == 2 || meq <= 128) {
+// L x = scale * rhs (or L' x): one chained launch, or block by block over the whole chip (k_trsv_block); OGSQP_TRSV=single
+// and few rows: the one-workgroup kernel
+int launch_trsv(og_qp_s* qp, const QpForms& f, int ldw, int meq, int transposed, double scale_rhs, const double* rhs,
+                double* x, hipStream_t s) {
+    if (f.trsv_mode == 2 || meq <= 128) {
         const size_t trsv_lds = (size_t)(meq + 64 * 65) * sizeof(double);
         hipLaunchKernelGGL(k_trsv, dim3(1), dim3(1024), trsv_lds, s, qp->Tc, ldw, qp->diagL, meq, transposed, scale_rhs,
                            rhs, x, qp->dthresh, qp->flag);
@@ -2693,7 +2867,7 @@ int launch_trsv(og_qp_s* qp, int ldw, int meq, int transposed, double scale_rhs,
         hipLaunchKernelGGL(k_trsv_invert, dim3((meq + 63) / 64), dim3(64), 0, s, qp->Tc, ldw, qp->diagL, meq, qp->dthresh,
                            qp->Linv, qp->has_gone);
     const int nblk = (meq + 63) / 64;
-    if (qp->trsv_mode == 0 && nblk <= 128 && x != rhs) {
+    if (f.trsv_mode == 0 && nblk <= 128 && x != rhs) {
         // one launch: a chain of hand-offs between the block rows' workgroups (k_trsv_chain)
         hipLaunchKernelGGL(k_trsv_prepare, dim3(1), dim3(256), 0, s, rhs, meq, scale_rhs, qp->trsv_work, qp->dthresh + 2, x);
         hipLaunchKernelGGL(k_trsv_chain, dim3(nblk), dim3(256), 0, s, qp->Tc, ldw, qp->diagL, meq, transposed,
@@ -2714,6 +2888,649 @@ int launch_trsv(og_qp_s* qp, int ldw, int meq, int transposed, double scale_rhs,
     }
     return 0;
 }
+
+// ---- the launches of the sweep, each kernel chosen by the length of the rows
+
+// dynamic LDS of a 16-reflector panel over E groups of 256 columns (k_lq_panel16<E>, k_lq_step16<U, E>'s panel workgroup)
+constexpr size_t panel16_lds(int E) { return (size_t)(E <= 6 ? P16_RING : 2) * 256 * E * sizeof(double); }
+
+// blocks of 16 columns per wavefront for rows of `ub` blocks of 128 entries (k_lq_apply16<U>, k_lq_step16<U, E>)
+constexpr int lq16_u(int ub) { return ub <= 2 ? 2 : ub <= 4 ? 4 : ub <= 8 ? 8 : ub <= 12 ? 12 : 16; }
+
+// the kernels whose dynamic LDS og_qp_create lets go up to LDS_LIMIT
+const void* const BIG_LDS[] = {(const void*)k_gi_iter, (const void*)k_gi_coop, (const void*)k_trsv,
+                               (const void*)k_rows_decide, (const void*)k_rows_invert, (const void*)k_rows_resident,
+                               (const void*)k_rows_apply_stream<true>, (const void*)k_rows_apply_stream<false>};
+
+// The look-ahead kernels there are: og_qp_create raises the dynamic-LDS limit of each, launch_step16 picks one.
+struct Step16 { int U, E; decltype(&k_lq_step16<2, 1>) kernel; };
+#define OG_S16(U, E) Step16{U, E, k_lq_step16<U, E>}
+constexpr Step16 STEP16[] = {OG_S16(2, 1),  OG_S16(2, 2),  OG_S16(4, 1),  OG_S16(4, 2),  OG_S16(8, 2),
+                             OG_S16(8, 3),  OG_S16(8, 4),  OG_S16(12, 4), OG_S16(12, 5), OG_S16(12, 6),
+                             OG_S16(16, 6), OG_S16(16, 7), OG_S16(16, 8)};
+#undef OG_S16
+
+// -> the entry of STEP16 for rows of len16 entries now (U) and of len16 - 16 in the NEXT panel (E groups of 256, exact)
+constexpr int step16_index(int len16) {
+    const int U = lq16_u((len16 + 127) / 128), E = std::max(1, (len16 - LQ16 + 255) / 256);
+    for (int i = 0; i < (int)(sizeof(STEP16) / sizeof(STEP16[0])); ++i)
+        if (STEP16[i].U == U && STEP16[i].E == E) return i;
+    return -1;
+}
+
+constexpr bool step16_covers(int first, int last) {
+    for (int len16 = first; len16 <= last; ++len16) {
+        const int i = step16_index(len16);
+        if (i < 0 || 128 * STEP16[i].U < len16 || STEP16[i].E != std::max(1, (len16 - LQ16 + 255) / 256)) return false;
+    }
+    return true;
+}
+// (a look-ahead launch has a next panel: more than 16 entries; the 16-reflector kernels hold rows of up to 2048)
+static_assert(step16_covers(LQ16 + 1, 2048), "a row length has no k_lq_step16<U, E> that holds its rows and the next panel's");
+
+void launch_panel16(int eg, og_qp_s* qp, const QpAttempt& at, int k, double* V, Lq16Panel* panel) {
+    // (E = groups of 256 columns, exactly: the panel's steps are bound by the multiply-adds it issues, padding included)
+    constexpr decltype(&k_lq_panel16<1>) kernels[8] = {k_lq_panel16<1>, k_lq_panel16<2>, k_lq_panel16<3>, k_lq_panel16<4>,
+                                                       k_lq_panel16<5>, k_lq_panel16<6>, k_lq_panel16<7>, k_lq_panel16<8>};
+    const int E = std::min(eg, 8);
+    hipLaunchKernelGGL(kernels[E - 1], dim3(1), dim3(P16_THREADS), panel16_lds(E), at.s, qp->Tc, at.ldw, at.msweep, at.nq,
+                       k, V, at.ldw, qp->diagL, panel, qp->dthresh + 1);
+}
+
+// the trailing update of panel k, whose launch factors the next panel on the side (k_lq_step16)
+int launch_step16(int len16, og_qp_s* qp, const QpAttempt& at, int k, int nrows16, int rpg, const double* V,
+                  const Lq16Panel* panel, double* Vnext, Lq16Panel* pnext) {
+    const int i = step16_index(len16);
+    if (i < 0) return fail(8, "og_qp_solve_dev: no look-ahead kernel for rows of this length (internal error)");
+    hipLaunchKernelGGL(STEP16[i].kernel, dim3(1 + LQ_HEADS + (std::max(nrows16 - LQ16, 0) + rpg - 1) / rpg),
+                       dim3(64 * A16_WAVES), panel16_lds(STEP16[i].E), at.s, qp->Tc, qp->Jw, at.ldw, at.msweep, at.nq, k, V,
+                       at.ldw, panel, Vnext, pnext, qp->diagL, qp->dthresh + 1, rpg, qp->lq_go,
+                       (qp->lq_token += LQ_HEADS), qp->lq_wpart, qp->flag + 2, qp->spin_limit);
+    return 0;
+}
+
+void launch_apply16(int ub, og_qp_s* qp, const QpAttempt& at, int k, int nrows16, int rpg, const double* V,
+                    const Lq16Panel* panel) {
+    constexpr decltype(&k_lq_apply16<2>) kernels[5] = {k_lq_apply16<2>, k_lq_apply16<4>, k_lq_apply16<8>, k_lq_apply16<12>,
+                                                       k_lq_apply16<16>};
+    const int i = ub <= 2 ? 0 : ub <= 4 ? 1 : ub <= 8 ? 2 : ub <= 12 ? 3 : 4;
+    hipLaunchKernelGGL(kernels[i], dim3((nrows16 + rpg - 1) / rpg), dim3(64 * A16_WAVES), 0, at.s, qp->Tc, qp->Jw, at.ldw,
+                       at.msweep, at.nq, k, V, at.ldw, panel, rpg);
+}
+
+void launch_panel8(int len, og_qp_s* qp, const QpAttempt& at, int k) {
+    constexpr int PS = PANEL_SMALL_PT, PM = LQ_PT_MAX;      // threads: few while the panel fits their registers
+    constexpr decltype(&k_lq_panel<PS, 4>) kernels[6] = {k_lq_panel<PS, 4>, k_lq_panel<PS, 8>, k_lq_panel<PS, 12>,
+                                                         k_lq_panel<PM, 4>, k_lq_panel<PM, 8>, k_lq_panel<PM, LQ_CPT_MAX>};
+    const int i = len <= PS * 4 ? 0 : len <= PS * 8 ? 1 : len <= PS * 12 ? 2 : len <= PM * 4 ? 3 : len <= PM * 8 ? 4 : 5;
+    hipLaunchKernelGGL(kernels[i], dim3(1), dim3(i < 3 ? PS : PM), 0, at.s, qp->Tc, at.ldw, at.msweep, at.nq, k, qp->Vp,
+                       qp->diagL, qp->panel, qp->dthresh + 1);
+}
+
+void launch_apply8(int len, og_qp_s* qp, const QpAttempt& at, int k, int nrows) {
+    constexpr decltype(&k_lq_apply) kernels[4] = {k_lq_apply_reg<2>, k_lq_apply_reg<4>, k_lq_apply_reg<6>, k_lq_apply};
+    const int jt = (len + 255) / 256, i = jt <= 2 ? 0 : jt <= 4 ? 1 : jt <= 6 ? 2 : 3;
+    hipLaunchKernelGGL(kernels[i], dim3((nrows + LQ_RW - 1) / LQ_RW), dim3(256), 0, at.s, qp->Tc, qp->Jw, at.ldw, at.msweep,
+                       at.nq, k, qp->Vp, qp->panel);
+}
+
+// The pass over the rows of a change, by the length nr of a row of the inverse: which kernel, and its dynamic LDS.
+struct RowsApply { void (*kernel)(RowsArgs); size_t lds; };
+
+RowsApply pick_rows_apply(const QpForms& f, int nr) {
+    const int tail_lanes = (nr + 63) / 64;
+    // long rows are streamed, the row staged in LDS when five vectors of the null space fit a workgroup's share
+    const size_t nrp = (size_t)tail_lanes * 64;
+    const bool stream = f.rows_stream && tail_lanes > 16;
+    // (the second pass re-reads the row from the caches by default: staging it in LDS - OGSQP_ROWS=stage, where five
+    // vectors fit - costs the occupancy the streamed form lives on: 111 instead of 47 us per change at C5)
+    const bool stage = stream && f.rows_stage > 0 && 5 * nrp * sizeof(double) <= LDS_LIMIT;
+    if (stream) return {stage ? k_rows_apply_stream<true> : k_rows_apply_stream<false>, (stage ? 5 : 1) * nrp * sizeof(double)};
+    if (f.rows_r4 >= 0 && tail_lanes <= 8) return {k_rows_apply_r4<8>, 0};
+    if (f.rows_r4 > 0 && tail_lanes <= 16) return {k_rows_apply_r4<16>, 0};
+    constexpr decltype(&k_rows_apply<8>) kernels[4] = {k_rows_apply<8>, k_rows_apply<16>, k_rows_apply<32>, k_rows_apply<80>};
+    return {kernels[tail_lanes <= 8 ? 0 : tail_lanes <= 16 ? 1 : tail_lanes <= 32 ? 2 : 3], 0};
+}
+
+void launch_rows_apply(const RowsApply& pass, const RowsArgs& ra, hipStream_t s) {
+    hipLaunchKernelGGL(pass.kernel, dim3(ra.G2), dim3(ROWS_THREADS), pass.lds, s, ra);
+}
+
+// ---- the stages of an attempt, in the order qp_solve_attempt runs them
+
+// g, dl, du, c (and the relaxation's row) on the device, the flags cleared, Jw = the work copy of the factor Z
+int upload_inputs(og_qp_s* qp, const QpCall& in, const QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int n = at.n, n1 = at.n1, m = at.m, nq = at.nq;
+    std::vector<double>& hs = qp->host_stage;
+    hs.assign((size_t)3 * n1 + m, 0.0);
+    double *hg = hs.data(), *hdl = hg + n1, *hdu = hdl + n1, *hc = hdu + n1;
+    memcpy(hg, in.g, sizeof(double) * n);
+    memcpy(hdl, in.dl, sizeof(double) * nq);
+    memcpy(hdu, in.du, sizeof(double) * nq);
+    if (m) memcpy(hc, in.c, sizeof(double) * m);
+    OG_HIP(hipMemcpyAsync(qp->g, hg, sizeof(double) * n1, hipMemcpyHostToDevice, s));
+    OG_HIP(hipMemcpyAsync(qp->dl, hdl, sizeof(double) * n1, hipMemcpyHostToDevice, s));
+    OG_HIP(hipMemcpyAsync(qp->du, hdu, sizeof(double) * n1, hipMemcpyHostToDevice, s));
+    if (m) OG_HIP(hipMemcpyAsync(qp->c, hc, sizeof(double) * m, hipMemcpyHostToDevice, s));
+    OG_HIP(hipMemsetAsync(qp->flag, 0, 4 * sizeof(int), s));
+    if (in.augmented && m)
+        hipLaunchKernelGGL(k_relaxation_row, dim3((m + 255) / 256), dim3(256), 0, s, qp->c, at.meq, m, qp->extra);
+    OG_STAGE("copy_factor");
+    hipLaunchKernelGGL(k_copy_factor, dim3((nq + 255) / 256, nq), dim3(256), 0, s, qp->Z, qp->Jw, at.ldw, n, nq,
+                       in.augmented ? 1.0 / in.rho : 0.0);
+    return 0;
+}
+
+// The rows of a warm start - active at the solution of the previous subproblem - appended to the sweep: their ids in
+// d_warm, the rows themselves in Tc behind the equalities; at.nwarm, at.msweep
+int warm_rows(og_qp_s* qp, const QpForms& f, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int meq = at.meq, mg = at.mg, nq = at.nq, nr = at.nr, ldw = at.ldw;
+    at.nwarm = 0;
+    at.msweep = meq;
+    if (!(f.gi_mode == 0 && f.warm_enabled && qp->warm_use && nr > 0 && !qp->warm.empty())) return 0;
+    std::vector<int> general, bound;
+    for (int id : qp->warm) {
+        const int i = (id - mg) >> 1, upper = (id - mg) & 1;
+        if (id < mg) general.push_back(id);
+        else if (i < nq) bound.push_back(mg + (upper ? nq : 0) + i);
+    }
+    std::vector<int> ids(general);
+    ids.insert(ids.end(), bound.begin(), bound.end());
+    if ((int)ids.size() > nr) ids.resize(nr);
+    const int nwarm = (int)ids.size(), ng = std::min((int)general.size(), nwarm);
+    if (!nwarm) return 0;
+    OG_HIP(hipMemcpyAsync(qp->d_warm, ids.data(), sizeof(int) * nwarm, hipMemcpyHostToDevice, s));
+    OG_HIP(hipStreamSynchronize(s));                   // ids is a local
+    double* Text = qp->Tc + (size_t)meq * ldw;
+    OG_STAGE("warm rows");
+    if (ng) OG_TRY(launch_gemm(qp, at.A, meq, ng, nq, ldw, Text, (const int*)qp->d_warm, s));
+    if (nwarm > ng)
+        hipLaunchKernelGGL(k_rows_gather_bounds, dim3((nq + 255) / 256, nwarm - ng), dim3(256), 0, s, qp->Jw, ldw, nq, mg,
+                           (const int*)qp->d_warm, ng, nwarm, Text);
+    at.nwarm = nwarm;
+    at.msweep = meq + nwarm;
+    return 0;
+}
+
+// 8 reflectors per trip from *k on (k_lq_panel, k_lq_apply*), until the 16-reflector kernels can take over: the rows fit
+// them and k is a multiple of 16 - which then holds to the end of the sweep - or, with OGSQP_LQ=8, to the end
+int lq_loop8(og_qp_s* qp, const QpForms& f, const QpAttempt& at, int* k_io) {
+    int k = *k_io;
+    for (; k < at.msweep && !(f.lq16 && at.nq - k <= 2048 && k % LQ16 == 0); k += LQ_NB) {
+        const int nb = std::min(LQ_NB, at.msweep - k), nrows = (at.msweep - k - nb) + at.nq;
+        const int len = at.nq - k;                             // length of the panel rows
+        launch_panel8(len, qp, at, k);
+        if (k == 0) OG_TRY(trace_panel8(at.s, qp->panel, len));
+        launch_apply8(len, qp, at, k, nrows);
+    }
+    *k_io = k;
+    return 0;
+}
+
+// 16 reflectors per trip from k to the end of the sweep: row-distributed panel kernel, MFMA trailing update
+// (ogsqp_lq16.h); with the look-ahead the launch of the update factors the next panel on the side
+int lq_loop16(og_qp_s* qp, const QpForms& f, const QpAttempt& at, int k) {
+    const int msweep = at.msweep, nq = at.nq;
+    double *Vcur = qp->V16, *Vnxt = qp->V16b;
+    Lq16Panel *pcur = qp->panel16, *pnxt = qp->panel16b;
+    int factored = -1;                                         // the panel the previous launch factored on the side
+    for (; k < msweep; k += LQ16) {
+        const int nb16 = std::min(LQ16, msweep - k), len16 = nq - k;
+        const int nrows16 = (msweep - k - nb16) + nq;
+        const int eg = (len16 + 255) / 256, ub = (len16 + 127) / 128;
+        // rows per workgroup of the trailing update: 16, or as few as fill the chip (not below 8: each reads all of V)
+        const int rpg = std::max(8, std::min(LQ16, (nrows16 + 239) / 240));
+        if (factored != k) {
+            launch_panel16(eg, qp, at, k, Vcur, pcur);
+            if (k == 0 || k == 512) OG_TRY(trace_panel16(at.s, k, len16, pcur));
+        }
+        if (f.lq_ahead && k + LQ16 < msweep) {
+            OG_TRY(launch_step16(len16, qp, at, k, nrows16, rpg, Vcur, pcur, Vnxt, pnxt));
+            if (k == 0) OG_TRY(trace_apply16(at.s, len16, rpg, pnxt));
+            factored = k + LQ16;
+            std::swap(Vcur, Vnxt), std::swap(pcur, pnxt);
+        } else {
+            launch_apply16(ub, qp, at, k, nrows16, rpg, Vcur, pcur);
+            if (k == 0) OG_TRY(trace_apply16(at.s, len16, rpg, f.lq_ahead ? pnxt : nullptr));
+        }
+    }
+    return 0;
+}
+
+// Tc = L of (C Z; the warm rows) Q and Jw = Z Q: the sweep's threshold and look-ahead counts reset, the product C Z,
+// the reflectors in the form the rows' length asks for, the verdict on L's diagonal (flag[0], dthresh)
+int lq_sweep(og_qp_s* qp, const QpForms& f, const QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int meq = at.meq, nq = at.nq, ldw = at.ldw, msweep = at.msweep;
+    if (msweep) {
+        OG_STAGE("gemm C Z");
+        if (meq) OG_TRY(launch_gemm(qp, at.A, 0, meq, nq, ldw, qp->Tc, (const int*)nullptr, s));
+        OG_STAGE("lq sweep");
+        OG_HIP(hipMemsetAsync(qp->dthresh, 0, 2 * sizeof(double), s));
+        OG_HIP(hipMemsetAsync(qp->lq_go, 0, 2 * sizeof(unsigned), s)); // counts of the head workgroups, this sweep
+        qp->lq_token = 0u;
+        int k = 0;
+        if (f.lq_wide && nq > LQW_SLAB) {
+            // long rows: column-split panels and 64-reflector blocks until the rows fit one workgroup (ogsqp_lqwide.h)
+            OG_STAGE("lq sweep, wide blocks");
+            OG_TRY(lq_sweep_wide(qp, f, msweep, nq, ldw, 0, s, &k));
+        }
+        OG_TRY(lq_loop8(qp, f, at, &k));
+        OG_TRY(lq_loop16(qp, f, at, k));
+        OG_TRY(trace_panel8(s, qp->panel, -1));
+        OG_STAGE("check diag");
+        if (meq) hipLaunchKernelGGL(k_check_diag, dim3(1), dim3(1024), 0, s, qp->diagL, meq, qp->flag, qp->dthresh);
+    }
+    OG_HIP(hipGetLastError());
+    return 0;
+}
+
+// The equality-constrained minimiser: L w1 = -c, deq = J1 w1 - Y (Y'g).  The first look at the flags: the attempt is
+// over when a wait of the sweep or of the chained solve gave up, or an equality row contradicts the others.
+int equality_minimiser(og_qp_s* qp, const QpForms& f, const QpCall& in, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int meq = at.meq, nq = at.nq, nr = at.nr, ldw = at.ldw;
+    OG_STAGE("trsv w1");
+    if (meq) launch_trsv(qp, f, ldw, meq, 0, -1.0, qp->c, qp->w1, s);
+    OG_TRY(fetch_status(qp, at, false));
+    OG_RUN(give_up_if_wait_lost(qp, at));
+    if (at.hflag[0]) {                    // a dependent equality row that contradicts the others
+        *in.status = OG_QP_SINGULAR_C;
+        at.over = true;
+        return 0;
+    }
+    OG_STAGE("deq");
+    if (nr > 0)
+        hipLaunchKernelGGL(k_gemv_cols, dim3((nr + 63) / 64), dim3(1024), 0, s, qp->Jw + meq, (long)ldw, nq, nr, qp->g,
+                           (const double*)nullptr, qp->t1);
+    hipLaunchKernelGGL(k_concat_neg, dim3((nq + 255) / 256), dim3(256), 0, s, qp->w1, meq, qp->t1, nr, qp->xcat);
+    hipLaunchKernelGGL(k_gemv_rows, dim3((nq + 3) / 4), dim3(256), 0, s, qp->Jw, (long)ldw, nq, nq, qp->xcat, 1.0,
+                       (const double*)nullptr, qp->deq);
+    return 0;
+}
+
+// The least-distance problem in the null space: GJ = G J, the rows' right-hand sides, scales and owners (k_ldp_setup);
+// at.ga: what every active-set kernel is given
+int ldp_setup(og_qp_s* qp, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int meq = at.meq, mg = at.mg, nq = at.nq, ldw = at.ldw;
+    OG_STAGE("gemm G J");
+    if (mg) {
+        OG_TRY(launch_gemm(qp, at.A, meq, mg, nq, ldw, qp->GJ, (const int*)nullptr, s));
+        hipLaunchKernelGGL(k_gemv_cols_A, dim3((mg + 63) / 64), dim3(1024), 0, s, at.A, meq, nq, mg, qp->deq,
+                           qp->c + meq, qp->bG);
+    }
+    OG_STAGE("ldp setup");
+    hipLaunchKernelGGL(k_ldp_setup, dim3((mg + nq + 3) / 4), dim3(256), 0, s, qp->GJ, qp->Jw, ldw, meq, nq, mg, qp->bG,
+                       qp->c + meq, qp->deq, qp->dl, qp->du, qp->bval, qp->scale, qp->own, qp->flag);
+    GiArgs& ga = at.ga;
+    ga.GJ = qp->GJ; ga.Jw = qp->Jw; ga.ld = ldw; ga.meq = meq; ga.nq = nq; ga.mg = mg; ga.nr = at.nr;
+    ga.qcap = qp->qcap; ga.bval = qp->bval; ga.scale = qp->scale; ga.own = qp->own; ga.u = qp->u;
+    ga.isact = qp->isact; ga.y = qp->y; ga.act = qp->act; ga.R[0] = qp->R[0]; ga.R[1] = qp->R[1];
+    ga.RI[0] = qp->RI[0]; ga.RI[1] = qp->RI[1]; ga.Q1t = qp->Q1t; ga.partials = qp->partials; ga.st = qp->st;
+    ga.limit = 10 * (mg + 2 * nq + at.nr) + 100;
+    return 0;
+}
+
+// Round 6: the whole active-set loop as ONE launch of res_wg workgroups with the rows in registers (ogsqp_resident.h).
+// In front of it as many two-launch pairs as the warm start's removals are expected to take (in `only_warm` form: with
+// the warm start over they do nothing); the launch returns at once while the warm start is not over.  One synchronise
+// per launch fetches its state and the flags.
+int run_resident(og_qp_s* qp, QpAttempt& at, const RowsArgs& ra, const RowsApply& pass, size_t lds_decide, int res_wg) {
+    hipStream_t s = at.s;
+    ResArgs rs;
+    rs.r = ra; rs.mail = qp->res_mail; rs.seq = qp->res_seq; rs.NW = res_wg;
+    RowsArgs rw = ra;
+    rw.only_warm = 1;
+    const size_t ldsr = res_lds_bytes(at.nr, qp->qcap);
+    int pairs = at.nwarm ? std::max(1, qp->warm_pairs_hint) : 0;
+    long warm_launched = 0;
+    while (true) {
+        for (int it = 0; it < pairs; ++it) {
+            hipLaunchKernelGGL(k_rows_decide, dim3(rw.G1), dim3(ROWS_THREADS), lds_decide, s, rw);
+            launch_rows_apply(pass, rw, s);
+        }
+        warm_launched += pairs;
+        hipLaunchKernelGGL(k_rows_resident, dim3(res_wg), dim3(RES_THREADS), ldsr, s, rs);
+        at.res_launched = true;
+        ++qp->resident_launches;
+        OG_HIP(hipGetLastError());
+        OG_TRY(fetch_status(qp, at, true));
+        // the flags before the phase: workgroup 0 may have written back a phase >= 2 while another workgroup gave up a
+        // wait (or a wait gave up earlier in this attempt: the loop ran on garbage)
+        OG_RUN(give_up_if_wait_lost(qp, at));
+        if (at.hst.phase >= 2) break;
+        // a workgroup of the resident launch was not there to answer: nothing was written back; the attempt is run
+        // again with the forms that wait for nothing
+        if (at.hst.phase >= 0) return give_up(qp, at);
+        if (warm_launched > (long)at.nwarm + 64) {
+            OG_TRY(clear_mail(qp, at));
+            return fail(8, "og_qp_solve_dev: the warm start's removals made no progress (internal error)");
+        }
+        pairs = std::min(128, std::max(4, 4 * pairs));
+    }
+    // next time: as many pairs as this warm start's removals took, and a few (a pair that has nothing to do costs
+    // ~5 us, a second round trip to the host 50)
+    if (at.nwarm) qp->warm_pairs_hint = std::min(96, at.hst.warm_removals + 4);
+    qp->resident_changes += at.hst.iters;
+    return 0;
+}
+
+// The active-set loop as pairs of launches (k_rows_decide, the pass over the rows), a growing batch of them per look at
+// the state; the flags are looked at only when the loop made no progress
+int run_two_launch(og_qp_s* qp, QpAttempt& at, const RowsArgs& ra, const RowsApply& pass, size_t lds_decide) {
+    hipStream_t s = at.s;
+    int batch = debug_stages() ? 1 : 8;
+    long launched = 0;
+    static const bool timing = getenv("OGSQP_TIMING") != nullptr;
+    double t_front = 0.0, t_enqueue = 0.0, t_wait = 0.0;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    if (timing) {
+        const double t0 = now();
+        OG_HIP(hipStreamSynchronize(s));
+        t_front = now() - t0;
+    }
+    while (true) {
+        const double te = timing ? now() : 0.0;
+        for (int it = 0; it < batch; ++it) {
+            hipLaunchKernelGGL(k_rows_decide, dim3(ra.G1), dim3(ROWS_THREADS), lds_decide, s, ra);
+            launch_rows_apply(pass, ra, s);
+        }
+        launched += batch;
+        OG_HIP(hipGetLastError());
+        const double tw = timing ? now() : 0.0;
+        OG_TRY(fetch_status(qp, at, true, false));
+        if (timing) {
+            t_enqueue += tw - te;
+            t_wait += now() - tw;
+        }
+        if (at.hst.phase >= 2) {
+            if (timing)
+                fprintf(stderr, "[ogsqp timing] front end drained in %.3f ms; active set: %d changes, %ld pairs launched, "
+                                "enqueue %.3f ms, wait %.3f ms\n", 1e3 * t_front, at.hst.iters, launched, 1e3 * t_enqueue,
+                        1e3 * t_wait);
+            return 0;
+        }
+        // every pair of launches is one change (or the end of the warm start): the device's own limit ends the loop
+        if (launched > (long)at.ga.limit + at.nwarm + 64) {
+            // (a wait that gave up earlier in this attempt - sweep, chained solve - leaves garbage the active-set
+            // kernels cannot make progress on: that is a lost attempt, to be re-run with the forms that wait for
+            // nothing, not an internal error)
+            OG_TRY(fetch_status(qp, at, false));
+            OG_RUN(give_up_if_wait_lost(qp, at));
+            return fail(8, "og_qp_solve_dev: the active-set kernels made no progress (internal error)");
+        }
+        if (batch < 128) batch *= 2;
+    }
+}
+
+// The active-set method in rotated coordinates, one pass over the rows per change (ogsqp_rows.h), started from the
+// warm rows the sweep made triangular: u, y, the active list and at.hst at the end of the loop
+int active_set_rows(og_qp_s* qp, const QpForms& f, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int mg = at.mg, nq = at.nq, nr = at.nr, nwarm = at.nwarm, nrows = mg + nq;
+    RowsArgs ra;
+    ra.g = at.ga; ra.dots = qp->dots; ra.dvec = qp->dvec; ra.rvec = qp->rvec; ra.vvec = qp->csbuf; ra.slot = qp->d_slot;
+    ra.price = qp->price; ra.ratio = qp->ratio; ra.rec = qp->rec; ra.uval = qp->uval; ra.lost = qp->flag + 2;
+    ra.spin_limit = qp->spin_limit; ra.only_warm = 0;
+    ra.G1 = std::max(8, std::min(128, (qp->qcap + 15) / 16));
+    // a wavefront per row (2048 workgroups at most: k_rows_decide reads that many partial prices in one trip)
+    ra.G2 = std::max(1, std::min(2048, (nrows + 1 + ROWS_WAVES - 1) / ROWS_WAVES));
+    // the warm start's removals spread over the grid where the tile fits next to the three vectors (ogsqp_rows.h)
+    ra.warm_spread = (f.warm_spread && rows_lds_bytes(nr, qp->qcap) + rows_spread_lds_bytes(qp->qcap) <= LDS_LIMIT) ? 1 : 0;
+    const size_t lds_decide = rows_lds_bytes(nr, qp->qcap) + (ra.warm_spread ? rows_spread_lds_bytes(qp->qcap) : 0);
+    OG_STAGE("rows init");
+    hipLaunchKernelGGL(k_rows_init, dim3((mg + 2 * nq + at.n1 + 255) / 256 + 1), dim3(ROWS_THREADS), 0, s, ra, qp->diagL,
+                       (const int*)qp->d_warm, nwarm, qp->dthresh, qp->flag);
+    if (nwarm) {
+        hipLaunchKernelGGL(k_rows_mark, dim3((nwarm + 255) / 256), dim3(256), 0, s, ra, (const int*)qp->d_warm, nwarm);
+        hipLaunchKernelGGL(k_rows_invert, dim3(nwarm), dim3(ROWS_THREADS), (size_t)(nwarm + 1) * sizeof(double), s,
+                           ra, (const double*)qp->Tc, (const double*)qp->diagL);
+    }
+    const RowsApply pass = pick_rows_apply(f, nr);
+    launch_rows_apply(pass, ra, s);                            // values and pricing at y = 0
+    OG_HIP(hipGetLastError());
+    OG_STAGE("rows changes");
+    // the resident launch where the rows fit the chip's registers and the mailbox the handle was created with
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, qp->device);
+    const int res_len = std::max(nr, qp->qcap);
+    const int res_wg = (nrows + qp->qcap + RES_ROWS - 1) / RES_ROWS;
+    // (res_wg_alloc <= RES_MAX_WG: the workgroups the mailbox was sized for)
+    const bool resident = f.resident && !debug_stages() && res_len <= RES_MAX_LEN &&
+                          res_wg <= std::min(qp->res_wg_alloc, cus) && res_lds_bytes(nr, qp->qcap) <= LDS_LIMIT;
+    if (resident) OG_RUN(run_resident(qp, at, ra, pass, lds_decide, res_wg));
+    else OG_RUN(run_two_launch(qp, at, ra, pass, lds_decide));
+    if (debug_stages()) OG_TRY(fetch_status(qp, at, false));
+    return 0;
+}
+
+// The two older active-set kernels (OGSQP_GI=single|coop|old) - the whole loop in one cooperative launch, or a launch of
+// one workgroup per change - and a subproblem without a null space (nr == 0), whatever the mode: at.hst at the end
+int active_set_old(og_qp_s* qp, const QpForms& f, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int mg = at.mg, nq = at.nq, nr = at.nr;
+    const GiArgs& ga = at.ga;
+    const dim3 init_grid((mg + 2 * nq + at.n1 + 255) / 256);
+    if (f.gi_mode != 0) {
+        OG_STAGE("gi init");
+        hipLaunchKernelGGL(k_gi_init, init_grid, dim3(256), 0, s, ga, qp->flag);
+        OG_HIP(hipGetLastError());
+    }
+    if (debug_stages()) OG_TRY(fetch_status(qp, at, false));
+    if (nr <= 0) {
+        hipLaunchKernelGGL(k_gi_init, init_grid, dim3(256), 0, s, ga, qp->flag);
+        OG_TRY(fetch_status(qp, at, true, false));
+        if (at.hst.phase < 2) at.hst.phase = 2;   // nothing to move: feasibility was settled by k_ldp_setup
+        return 0;
+    }
+    const int coop_width = nr <= 1024 ? 16 : 64;
+    // workgroups beyond the ceil(nr / width) that own a slice only take part in the pricing
+    const int coop_slices = (nr + coop_width - 1) / coop_width;
+    // as many as it takes to bring the pricing (all of W, every change) down to ~256 KB per workgroup,
+    // between 64 and one per CU
+    const size_t pricing_bytes = (size_t)(mg + nq) * (size_t)nr * sizeof(double);
+    const int coop_G = std::max(coop_slices, (int)std::min<size_t>(256, std::max<size_t>(64, pricing_bytes / (256 * 1024))));
+    const size_t coop_lds = (size_t)(4 * qp->qcap + 2 * coop_width + 2 * nr + COOP_THREADS) * sizeof(double) +
+                            (size_t)3 * qp->qcap * sizeof(int) + (size_t)((mg + 2 * nq + 31) / 32 + 1) * sizeof(unsigned) + 64;
+    // measured (tests/perf/solve_timing.py, OGSQP_GI=single|coop): per active-set change the cooperative kernel
+    // wins from C2's size on (C3: 40 vs 72 us; the first 25 major iterations of C3, 300-400 changes per
+    // subproblem, take 0.49 instead of 0.67 s), but its launch costs 0.15-0.3 ms more than the first batch of
+    // single-workgroup launches and late in a solve a subproblem moves a handful of rows: over whole solves the
+    // time per subproblem is the same within 4 % below 512 free directions (C2 1.60 / 1.77, C3' 1.50 / 1.65, C3
+    // 7.96 / 8.28 ms, single / cooperative).  The single-workgroup kernel is also the one whose sums run in the
+    // restatement's order (with exact Jacobians it walks SciPy's path iteration for iteration), so it stays the
+    // default there; from 512 on (C4, C5) the cooperative kernel is 1.5-3x faster per subproblem.
+    // Between 256 and 512 free directions the choice follows the previous subproblem: early in a solve (or after a
+    // restart) hundreds of rows move per subproblem and the cooperative kernel's 40 us per change beat the 72-83 us
+    // of single launches; later a handful move and the single-workgroup kernel's cheaper start wins.
+    const bool use_coop = qp->coop_mode == 2 ||
+                          (qp->coop_mode == 1 && (nr >= 512 || (nr >= 256 && qp->last_iters > 96)));
+    if (use_coop && coop_slices <= 64 && coop_lds <= LDS_LIMIT) {
+        // the whole active-set loop in one cooperative launch
+        CoopArgs ca;
+        ca.g = ga; ca.g.Q1t = nullptr; ca.G = coop_G; ca.nslices = coop_slices; ca.width = coop_width;
+        ca.astride = qp->qcap + 8; ca.Q1s = qp->Q1t; ca.RIr = qp->RI[0]; ca.apart = qp->apart; ca.zg = qp->zg;
+        ca.rg = qp->uact; ca.cs = qp->csbuf; ca.cpart = qp->cpart; ca.bar = qp->bar; ca.abort_flag = qp->abort_flag;
+        OG_HIP(hipMemsetAsync(qp->bar, 0, sizeof(unsigned), s));
+        OG_HIP(hipMemsetAsync(qp->abort_flag, 0, sizeof(int), s));
+        void* kargs[] = {(void*)&ca};
+        OG_STAGE("gi cooperative");
+        if (hipLaunchCooperativeKernel((const void*)k_gi_coop, dim3(coop_G), dim3(COOP_THREADS), kargs,
+                                       (unsigned)coop_lds, s) == hipSuccess) {
+            int habort = 0;
+            OG_HIP(hipMemcpyAsync(&habort, qp->abort_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+            OG_TRY(fetch_status(qp, at, true, false));
+            trace_cooperative(at.hst, coop_G);
+            if (habort) {
+                OG_TRY(fetch_status(qp, at, false));
+                OG_RUN(give_up_if_wait_lost(qp, at));   // (the input of the loop came from a lost wait)
+                return fail(7, "og_qp_solve_dev: the cooperative active-set kernel lost a workgroup at a barrier");
+            }
+            return 0;
+        }
+        // the runtime cannot keep 64 workgroups of this size resident: the one-workgroup kernel below does the same job
+        // (both run on the GPU; nothing leaves it)
+        (void)hipGetLastError();
+        qp->coop_mode = 0;
+    }
+    const int blocks = (mg + nq + GI_WAVES - 1) / GI_WAVES;
+    const size_t lds = gi_lds_bytes(nr, qp->qcap);
+    OG_STAGE("gi iterations");
+    for (int batch = debug_stages() ? 1 : 8; ; batch = std::min(64, 2 * batch)) {
+        for (int it = 0; it < batch; ++it)
+            hipLaunchKernelGGL(k_gi_iter, dim3(blocks), dim3(GI_THREADS), lds, s, ga);
+        OG_HIP(hipGetLastError());
+        OG_TRY(fetch_status(qp, at, true, false));
+        if (at.hst.phase >= 2) return 0;
+    }
+}
+
+// What the loop came to: the count of changes reported and remembered; the attempt is over unless it ended at a solution
+int active_set_verdict(og_qp_s* qp, const QpForms& f, const QpCall& in, QpAttempt& at) {
+    const GiState& hst = at.hst;
+    if (in.iterations) *in.iterations = hst.iters;
+    qp->last_iters = hst.iters;
+    if (debug_stages())
+        fprintf(stderr, "[ogsqp] LDP finished: phase %d after %d iterations, %d active, unfixable-row flag %d\n",
+                hst.phase, hst.iters, hst.q, at.hflag[1]);
+    trace_active_set(hst, f.gi_mode == 0, f.gi_mode == 0 && qp->resident_launches > 0);
+    if (hst.dbg != 0) fprintf(stderr, "[ogsqp] internal check failed: code %d aux %d (q %d, p %d)\n", hst.dbg, hst.dbg2, hst.q, hst.p);
+    if (hst.phase == 2) return 0;
+    // (a phase that came from a lost wait is no verdict on the subproblem: the attempt is run again)
+    OG_TRY(fetch_status(qp, at, false));
+    OG_RUN(give_up_if_wait_lost(qp, at));
+    *in.status = hst.phase == 3 ? OG_QP_ITERATION_LIMIT : OG_QP_INCOMPATIBLE;
+    at.over = true;
+    return 0;
+}
+
+// Step and multipliers, in the caller's arrays: d = clip(deq + Y y), the bounds' and the inequalities' multipliers, those
+// of the equalities from L' lam = ...; the last look at the flags (the transposed chained solve ran after the first)
+int finish_step(og_qp_s* qp, const QpForms& f, const QpCall& in, QpAttempt& at) {
+    hipStream_t s = at.s;
+    const int meq = at.meq, mg = at.mg, nq = at.nq, nr = at.nr, ldw = at.ldw;
+    OG_STAGE("finish");
+    hipLaunchKernelGGL(k_finish_step, dim3((nq + 3) / 4), dim3(256), 0, s, qp->Jw, ldw, meq, nq, nr, mg, qp->y, qp->deq,
+                       qp->dl, qp->du, qp->u, qp->d, qp->bm);
+    hipLaunchKernelGGL(k_dual_residual, dim3((nq + 3) / 4), dim3(256), 0, s, at.A, meq, mg, nq, qp->g, qp->u, qp->bm,
+                       qp->tvec);
+    if (meq) {
+        hipLaunchKernelGGL(k_gemv_cols, dim3((meq + 63) / 64), dim3(1024), 0, s, qp->Jw, (long)ldw, nq, meq, qp->tvec,
+                           qp->w1, qp->rhs);
+        launch_trsv(qp, f, ldw, meq, 1, 1.0, qp->rhs, qp->lam, s);
+    }
+    OG_HIP(hipGetLastError());
+    OG_HIP(hipMemcpyAsync(in.d, qp->d, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
+    OG_HIP(hipMemcpyAsync(in.bound_mult, qp->bm, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
+    if (meq) OG_HIP(hipMemcpyAsync(in.mult, qp->lam, sizeof(double) * meq, hipMemcpyDeviceToHost, s));
+    if (mg) OG_HIP(hipMemcpyAsync(in.mult + meq, qp->u, sizeof(double) * mg, hipMemcpyDeviceToHost, s));
+    OG_TRY(fetch_status(qp, at, false));
+    return give_up_if_wait_lost(qp, at);
+}
+
+// qp->warm: the rows active at this solution, in the numbering of og_qp_get_active - where the next subproblem starts;
+// qp->warm_use: whether it is to
+int remember_active_rows(og_qp_s* qp, const QpAttempt& at) {
+    const int mg = at.mg, nq = at.nq, q = at.hst.q;
+    std::vector<int> act((size_t)std::max(q, 1));
+    if (q > 0) OG_HIP(hipMemcpy(act.data(), qp->act, sizeof(int) * q, hipMemcpyDeviceToHost));
+    std::vector<int> before(qp->warm);
+    qp->warm.clear();
+    for (int j = 0; j < q; ++j) {
+        const int c = act[j];                                  // (a general row, a lower bound, an upper bound)
+        qp->warm.push_back(c < mg ? c : c < mg + nq ? mg + 2 * (c - mg) : mg + 2 * (c - mg - nq) + 1);
+    }
+    // warm-start the next solve only if this solution kept most of the previous one's rows
+    std::vector<int> now(qp->warm);
+    std::sort(now.begin(), now.end());
+    std::sort(before.begin(), before.end());
+    std::vector<int> common;
+    std::set_intersection(now.begin(), now.end(), before.begin(), before.end(), std::back_inserter(common));
+    const size_t larger = std::max(now.size(), before.size());
+    qp->warm_use = before.empty() || 10 * common.size() >= 7 * larger;
+    return 0;
+}
+
+// One attempt at the subproblem with the launch forms f: its stages, top to bottom, each unless an earlier one ended
+// the attempt.  *lost = true (and nothing of the handle's state changed: the factor, the warm-start list) when an
+// inter-workgroup wait gave up.
+int qp_solve_attempt(og_qp_s* qp, const QpForms& f, const QpCall& in, bool* lost) {
+    *lost = false;
+    if (!qp || !in.d_jt || !in.g || !in.dl || !in.du || !in.d || !in.mult || !in.bound_mult || !in.status)
+        return fail(2, "og_qp_solve_dev: null argument");
+    if (qp->m > 0 && !in.c) return fail(2, "og_qp_solve_dev: null constraint values");
+    if (in.ld < 1 + qp->m) return fail(2, "og_qp_solve_dev: leading dimension smaller than 1 + m");
+    if (in.augmented && !(in.rho > 0.0)) return fail(2, "og_qp_solve_dev: rho must be positive");
+    OG_HIP(hipSetDevice(qp->device));
+    if (in.hip_stream) OG_HIP(hipStreamSynchronize((hipStream_t)in.hip_stream));   // producer of d_jt
+    QpAttempt at;
+    at.s = qp->stream, at.lost = lost;
+    at.n = qp->n, at.n1 = qp->n1, at.ldw = qp->ldw, at.meq = qp->meq, at.mg = qp->mg, at.m = qp->m;
+    at.nq = in.augmented ? at.n + 1 : at.n, at.nr = at.nq - at.meq;
+    at.A = AView{in.d_jt, (long)in.ld, qp->extra, at.n};
+    if (in.iterations) *in.iterations = 0;
+    if (at.meq > at.nq) {
+        *in.status = OG_QP_TOO_MANY_EQ;
+        return 0;
+    }
+    OG_RUN(upload_inputs(qp, in, at));
+    OG_RUN(warm_rows(qp, f, at));
+    OG_RUN(lq_sweep(qp, f, at));
+    OG_RUN(equality_minimiser(qp, f, in, at));
+    OG_RUN(ldp_setup(qp, at));
+    if (f.gi_mode == 0 && at.nr > 0) OG_RUN(active_set_rows(qp, f, at));
+    else OG_RUN(active_set_old(qp, f, at));
+    OG_RUN(active_set_verdict(qp, f, in, at));
+    OG_RUN(finish_step(qp, f, in, at));
+    if (f.gi_mode == 0 && at.nr > 0) OG_RUN(remember_active_rows(qp, at));
+    if (!in.augmented) std::swap(qp->Z, qp->Jw);   // Z Q: same B, what og_qp_bfgs updates next
+    *in.status = OG_QP_SOLVED;
+    return 0;
+}
+
+// The wide sweep's buffers, mailbox and - with f.wide_ahead - the two side streams and their events
+int setup_wide(og_qp_s* qp, const QpForms& f) {
+    const size_t n1 = qp->n1, ldw = qp->ldw, qc = qp->qcap;
+    int rc = 0;
+    auto A = [&](auto** p, size_t cnt) { if (!rc) rc = dev_alloc(qp, p, cnt); };
+    const size_t vrows = ((size_t)qp->meq + qc + LQW_BLOCK - 1) / LQW_BLOCK * LQW_BLOCK + LQW_BLOCK;
+    A(&qp->Vall, vrows * ldw); A(&qp->panelw, 1); A(&qp->wide_mail, 1); A(&qp->wide_count, 4);
+    A(&qp->wy_w, 2 * (n1 + vrows) * LQW_BLOCK); A(&qp->wy_m, (size_t)LQW_BLOCK * LQW_BLOCK);
+    const size_t nblocks = vrows / LQW_BLOCK + 1;
+    A(&qp->wy_t, nblocks * LQW_BLOCK * LQW_BLOCK);
+    qp->wy_part_cap = std::max((size_t)WYW_SPLIT_MAX * 2 * LQW_BLOCK * LQW_BLOCK, 4 * (n1 + vrows) * LQW_BLOCK);
+    A(&qp->wy_part, qp->wy_part_cap);
+    A(&qp->wy_small, (size_t)2 * LQ16 * LQW_BLOCK);
+    if (!rc && (hipMemset(qp->wide_count, 0, 4 * sizeof(unsigned)) != hipSuccess ||
+                hipMemset(qp->Vall, 0, vrows * ldw * sizeof(double)) != hipSuccess))
+        rc = fail(5, "og_qp_create: hipMemset failed");
+    if (!rc) {
+        const int cells = (int)(sizeof(LqWideMail) / sizeof(double));
+        hipLaunchKernelGGL(k_lq_wide_arm, dim3((cells + 255) / 256), dim3(256), 0, 0, qp->wide_mail);
+        if (hipDeviceSynchronize() != hipSuccess) rc = fail(5, "og_qp_create: arming the panel mailbox failed");
+    }
+    if (rc || !f.wide_ahead) return rc;
+    for (int l = 1; l < 3 && !rc; ++l) {
+        og_qp_s::WyLane& ln = qp->lane[l];
+        A(&ln.w, 2 * (n1 + vrows) * LQW_BLOCK);
+        A(&ln.part, qp->wy_part_cap);
+        if (!rc && hipStreamCreateWithFlags(&ln.s, hipStreamNonBlocking) != hipSuccess)
+            rc = fail(5, "og_qp_create: hipStreamCreate failed");
+        if (!rc && hipEventCreateWithFlags(&qp->ev_join[l - 1], hipEventDisableTiming) != hipSuccess)
+            rc = fail(5, "og_qp_create: hipEventCreate failed");
+    }
+    qp->ev_t.assign(nblocks, nullptr);
+    qp->ev_tc.assign(nblocks, nullptr);
+    for (size_t e = 0; e < nblocks && !rc; ++e)
+        if (hipEventCreateWithFlags(&qp->ev_t[e], hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&qp->ev_tc[e], hipEventDisableTiming) != hipSuccess)
+            rc = fail(5, "og_qp_create: hipEventCreate failed");
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2730,14 +3547,9 @@ int og_qp_create(int32_t abi_version, int32_t device, int32_t n, int32_t m_eq, i
     OG_HIP(hipSetDevice(device));
     og_qp_s* qp = new og_qp_s();
     qp->device = device;
-    qp->n = n;
-    qp->n1 = n + 1;
-    qp->ldw = (n + 1 + 15) / 16 * 16;
-    qp->meq = m_eq;
-    qp->mg = m_ineq;
-    qp->m = m_eq + m_ineq;
-    qp->qcap = qp->n1 - (m_eq < qp->n1 ? m_eq : qp->n1);
-    if (qp->qcap < 1) qp->qcap = 1;
+    qp->n = n, qp->n1 = n + 1, qp->ldw = (n + 1 + 15) / 16 * 16;
+    qp->meq = m_eq, qp->mg = m_ineq, qp->m = m_eq + m_ineq;
+    qp->qcap = std::max(1, qp->n1 - std::min(m_eq, qp->n1));
     const size_t n1 = qp->n1, ldw = qp->ldw, mt = (size_t)qp->mg + 2 * n1, qc = qp->qcap;
     if (rows_lds_bytes((int)qc, (int)qc) > LDS_LIMIT) {
         delete qp;
@@ -2753,15 +3565,26 @@ int og_qp_create(int32_t abi_version, int32_t device, int32_t n, int32_t m_eq, i
     const bool beyond_fallback = n1 > (size_t)LQ_PT_MAX * LQ_CPT_MAX;
     int rc = 0;
     auto A = [&](auto** p, size_t cnt) { if (!rc) rc = dev_alloc(qp, p, cnt); };
-    // Tc and diagL: the equalities, then the rows of a warm start (at most qcap of them) behind them in the sweep
+    // the factor, its work copy, the sweep (Tc, diagL: the equalities, then the at most qcap rows of a warm start)
     A(&qp->Z, n1 * ldw); A(&qp->Jw, n1 * ldw); A(&qp->Tc, ((size_t)qp->meq + qc) * ldw); A(&qp->GJ, (size_t)qp->mg * ldw);
-    A(&qp->diagL, qp->meq + qc); A(&qp->dots, (size_t)qp->mg + n1); A(&qp->dvec, n1); A(&qp->rvec, qc);
+    A(&qp->diagL, qp->meq + qc);
+    A(&qp->dots, (size_t)qp->mg + n1); A(&qp->dvec, n1); A(&qp->rvec, qc);                      // the active set by rows
     A(&qp->price, 2048); A(&qp->ratio, 256); A(&qp->rec, 1); A(&qp->d_warm, qc); A(&qp->d_slot, qc); A(&qp->uval, qc);
-    A(&qp->V16, (size_t)LQ16 * ldw); A(&qp->panel16, 1); A(&qp->V16b, (size_t)LQ16 * ldw); A(&qp->panel16b, 1); A(&qp->lq_go, 4); A(&qp->lq_wpart, (size_t)LQ_HEADS * 64 * 4); A(&qp->trsv_work, qp->meq); A(&qp->gemm_map, ((size_t)std::max(qp->meq, qp->mg) + 63 + qc) / 64 * ((n1 + 15) / 16) + 64); A(&qp->Linv, ((size_t)qp->meq + 63) / 64 * 4096); A(&qp->has_gone, ((size_t)qp->meq + 63) / 64); A(&qp->Vp, (size_t)LQ_NB * ldw); A(&qp->panel, 1); A(&qp->extra, qp->m); A(&qp->g, n1); A(&qp->c, qp->m); A(&qp->dl, n1); A(&qp->du, n1);
+    A(&qp->V16, (size_t)LQ16 * ldw); A(&qp->panel16, 1); A(&qp->V16b, (size_t)LQ16 * ldw); A(&qp->panel16b, 1);   // sweep: 16
+    A(&qp->lq_go, 4); A(&qp->lq_wpart, (size_t)LQ_HEADS * 64 * 4);
+    A(&qp->trsv_work, qp->meq);                               // the triangular solves, the products with the Jacobian
+    A(&qp->gemm_map, ((size_t)std::max(qp->meq, qp->mg) + 63 + qc) / 64 * ((n1 + 15) / 16) + 64);
+    A(&qp->Linv, ((size_t)qp->meq + 63) / 64 * 4096); A(&qp->has_gone, ((size_t)qp->meq + 63) / 64);
+    A(&qp->Vp, (size_t)LQ_NB * ldw); A(&qp->panel, 1);        // sweep: 8 reflectors
+    // the inputs and the equality-constrained minimiser
+    A(&qp->extra, qp->m); A(&qp->g, n1); A(&qp->c, qp->m); A(&qp->dl, n1); A(&qp->du, n1);
     A(&qp->w1, qp->meq); A(&qp->t1, n1); A(&qp->xcat, n1); A(&qp->deq, n1); A(&qp->bG, qp->mg);
+    // the least-distance problem and the active set (every form)
     A(&qp->bval, mt); A(&qp->scale, mt); A(&qp->own, mt); A(&qp->u, mt); A(&qp->y, n1);
-    A(&qp->Q1t, qc * (qc + 64)); A(&qp->apart, 2 * 64 * (qc + 8)); A(&qp->uact, qc); A(&qp->zg, n1); A(&qp->dthresh, 4); A(&qp->csbuf, 2 * qc);
-    A(&qp->cpart, 256); A(&qp->bar, 1); A(&qp->abort_flag, 1); A(&qp->R[0], qc * qc); A(&qp->R[1], qc * qc); A(&qp->RI[0], qc * qc); A(&qp->RI[1], qc * qc);
+    A(&qp->Q1t, qc * (qc + 64)); A(&qp->apart, 2 * 64 * (qc + 8)); A(&qp->uact, qc); A(&qp->zg, n1); A(&qp->dthresh, 4);
+    A(&qp->csbuf, 2 * qc); A(&qp->cpart, 256); A(&qp->bar, 1); A(&qp->abort_flag, 1);
+    A(&qp->R[0], qc * qc); A(&qp->R[1], qc * qc); A(&qp->RI[0], qc * qc); A(&qp->RI[1], qc * qc);
+    // step, multipliers, the quasi-Newton update and og_jt_times
     A(&qp->d, n1); A(&qp->bm, n1); A(&qp->tvec, n1); A(&qp->rhs, qp->meq); A(&qp->lam, qp->meq); A(&qp->vz, n1);
     A(&qp->svec, n1); A(&qp->vvec, n1); A(&qp->coef, qp->m + 1); A(&qp->outn, n1);
     A(&qp->isact, mt); A(&qp->act, qc); A(&qp->flag, 4);
@@ -2780,130 +3603,39 @@ int og_qp_create(int32_t abi_version, int32_t device, int32_t n, int32_t m_eq, i
     A(&qp->partials, ((size_t)qp->mg + n1) / GI_WAVES + 2); A(&qp->st, 1);
     if (!rc && hipStreamCreate(&qp->stream) != hipSuccess) rc = fail(5, "og_qp_create: hipStreamCreate failed");
     if (!rc && hipMemset(qp->lq_go, 0, 4 * sizeof(unsigned)) != hipSuccess) rc = fail(5, "og_qp_create: hipMemset failed");
-    if (!rc && hipFuncSetAttribute((const void*)k_gi_iter, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)LDS_LIMIT) != hipSuccess)
-        rc = fail(5, "og_qp_create: cannot raise the dynamic LDS limit");
-    if (!rc && hipFuncSetAttribute((const void*)k_gi_coop, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)LDS_LIMIT) != hipSuccess)
-        rc = fail(5, "og_qp_create: cannot raise the dynamic LDS limit");
-    if (!rc && hipFuncSetAttribute((const void*)k_trsv, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)LDS_LIMIT) != hipSuccess)
-        rc = fail(5, "og_qp_create: cannot raise the dynamic LDS limit");
-    if (!rc && (hipFuncSetAttribute((const void*)k_rows_decide, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_LIMIT) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k_rows_invert, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_LIMIT) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k_rows_resident, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_LIMIT) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k_rows_apply_stream<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_LIMIT) != hipSuccess ||
-                hipFuncSetAttribute((const void*)k_rows_apply_stream<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)LDS_LIMIT) != hipSuccess))
-        rc = fail(5, "og_qp_create: cannot raise the dynamic LDS limit");
-    {
-        const void* steps[13] = {(const void*)k_lq_step16<2, 1>, (const void*)k_lq_step16<2, 2>, (const void*)k_lq_step16<4, 1>,
-                                 (const void*)k_lq_step16<4, 2>, (const void*)k_lq_step16<8, 2>, (const void*)k_lq_step16<8, 3>,
-                                 (const void*)k_lq_step16<8, 4>, (const void*)k_lq_step16<12, 4>, (const void*)k_lq_step16<12, 5>,
-                                 (const void*)k_lq_step16<12, 6>, (const void*)k_lq_step16<16, 6>, (const void*)k_lq_step16<16, 7>,
-                                 (const void*)k_lq_step16<16, 8>};
-        for (const void* f : steps) {
-            const hipError_t e = rc ? hipSuccess : hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess)
-                rc = fail(5, std::string("og_qp_create: cannot raise the dynamic LDS limit of the look-ahead kernel: ") +
-                                 hipGetErrorString(e));
-        }
+    for (const void* kernel : BIG_LDS)
+        if (!rc && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT) != hipSuccess)
+            rc = fail(5, "og_qp_create: cannot raise the dynamic LDS limit");
+    for (const Step16& step : STEP16) {
+        const hipError_t e = rc ? hipSuccess : hipFuncSetAttribute((const void*)step.kernel,
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+        if (e != hipSuccess)
+            rc = fail(5, std::string("og_qp_create: cannot raise the dynamic LDS limit of the look-ahead kernel: ") +
+                             hipGetErrorString(e));
     }
+    qp->forms = forms_from_env(n1, (int)qc);
+    // rows longer than one workgroup holds: the wide sweep (ogsqp_lqwide.h)
+    if (!rc && qp->forms.lq_wide) rc = setup_wide(qp, qp->forms);
     if (rc) {
         og_qp_destroy(qp);
         return rc;
     }
-    {
-        int can = 0;
-        (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCooperativeLaunch, device);
-        // OGSQP_GI = "single": one-workgroup active-set update (k_gi_iter), "coop": the cooperative
-        // multi-workgroup one (k_gi_coop); default: by size (the barriers of the cooperative kernel cost
-        // 12 us per change, its bandwidth pays from a null space of about 500 on)
-        const char* mode = getenv("OGSQP_GI");
-        qp->coop_mode = !can ? 0 : (mode && std::string(mode) == "single") ? 0 : (mode && std::string(mode) == "coop") ? 2 : 1;
-        // the default is the row-parallel method in rotated coordinates (ogsqp_rows.h); "single" / "coop" / "old"
-        // select the two older kernels (kept for comparison; they need their own, smaller, LDS budget)
-        qp->gi_mode = (mode && (std::string(mode) == "single" || std::string(mode) == "coop" || std::string(mode) == "old")) ? 1 : 0;
-        if (qp->gi_mode == 1 && gi_lds_bytes((int)qc, (int)qc) > LDS_LIMIT) qp->gi_mode = 0;
-        const char* resk = getenv("OGSQP_RESIDENT");
-        qp->resident = !(resk && std::string(resk) == "0");
-        const char* rowsk = getenv("OGSQP_ROWS");
-        qp->rows_stream = !(rowsk && std::string(rowsk) == "reg");
-        qp->rows_r4 = (rowsk && std::string(rowsk) == "r4") ? 1 : (rowsk && std::string(rowsk) == "lds") ? -1 : 0;
-        qp->rows_stage = (rowsk && std::string(rowsk) == "stage") ? 1 : (rowsk && std::string(rowsk) == "nostage") ? -1 : 0;
-        const char* lq = getenv("OGSQP_LQ");
-        qp->lq16 = !(lq && std::string(lq) == "8");
-        qp->lq_ahead = !(lq && std::string(lq) == "16");
-        const char* tr = getenv("OGSQP_TRSV");
-        qp->trsv_mode = (tr && std::string(tr) == "block") ? 1 : (tr && std::string(tr) == "single") ? 2 : 0;
-        // rows longer than one workgroup holds: the wide sweep (ogsqp_lqwide.h) when the default kernels are selected
-        // (OGSQP_WIDE=0: round 2's 8-reflector kernels serve those rows, as before round 4)
-        const char* wide = getenv("OGSQP_WIDE");
-        if (qp->lq16 && qp->lq_ahead && n1 > (size_t)LQW_SLAB && n1 <= (size_t)LQW_SLAB * LQW_MAX &&
-            !(wide && std::string(wide) == "0")) {
-            const size_t vrows = ((size_t)qp->meq + qc + LQW_BLOCK - 1) / LQW_BLOCK * LQW_BLOCK + LQW_BLOCK;
-            A(&qp->Vall, vrows * ldw); A(&qp->panelw, 1); A(&qp->wide_mail, 1); A(&qp->wide_count, 4);
-            A(&qp->wy_w, 2 * (n1 + vrows) * LQW_BLOCK); A(&qp->wy_m, (size_t)LQW_BLOCK * LQW_BLOCK);
-            const size_t nblocks = vrows / LQW_BLOCK + 1;
-            A(&qp->wy_t, nblocks * LQW_BLOCK * LQW_BLOCK);
-            qp->wy_part_cap = std::max((size_t)WYW_SPLIT_MAX * 2 * LQW_BLOCK * LQW_BLOCK, 4 * (n1 + vrows) * LQW_BLOCK);
-            A(&qp->wy_part, qp->wy_part_cap);
-            A(&qp->wy_small, (size_t)2 * LQ16 * LQW_BLOCK);
-            if (!rc && hipMemset(qp->wide_count, 0, 4 * sizeof(unsigned)) != hipSuccess)
-                rc = fail(5, "og_qp_create: hipMemset failed");
-            const char* inblock = getenv("OGSQP_WIDE_INBLOCK");
-            qp->wide_inblock = inblock && std::string(inblock) == "1";
-            if (!rc && hipMemset(qp->Vall, 0, vrows * ldw * sizeof(double)) != hipSuccess)
-                rc = fail(5, "og_qp_create: hipMemset failed");
-            if (!rc) {
-                const int cells = (int)(sizeof(LqWideMail) / sizeof(double));
-                hipLaunchKernelGGL(k_lq_wide_arm, dim3((cells + 255) / 256), dim3(256), 0, 0, qp->wide_mail);
-                if (hipDeviceSynchronize() != hipSuccess) rc = fail(5, "og_qp_create: arming the panel mailbox failed");
-            }
-            const char* wahead = getenv("OGSQP_WIDE_AHEAD");
-            if (!rc && !(wahead && std::string(wahead) == "0")) {
-                for (int l = 1; l < 3 && !rc; ++l) {
-                    og_qp_s::WyLane& ln = qp->lane[l];
-                    A(&ln.w, 2 * (n1 + vrows) * LQW_BLOCK);
-                    A(&ln.part, qp->wy_part_cap);
-                    if (!rc && hipStreamCreateWithFlags(&ln.s, hipStreamNonBlocking) != hipSuccess)
-                        rc = fail(5, "og_qp_create: hipStreamCreate failed");
-                    if (!rc && hipEventCreateWithFlags(&qp->ev_join[l - 1], hipEventDisableTiming) != hipSuccess)
-                        rc = fail(5, "og_qp_create: hipEventCreate failed");
-                }
-                qp->ev_t.assign(nblocks, nullptr);
-                qp->ev_tc.assign(nblocks, nullptr);
-                for (size_t e = 0; e < nblocks && !rc; ++e)
-                    if (hipEventCreateWithFlags(&qp->ev_t[e], hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&qp->ev_tc[e], hipEventDisableTiming) != hipSuccess)
-                        rc = fail(5, "og_qp_create: hipEventCreate failed");
-                qp->wide_ahead = !rc;
-            }
-            if (rc) {
-                og_qp_destroy(qp);
-                return rc;
-            }
-            qp->lq_wide = true;
-        }
-        if (beyond_fallback && !qp->lq_wide) {
-            og_qp_destroy(qp);
-            return fail(4, "og_qp_create: rows of more than " + std::to_string(LQ_PT_MAX * LQ_CPT_MAX) +
-                               " entries need the wide sweep (OGSQP_LQ / OGSQP_WIDE must not turn it off)");
-        }
-        // (beyond 8192 variables a lost wait cannot fall back to a form without one: the long bound of rounds 3-4 there)
-        if (beyond_fallback) qp->spin_limit = 1 << 25;
-        const char* spin = getenv("OGSQP_SPIN_LIMIT");
-        if (spin && atoi(spin) > 0) qp->spin_limit = atoi(spin);
-        qp->spin_default = qp->spin_limit;
-        const char* wspread = getenv("OGSQP_WARM_SPREAD");
-        qp->warm_spread = !(wspread && std::string(wspread) == "0");
-        const char* warm = getenv("OGSQP_WARM");
-        qp->warm_enabled = !(warm && std::string(warm) == "0");
+    if (beyond_fallback && !qp->forms.lq_wide) {
+        og_qp_destroy(qp);
+        return fail(4, "og_qp_create: rows of more than " + std::to_string(LQ_PT_MAX * LQ_CPT_MAX) +
+                           " entries need the wide sweep (OGSQP_LQ / OGSQP_WIDE must not turn it off)");
     }
+    int can = 0;
+    (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCooperativeLaunch, device);
+    // OGSQP_GI = "single": one-workgroup active-set update (k_gi_iter), "coop": the cooperative multi-workgroup one
+    // (k_gi_coop); otherwise by size (the barriers of the cooperative kernel cost 12 us per change, its bandwidth
+    // pays from a null space of about 500 on)
+    qp->coop_mode = !can || env_is("OGSQP_GI", "single") ? 0 : env_is("OGSQP_GI", "coop") ? 2 : 1;
+    // (beyond 8192 variables a lost wait cannot fall back to a form without one: the long bound of rounds 3-4 there)
+    if (beyond_fallback) qp->spin_limit = 1 << 25;
+    const char* spin = getenv("OGSQP_SPIN_LIMIT");
+    if (spin && atoi(spin) > 0) qp->spin_limit = atoi(spin);
+    qp->spin_default = qp->spin_limit;
     *out = qp;
     return og_qp_reset(qp);
 }
@@ -2949,647 +3681,12 @@ int og_qp_set_factor(og_qp_handle qp, const double* Z) {
     return 0;
 }
 
-// One attempt at the subproblem.  *lost = 1 (and nothing of the handle's state changed: the factor, the warm-start
-// list) when an inter-workgroup wait of the look-ahead sweep or of the chained triangular solves gave up.
-static int qp_solve_attempt(og_qp_handle qp, const double* d_jt, int64_t ld, const double* g, const double* c,
-                            const double* dl, const double* du, int32_t augmented, double rho, double* d, double* mult,
-                            double* bound_mult, int32_t* status, int32_t* iterations, void* hip_stream, int* lost) {
-    if (!qp || !d_jt || !g || !dl || !du || !d || !mult || !bound_mult || !status)
-        return fail(2, "og_qp_solve_dev: null argument");
-    if (qp->m > 0 && !c) return fail(2, "og_qp_solve_dev: null constraint values");
-    if (ld < 1 + qp->m) return fail(2, "og_qp_solve_dev: leading dimension smaller than 1 + m");
-    if (augmented && !(rho > 0.0)) return fail(2, "og_qp_solve_dev: rho must be positive");
-    OG_HIP(hipSetDevice(qp->device));
-    hipStream_t s = qp->stream;
-    if (hip_stream) OG_HIP(hipStreamSynchronize((hipStream_t)hip_stream));   // producer of d_jt
-    const int n = qp->n, n1 = qp->n1, ldw = qp->ldw, meq = qp->meq, mg = qp->mg, m = qp->m;
-    const int nq = augmented ? n + 1 : n;
-    const int nr = nq - meq;
-    if (iterations) *iterations = 0;
-    if (meq > nq) {
-        *status = OG_QP_TOO_MANY_EQ;
-        return 0;
-    }
-    // ---- inputs
-    std::vector<double>& hs = qp->host_stage;
-    hs.assign((size_t)3 * n1 + m, 0.0);
-    double* hg = hs.data();
-    double* hdl = hg + n1;
-    double* hdu = hdl + n1;
-    double* hc = hdu + n1;
-    memcpy(hg, g, sizeof(double) * n);
-    memcpy(hdl, dl, sizeof(double) * nq);
-    memcpy(hdu, du, sizeof(double) * nq);
-    if (m) memcpy(hc, c, sizeof(double) * m);
-    OG_HIP(hipMemcpyAsync(qp->g, hg, sizeof(double) * n1, hipMemcpyHostToDevice, s));
-    OG_HIP(hipMemcpyAsync(qp->dl, hdl, sizeof(double) * n1, hipMemcpyHostToDevice, s));
-    OG_HIP(hipMemcpyAsync(qp->du, hdu, sizeof(double) * n1, hipMemcpyHostToDevice, s));
-    if (m) OG_HIP(hipMemcpyAsync(qp->c, hc, sizeof(double) * m, hipMemcpyHostToDevice, s));
-    OG_HIP(hipMemsetAsync(qp->flag, 0, 4 * sizeof(int), s));     // [2]: a look-ahead workgroup of the LQ sweep gave up waiting
-    if (augmented && m)
-        hipLaunchKernelGGL(k_relaxation_row, dim3((m + 255) / 256), dim3(256), 0, s, qp->c, meq, m, qp->extra);
-    AView A{d_jt, (long)ld, qp->extra, n};
-    // ---- work factor, C Z, LQ sweep
-    OG_STAGE("copy_factor");
-    hipLaunchKernelGGL(k_copy_factor, dim3((nq + 255) / 256, nq), dim3(256), 0, s, qp->Z, qp->Jw, ldw, n, nq,
-                       augmented ? 1.0 / rho : 0.0);
-    // ---- rows of a warm start: active at the solution of the previous subproblem, appended to the sweep
-    int nwarm = 0;
-    if (qp->gi_mode == 0 && qp->warm_enabled && qp->warm_use && nr > 0 && !qp->warm.empty()) {
-        std::vector<int> general, bound;
-        for (int id : qp->warm) {
-            if (id < mg) {
-                general.push_back(id);
-            } else {
-                const int i = (id - mg) >> 1, upper = (id - mg) & 1;
-                if (i < nq) bound.push_back(mg + (upper ? nq : 0) + i);
-            }
-        }
-        std::vector<int> ids(general);
-        ids.insert(ids.end(), bound.begin(), bound.end());
-        if ((int)ids.size() > nr) ids.resize(nr);
-        nwarm = (int)ids.size();
-        const int ng = std::min((int)general.size(), nwarm);
-        if (nwarm) {
-            OG_HIP(hipMemcpyAsync(qp->d_warm, ids.data(), sizeof(int) * nwarm, hipMemcpyHostToDevice, s));
-            OG_HIP(hipStreamSynchronize(s));                   // ids is a local
-            double* Text = qp->Tc + (size_t)meq * ldw;
-            OG_STAGE("warm rows");
-            if (ng)
-                OG_TRY(launch_gemm(qp, A, meq, ng, nq, ldw, Text, (const int*)qp->d_warm, s));
-            if (nwarm > ng)
-                hipLaunchKernelGGL(k_rows_gather_bounds, dim3((nq + 255) / 256, nwarm - ng), dim3(256), 0, s, qp->Jw, ldw,
-                                   nq, mg, (const int*)qp->d_warm, ng, nwarm, Text);
-        }
-    }
-    const int msweep = meq + nwarm;                            // rows the sweep makes triangular
-    if (msweep) {
-        OG_STAGE("gemm C Z");
-        if (meq)
-            OG_TRY(launch_gemm(qp, A, 0, meq, nq, ldw, qp->Tc, (const int*)nullptr, s));
-        OG_STAGE("lq sweep");
-        OG_HIP(hipMemsetAsync(qp->dthresh, 0, 2 * sizeof(double), s));
-        double* Vcur = qp->V16;
-        double* Vnxt = qp->V16b;
-        Lq16Panel* pcur = qp->panel16;
-        Lq16Panel* pnxt = qp->panel16b;
-        int factored = -1;                                  // the panel the previous launch factored on the side
-        OG_HIP(hipMemsetAsync(qp->lq_go, 0, 2 * sizeof(unsigned), s)); // counts of the head workgroups, this sweep
-        qp->lq_token = 0u;
-        int kstart = 0;
-        if (qp->lq_wide && nq > LQW_SLAB) {
-            // long rows: column-split panels and 64-reflector blocks until the rows fit one workgroup (ogsqp_lqwide.h)
-            OG_STAGE("lq sweep, wide blocks");
-            OG_TRY(lq_sweep_wide(qp, msweep, nq, ldw, 0, s, &kstart));
-        }
-        for (int k = kstart; k < msweep;) {
-            if (qp->lq16 && nq - k <= 2048 && k % LQ16 == 0) {
-                // 16 reflectors per trip: row-distributed panel kernel, MFMA trailing update (ogsqp_lq16.h)
-                const int nb16 = std::min(LQ16, msweep - k), len16 = nq - k;
-                const int nrows16 = (msweep - k - nb16) + nq;
- const int eg = (len16 + 255) / 256, ub = (len16 + 127) / 128;
-                // rows per workgroup of the trailing update: 16, or as few as fill the chip (not below 8: every
-                // workgroup reads all of V)
-                const int rpg = std::max(8, std::min(LQ16, (nrows16 + 239) / 240));
-#define OG_PANEL16(E)                                                                                              \
-    hipLaunchKernelGGL(k_lq_panel16<E>, dim3(1), dim3(P16_THREADS), (size_t)((E) <= 6 ? P16_RING : 2) * 256 * (E) * sizeof(double), s, qp->Tc, ldw, \
-                       msweep, nq, k, Vcur, ldw, qp->diagL, pcur, qp->dthresh + 1)
-                if (factored != k) {
-                    // (E = groups of 256 columns, exactly: the panel's steps are bound by the multiply-adds it issues,
-                    // padding included)
-                    switch (eg) {
-                        case 1: OG_PANEL16(1); break;
-                        case 2: OG_PANEL16(2); break;
-                        case 3: OG_PANEL16(3); break;
-                        case 4: OG_PANEL16(4); break;
-                        case 5: OG_PANEL16(5); break;
-                        case 6: OG_PANEL16(6); break;
-                        case 7: OG_PANEL16(7); break;
-                        default: OG_PANEL16(8); break;
-                    }
-                }
-#undef OG_PANEL16
-#ifdef OGSQP_TRACE
-                if ((k == 0 || k == 512) && factored != k) {
-                    Lq16Panel hp;
-                    OG_HIP(hipMemcpyAsync(&hp, pcur, sizeof(Lq16Panel), hipMemcpyDeviceToHost, s));
-                    OG_HIP(hipStreamSynchronize(s));
-                    fprintf(stderr, "[ogsqp trace] panel16 at k = %d (len %d) ticks (wavefront 0): load %lld first reflector %lld waits for the flag %lld vector %lld row in line %lld other row %lld store %lld\n",
-                            k, len16, hp.tr[0], hp.tr[5], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[6]);
-                }
-#endif
-#ifdef OGSQP_TRACE
-#define OG_APPLY16_TRACE()                                                                                               \
-    if (k == 0) {                                                                                                        \
-        long long tr[8];                                                                                                 \
-        OG_HIP(hipStreamSynchronize(s));                                                                                 \
-        OG_HIP(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_apply16_trace), sizeof tr));                                         \
-        fprintf(stderr, "[ogsqp trace] apply16 at k = 0 (len %d, %d rows per workgroup), 10 ns ticks: header %lld loads %lld " \
-                        "product-1 %lld barrier %lld products-2,3 %lld stores %lld\n", len16, rpg, tr[0], tr[1], tr[2],  \
-                tr[3], tr[4], tr[5]);                                                                                    \
-        if (qp->lq_ahead) {                                                                                              \
-            Lq16Panel hp;                                                                                                \
-            OG_HIP(hipMemcpyFromSymbol(tr, HIP_SYMBOL(g_head16_trace), sizeof tr));                                      \
-            OG_HIP(hipMemcpy(&hp, pnxt, sizeof(Lq16Panel), hipMemcpyDeviceToHost));                                      \
-            fprintf(stderr, "[ogsqp trace] head workgroup 0, 10 ns ticks: header %lld loads %lld product-1 %lld barrier %lld " \
-                            "exchange %lld products-2,3 + stores issued %lld drain %lld; its panel (shader clocks, wavefront 0): load %lld " \
-                            "first reflector %lld waits for the flag %lld vector %lld row in line %lld other row %lld store %lld\n", tr[0], tr[1],  \
-                    tr[2], tr[3], tr[6], tr[4], tr[5], hp.tr[0], hp.tr[5], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[6]); \
-        }                                                                                                                \
-    }
-#else
-#define OG_APPLY16_TRACE() do { } while (0)
-#endif
-                if (qp->lq_ahead && k + LQ16 < msweep) {
-                    // the launch of the trailing update factors the next panel on the side (k_lq_step16)
-#define OG_STEP16(U, E)                                                                                           \
-    hipLaunchKernelGGL((k_lq_step16<U, E>), dim3(1 + LQ_HEADS + (std::max(nrows16 - LQ16, 0) + rpg - 1) / rpg),        \
-                       dim3(64 * A16_WAVES), (size_t)((E) <= 6 ? P16_RING : 2) * 256 * (E) * sizeof(double), s, qp->Tc, qp->Jw, ldw, msweep, nq, k,   \
-                       (const double*)Vcur, ldw, (const Lq16Panel*)pcur, Vnxt, pnxt, qp->diagL, qp->dthresh + 1, rpg,      \
-                       qp->lq_go, (qp->lq_token += LQ_HEADS), qp->lq_wpart, qp->flag + 2, qp->spin_limit)
-                    // U by the length of the rows now, E by the length of the NEXT panel's rows (exact)
-                    const int en = (len16 - LQ16 + 255) / 256;
-                    if (ub <= 2) { if (en <= 1) OG_STEP16(2, 1); else OG_STEP16(2, 2); }
-                    else if (ub <= 4) { if (en <= 1) OG_STEP16(4, 1); else OG_STEP16(4, 2); }
-                    else if (ub <= 8) { if (en <= 2) OG_STEP16(8, 2); else if (en == 3) OG_STEP16(8, 3); else OG_STEP16(8, 4); }
-                    else if (ub <= 12) { if (en <= 4) OG_STEP16(12, 4); else if (en == 5) OG_STEP16(12, 5); else OG_STEP16(12, 6); }
-                    else { if (en <= 6) OG_STEP16(16, 6); else if (en == 7) OG_STEP16(16, 7); else OG_STEP16(16, 8); }
-#undef OG_STEP16
-                    OG_APPLY16_TRACE();
-                    factored = k + LQ16;
-                    std::swap(Vcur, Vnxt);
-                    std::swap(pcur, pnxt);
-                    k += LQ16;
-                    continue;
-                }
-#define OG_APPLY16(U)                                                                                            \
-    hipLaunchKernelGGL(k_lq_apply16<U>, dim3((nrows16 + rpg - 1) / rpg), dim3(64 * A16_WAVES), 0, s, qp->Tc, qp->Jw, ldw, msweep, \
-                       nq, k, (const double*)Vcur, ldw, (const Lq16Panel*)pcur, rpg)
-                if (ub <= 2) OG_APPLY16(2);
-                else if (ub <= 4) OG_APPLY16(4);
-                else if (ub <= 8) OG_APPLY16(8);
-                else if (ub <= 12) OG_APPLY16(12);
-                else OG_APPLY16(16);
-#undef OG_APPLY16
-                OG_APPLY16_TRACE();
-                k += LQ16;
-                continue;
-            }
-            const int nb = std::min(LQ_NB, msweep - k);
-            const int nrows = (msweep - k - nb) + nq;
-            const int len = nq - k;                                // length of the panel rows
-#define OG_PANEL(PT, CPT)                                                                                      \
-    hipLaunchKernelGGL((k_lq_panel<PT, CPT>), dim3(1), dim3(PT), 0, s, qp->Tc, ldw, msweep, nq, k, qp->Vp, qp->diagL, \
-                       qp->panel, qp->dthresh + 1)
-            if (len <= PANEL_SMALL_PT * 4) OG_PANEL(PANEL_SMALL_PT, 4);
-            else if (len <= PANEL_SMALL_PT * 8) OG_PANEL(PANEL_SMALL_PT, 8);
-            else if (len <= PANEL_SMALL_PT * 12) OG_PANEL(PANEL_SMALL_PT, 12);
-            else if (len <= LQ_PT_MAX * 4) OG_PANEL(LQ_PT_MAX, 4);
-            else if (len <= LQ_PT_MAX * 8) OG_PANEL(LQ_PT_MAX, 8);
-            else OG_PANEL(LQ_PT_MAX, LQ_CPT_MAX);
-#ifdef OGSQP_TRACE
-            if (k == 0) {
-                LqPanel hp;
-                OG_HIP(hipMemcpyAsync(&hp, qp->panel, sizeof(LqPanel), hipMemcpyDeviceToHost, s));
-                OG_HIP(hipStreamSynchronize(s));
-                fprintf(stderr, "[ogsqp trace] first panel kernel (len %d) ticks: load %lld products %lld reduction %lld update %lld gram %lld gram-red %lld store %lld\n",
-                        len, hp.tr[0], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[5], hp.tr[6]);
-            }
-#endif
-#undef OG_PANEL
-            {
-                const dim3 grid((nrows + LQ_RW - 1) / LQ_RW);
-                const int jt = (len + 255) / 256;
-#define OG_APPLY(KERNEL) \
-    hipLaunchKernelGGL(KERNEL, grid, dim3(256), 0, s, qp->Tc, qp->Jw, ldw, msweep, nq, k, qp->Vp, qp->panel)
-                if (jt <= 2) OG_APPLY(k_lq_apply_reg<2>);
-                else if (jt <= 4) OG_APPLY(k_lq_apply_reg<4>);
-                else if (jt <= 6) OG_APPLY(k_lq_apply_reg<6>);
-                else OG_APPLY(k_lq_apply);
-#undef OG_APPLY
-            }
-            k += LQ_NB;
-        }
-#ifdef OGSQP_TRACE
-        {
-            LqPanel hp;
-            OG_HIP(hipMemcpyAsync(&hp, qp->panel, sizeof(LqPanel), hipMemcpyDeviceToHost, s));
-            OG_HIP(hipStreamSynchronize(s));
-            fprintf(stderr, "[ogsqp trace] last panel kernel ticks: load %lld products %lld reduction %lld update %lld gram %lld gram-red %lld store %lld\n",
-                    hp.tr[0], hp.tr[1], hp.tr[2], hp.tr[3], hp.tr[4], hp.tr[5], hp.tr[6]);
-        }
-#endif
-        OG_STAGE("check diag");
-        if (meq) hipLaunchKernelGGL(k_check_diag, dim3(1), dim3(1024), 0, s, qp->diagL, meq, qp->flag, qp->dthresh);
-    }
-    OG_HIP(hipGetLastError());
-    // ---- equality-constrained minimiser: L w1 = -c,  deq = J1 w1 - Y (Y'g)
-    OG_STAGE("trsv w1");
-    if (meq) launch_trsv(qp, ldw, meq, 0, -1.0, qp->c, qp->w1, s);
-    int hflag[4] = {0, 0, 0, 0};
-    OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    OG_HIP(hipStreamSynchronize(s));
-    if (hflag[2] || hflag[3]) {          // a look-ahead workgroup of the sweep / a block of the chained solve gave up waiting
-        *lost = 1;
-        return 0;
-    }
-    if (hflag[0]) {                       // a dependent equality row that contradicts the others
-        *status = OG_QP_SINGULAR_C;
-        return 0;
-    }
-    OG_STAGE("deq");
-    if (nr > 0)
-        hipLaunchKernelGGL(k_gemv_cols, dim3((nr + 63) / 64), dim3(1024), 0, s, qp->Jw + meq, (long)ldw, nq, nr, qp->g,
-                           (const double*)nullptr, qp->t1);
-    hipLaunchKernelGGL(k_concat_neg, dim3((nq + 255) / 256), dim3(256), 0, s, qp->w1, meq, qp->t1, nr, qp->xcat);
-    hipLaunchKernelGGL(k_gemv_rows, dim3((nq + 3) / 4), dim3(256), 0, s, qp->Jw, (long)ldw, nq, nq, qp->xcat, 1.0,
-                       (const double*)nullptr, qp->deq);
-    // ---- least-distance problem in the null space
-    OG_STAGE("gemm G J");
-    if (mg) {
-        OG_TRY(launch_gemm(qp, A, meq, mg, nq, ldw, qp->GJ, (const int*)nullptr, s));
-        hipLaunchKernelGGL(k_gemv_cols_A, dim3((mg + 63) / 64), dim3(1024), 0, s, A, meq, nq, mg, qp->deq,
-                           qp->c + meq, qp->bG);
-    }
-    OG_STAGE("ldp setup");
-    hipLaunchKernelGGL(k_ldp_setup, dim3((mg + nq + 3) / 4), dim3(256), 0, s, qp->GJ, qp->Jw, ldw, meq, nq, mg, qp->bG,
-                       qp->c + meq, qp->deq, qp->dl, qp->du, qp->bval, qp->scale, qp->own, qp->flag);
-    GiArgs ga;
-    ga.GJ = qp->GJ; ga.Jw = qp->Jw; ga.ld = ldw; ga.meq = meq; ga.nq = nq; ga.mg = mg; ga.nr = nr;
-    ga.qcap = qp->qcap; ga.bval = qp->bval; ga.scale = qp->scale; ga.own = qp->own; ga.u = qp->u;
-    ga.isact = qp->isact; ga.y = qp->y; ga.act = qp->act; ga.R[0] = qp->R[0]; ga.R[1] = qp->R[1];
-    ga.RI[0] = qp->RI[0]; ga.RI[1] = qp->RI[1]; ga.Q1t = qp->Q1t; ga.partials = qp->partials; ga.st = qp->st;
-    const int mt = mg + 2 * nq;
-    ga.limit = 10 * (mt + nr) + 100;
-    GiState hst;
-    memset(&hst, 0, sizeof(hst));
-    // The attempt is given up (*lost = 1).  A resident launch of this attempt may have stopped half way: its workgroups
-    // published records under exchange numbers that were never written back to res_seq, and the next launch on the
-    // handle counts through the same numbers again and would take those records for its own.  The mailbox is zeroed
-    // first (valid numbers start at 1: a zeroed record matches none).
-    bool res_launched = false;
-    auto clear_mail = [&]() -> int {
-        if (res_launched) OG_HIP(hipMemsetAsync(qp->res_mail, 0, qp->res_mail_bytes, s));
-        return 0;
-    };
-    auto give_up = [&]() -> int {
-        *lost = 1;
-        return clear_mail();
-    };
-    const bool rows_mode = qp->gi_mode == 0;
-    if (rows_mode && nr > 0) {
-        // ---- rotated coordinates, one pass over the rows per change (ogsqp_rows.h)
-        RowsArgs ra;
-        ra.g = ga;
-        ra.g.RI[0] = qp->RI[0];
-        ra.g.RI[1] = qp->RI[1];
-        ra.dots = qp->dots;
-        ra.dvec = qp->dvec;
-        ra.rvec = qp->rvec;
-        ra.vvec = qp->csbuf;
-        ra.slot = qp->d_slot;
-        ra.price = qp->price;
-        ra.ratio = qp->ratio;
-        ra.rec = qp->rec;
-        const int nrows = mg + nq;
-        ra.G1 = std::max(8, std::min(128, (qp->qcap + 15) / 16));
-        // a wavefront per row (2048 workgroups at most: k_rows_decide reads that many partial prices in one trip)
-        ra.G2 = std::max(1, std::min(2048, (nrows + 1 + ROWS_WAVES - 1) / ROWS_WAVES));
-        // the warm start's removals spread over the grid where the tile fits next to the three vectors (ogsqp_rows.h)
-        ra.uval = qp->uval;
-        ra.lost = qp->flag + 2;
-        ra.spin_limit = qp->spin_limit;
-        ra.warm_spread = (qp->warm_spread && rows_lds_bytes(nr, qp->qcap) + rows_spread_lds_bytes(qp->qcap) <= LDS_LIMIT) ? 1 : 0;
-        ra.only_warm = 0;
-        const size_t lds1 = rows_lds_bytes(nr, qp->qcap) + (ra.warm_spread ? rows_spread_lds_bytes(qp->qcap) : 0);
-        OG_STAGE("rows init");
-        hipLaunchKernelGGL(k_rows_init, dim3((mt + n1 + 255) / 256 + 1), dim3(ROWS_THREADS), 0, s, ra, qp->diagL,
-                           (const int*)qp->d_warm, nwarm, qp->dthresh, qp->flag);
-        if (nwarm) {
-            hipLaunchKernelGGL(k_rows_mark, dim3((nwarm + 255) / 256), dim3(256), 0, s, ra, (const int*)qp->d_warm, nwarm);
-            hipLaunchKernelGGL(k_rows_invert, dim3(nwarm), dim3(ROWS_THREADS), (size_t)(nwarm + 1) * sizeof(double), s,
-                               ra, (const double*)qp->Tc, (const double*)qp->diagL);
-        }
-        const int tail_lanes = (nr + 63) / 64;
-        // long rows are streamed, the row staged in LDS when five vectors of the null space fit a workgroup's share
-        const size_t nrp = (size_t)tail_lanes * 64;
-        const bool stream = qp->rows_stream && tail_lanes > 16;
-        // (the second pass re-reads the row from the caches by default: staging it in LDS - OGSQP_ROWS=stage, where five
-        // vectors fit - costs the occupancy the streamed form lives on: 111 instead of 47 us per change at C5)
-        const bool stage = stream && qp->rows_stage > 0 && 5 * nrp * sizeof(double) <= LDS_LIMIT;
-        const size_t lds2 = (stage ? 5 : 1) * nrp * sizeof(double);
-#define OG_ROWS_APPLY(ra)                                                                                      \
-    do {                                                                                                     \
-        if (stream && stage) hipLaunchKernelGGL(k_rows_apply_stream<true>, dim3(ra.G2), dim3(ROWS_THREADS), lds2, s, ra); \
-        else if (stream) hipLaunchKernelGGL(k_rows_apply_stream<false>, dim3(ra.G2), dim3(ROWS_THREADS), lds2, s, ra); \
-        else if (qp->rows_r4 >= 0 && tail_lanes <= 8) hipLaunchKernelGGL(k_rows_apply_r4<8>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra); \
-        else if (qp->rows_r4 > 0 && tail_lanes <= 16) hipLaunchKernelGGL(k_rows_apply_r4<16>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra); \
-        else if (tail_lanes <= 8) hipLaunchKernelGGL(k_rows_apply<8>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra);   \
-        else if (tail_lanes <= 16) hipLaunchKernelGGL(k_rows_apply<16>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra); \
-        else if (tail_lanes <= 32) hipLaunchKernelGGL(k_rows_apply<32>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra); \
-        else hipLaunchKernelGGL(k_rows_apply<80>, dim3(ra.G2), dim3(ROWS_THREADS), 0, s, ra);                  \
-    } while (0)
-        OG_ROWS_APPLY(ra);                                     // values and pricing at y = 0
-        OG_HIP(hipGetLastError());
-        int batch = debug_stages() ? 1 : 8;
-        long launched = 0;
-        OG_STAGE("rows changes");
-        static const bool timing = getenv("OGSQP_TIMING") != nullptr;
-        double t_front = 0.0, t_enqueue = 0.0, t_wait = 0.0;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        if (timing) {
-            const double t0 = now();
-            OG_HIP(hipStreamSynchronize(s));
-            t_front = now() - t0;
-        }
-        // ---- round 6: the whole loop as ONE launch with the rows in registers, where they fit (ogsqp_resident.h).  In
-        // front of it as many two-launch pairs as the warm start's removals are expected to take (in `only_warm` form:
-        // with the warm start over they do nothing); the launch returns at once while the warm start is not over.
-        int cus = 0;
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, qp->device);
-        const int res_len = std::max(nr, qp->qcap);
-        const int res_wg = (nrows + qp->qcap + RES_ROWS - 1) / RES_ROWS;
-        // (res_wg_alloc <= RES_MAX_WG: the workgroups the mailbox was sized for)
-        bool resident = qp->resident && !debug_stages() && res_len <= RES_MAX_LEN && res_wg <= std::min(qp->res_wg_alloc, cus) &&
-                        res_lds_bytes(nr, qp->qcap) <= LDS_LIMIT;
-        if (resident) {
-            ResArgs rs;
-            rs.r = ra;
-            rs.mail = qp->res_mail;
-            rs.seq = qp->res_seq;
-            rs.NW = res_wg;
-            RowsArgs rw = ra;
-            rw.only_warm = 1;
-            const size_t ldsr = res_lds_bytes(nr, qp->qcap);
-            int pairs = nwarm ? std::max(1, qp->warm_pairs_hint) : 0;
-            long warm_launched = 0;
-            while (true) {
-                for (int it = 0; it < pairs; ++it) {
-                    hipLaunchKernelGGL(k_rows_decide, dim3(rw.G1), dim3(ROWS_THREADS), lds1, s, rw);
-                    OG_ROWS_APPLY(rw);
-                }
-                warm_launched += pairs;
-                hipLaunchKernelGGL(k_rows_resident, dim3(res_wg), dim3(RES_THREADS), ldsr, s, rs);
-                res_launched = true;
-                ++qp->resident_launches;
-                OG_HIP(hipGetLastError());
-                OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
-                OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-                OG_HIP(hipStreamSynchronize(s));
-                // the flags before the phase: workgroup 0 may have written back a phase >= 2 while another workgroup
-                // gave up a wait (or a wait gave up earlier in this attempt: the loop ran on garbage)
-                if (hflag[2] || hflag[3]) return give_up();
-                if (hst.phase >= 2) break;
-                if (hst.phase >= 0) {
-                    // a workgroup of the resident launch was not there to answer: nothing was written back; the attempt
-                    // is run again with the forms that wait for nothing
-                    return give_up();
-                }
-                if (warm_launched > (long)nwarm + 64) {
-                    OG_TRY(clear_mail());
-                    return fail(8, "og_qp_solve_dev: the warm start's removals made no progress (internal error)");
-                }
-                pairs = std::min(128, std::max(4, 4 * pairs));
-            }
-            // next time: as many pairs as this warm start's removals took, and a few (a pair that has nothing to do costs
-            // ~5 us, a second round trip to the host 50)
-            if (nwarm) qp->warm_pairs_hint = std::min(96, hst.warm_removals + 4);
-            qp->resident_changes += hst.iters;
-        }
-        while (!resident) {
-            const double te = timing ? now() : 0.0;
-            for (int it = 0; it < batch; ++it) {
-                hipLaunchKernelGGL(k_rows_decide, dim3(ra.G1), dim3(ROWS_THREADS), lds1, s, ra);
-                OG_ROWS_APPLY(ra);
-            }
-            launched += batch;
-            OG_HIP(hipGetLastError());
-            const double tw = timing ? now() : 0.0;
-            OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
-            OG_HIP(hipStreamSynchronize(s));
-            if (timing) {
-                t_enqueue += tw - te;
-                t_wait += now() - tw;
-            }
-            if (hst.phase >= 2) {
-                if (timing)
-                    fprintf(stderr, "[ogsqp timing] front end drained in %.3f ms; active set: %d changes, %ld pairs launched, "
-                                    "enqueue %.3f ms, wait %.3f ms\n", 1e3 * t_front, hst.iters, launched, 1e3 * t_enqueue,
-                            1e3 * t_wait);
-                break;
-            }
-            // every pair of launches is one change (or the end of the warm start): the device's own limit ends the loop
-            if (launched > (long)ga.limit + nwarm + 64) {
-                // (a wait that gave up earlier in this attempt - sweep, chained solve - leaves garbage the active-set
-                // kernels cannot make progress on: that is a lost attempt, to be re-run with the forms that wait for
-                // nothing, not an internal error)
-                OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-                OG_HIP(hipStreamSynchronize(s));
-                if (hflag[2] || hflag[3]) return give_up();
-                return fail(8, "og_qp_solve_dev: the active-set kernels made no progress (internal error)");
-            }
-            if (batch < 128) batch *= 2;
-        }
-#undef OG_ROWS_APPLY
-    } else if (!rows_mode) {
-    OG_STAGE("gi init");
-    hipLaunchKernelGGL(k_gi_init, dim3((mt + n1 + 255) / 256), dim3(256), 0, s, ga, qp->flag);
-    OG_HIP(hipGetLastError());
-    }
-    if (debug_stages()) {
-        OG_HIP(hipMemcpyAsync(hflag, qp->flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-        OG_HIP(hipStreamSynchronize(s));
-    }
-    const int coop_width = nr <= 1024 ? 16 : 64;
-    // workgroups beyond the ceil(nr / width) that own a slice only take part in the pricing
-    const int coop_slices = nr > 0 ? (nr + coop_width - 1) / coop_width : 0;
-    // as many as it takes to bring the pricing (all of W, every change) down to ~256 KB per workgroup,
-    // between 64 and one per CU
-    const size_t pricing_bytes = (size_t)(mg + nq) * (size_t)nr * sizeof(double);
-    const int coop_G = std::max(coop_slices, (int)std::min<size_t>(256, std::max<size_t>(64, pricing_bytes / (256 * 1024))));
-    const size_t coop_lds = (size_t)(4 * qp->qcap + 2 * coop_width + 2 * nr + COOP_THREADS) * sizeof(double) +
-                            (size_t)3 * qp->qcap * sizeof(int) + (size_t)((mg + 2 * nq + 31) / 32 + 1) * sizeof(unsigned) + 64;
-    // measured (tests/perf/solve_timing.py, OGSQP_GI=single|coop): per active-set change the cooperative kernel
-    // wins from C2's size on (C3: 40 vs 72 us; the first 25 major iterations of C3, 300-400 changes per
-    // subproblem, take 0.49 instead of 0.67 s), but its launch costs 0.15-0.3 ms more than the first batch of
-    // single-workgroup launches and late in a solve a subproblem moves a handful of rows: over whole solves the
-    // time per subproblem is the same within 4 % below 512 free directions (C2 1.60 / 1.77, C3' 1.50 / 1.65, C3
-    // 7.96 / 8.28 ms, single / cooperative).  The single-workgroup kernel is also the one whose sums run in the
-    // restatement's order (with exact Jacobians it walks SciPy's path iteration for iteration), so it stays the
-    // default there; from 512 on (C4, C5) the cooperative kernel is 1.5-3x faster per subproblem.
-    // Between 256 and 512 free directions the choice follows the previous subproblem: early in a solve (or after a
-    // restart) hundreds of rows move per subproblem and the cooperative kernel's 40 us per change beat the 72-83 us
-    // of single launches; later a handful move and the single-workgroup kernel's cheaper start wins.
-    const bool use_coop = qp->coop_mode == 2 ||
-                          (qp->coop_mode == 1 && (nr >= 512 || (nr >= 256 && qp->last_iters > 96)));
-    bool coop_done = false;
-    if (!rows_mode && nr > 0 && use_coop && coop_slices <= 64 && coop_lds <= LDS_LIMIT) {
-        // the whole active-set loop in one cooperative launch
-        CoopArgs ca;
-        ca.g = ga;
-        ca.g.Q1t = nullptr;
-        ca.G = coop_G;
-        ca.nslices = coop_slices;
-        ca.width = coop_width;
-        ca.astride = qp->qcap + 8;
-        ca.Q1s = qp->Q1t;
-        ca.RIr = qp->RI[0];
-        ca.apart = qp->apart;
-        ca.zg = qp->zg;
-        ca.rg = qp->uact;
-        ca.cs = qp->csbuf;
-        ca.cpart = qp->cpart;
-        ca.bar = qp->bar;
-        ca.abort_flag = qp->abort_flag;
-        OG_HIP(hipMemsetAsync(qp->bar, 0, sizeof(unsigned), s));
-        OG_HIP(hipMemsetAsync(qp->abort_flag, 0, sizeof(int), s));
-        void* kargs[] = {(void*)&ca};
-        OG_STAGE("gi cooperative");
-        const hipError_t launched = hipLaunchCooperativeKernel((const void*)k_gi_coop, dim3(coop_G),
-                                                               dim3(COOP_THREADS), kargs, (unsigned)coop_lds, s);
-        if (launched != hipSuccess) {
-            // the runtime cannot keep 64 workgroups of this size resident: the one-workgroup kernel
-            // below does the same job (both run on the GPU; nothing leaves it)
-            (void)hipGetLastError();
-            qp->coop_mode = 0;
-        } else {
-            coop_done = true;
-        }
-    }
-    if (coop_done) {
-        int habort = 0;
-        OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
-        OG_HIP(hipMemcpyAsync(&habort, qp->abort_flag, sizeof(int), hipMemcpyDeviceToHost, s));
-        OG_HIP(hipStreamSynchronize(s));
-#ifdef OGSQP_TRACE
-        {
-            static const char* nm[12] = {"pricing", "barrier 1", "projections 1", "barrier 2", "gather a, z1", "barrier 2b",
-                                         "projections 2", "barrier 3", "gather a2, z2, r", "barrier 4", "updates",
-                                         "barrier 5"};
-            fprintf(stderr, "[ogsqp trace] cooperative: %d iterations, G = %d\n", hst.iters, coop_G);
-            for (int e = 0; e < 12; ++e)
-                fprintf(stderr, "[ogsqp trace]   %-18s %8.0f ticks per iteration\n", nm[e],
-                        hst.iters ? (double)hst.tr[e] / hst.iters : 0.0);
-        }
-#endif
-        if (habort) {
-            OG_HIP(hipMemcpy(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost));
-            if (hflag[2] || hflag[3]) return give_up();   // (as above: the input of the loop came from a lost wait)
-            return fail(7, "og_qp_solve_dev: the cooperative active-set kernel lost a workgroup at a barrier");
-        }
-    } else if (rows_mode && nr > 0) {
-        // done above
-    } else if (nr > 0) {
-        const int blocks = (mg + nq + GI_WAVES - 1) / GI_WAVES;
-        const size_t lds = gi_lds_bytes(nr, qp->qcap);
-        int batch = debug_stages() ? 1 : 8;
-        OG_STAGE("gi iterations");
-        while (true) {
-            for (int it = 0; it < batch; ++it)
-                hipLaunchKernelGGL(k_gi_iter, dim3(blocks), dim3(GI_THREADS), lds, s, ga);
-            OG_HIP(hipGetLastError());
-            OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
-            OG_HIP(hipStreamSynchronize(s));
-            if (hst.phase >= 2) break;
-            if (batch < 64) batch *= 2;
-        }
-    } else {
-        hipLaunchKernelGGL(k_gi_init, dim3((mt + n1 + 255) / 256), dim3(256), 0, s, ga, qp->flag);
-        OG_HIP(hipMemcpyAsync(&hst, qp->st, sizeof(GiState), hipMemcpyDeviceToHost, s));
-        OG_HIP(hipStreamSynchronize(s));
-        if (hst.phase < 2) hst.phase = 2;   // nothing to move: feasibility was settled by k_ldp_setup
-    }
-    if (iterations) *iterations = hst.iters;
-    qp->last_iters = hst.iters;
-    if (debug_stages())
-        fprintf(stderr, "[ogsqp] LDP finished: phase %d after %d iterations, %d active, unfixable-row flag %d\n",
-                hst.phase, hst.iters, hst.q, hflag[1]);
-#ifdef OGSQP_TRACE
-    {
-        static const char* names_iter[9] = {"phase A + wait", "election", "load normal", "projections", "z update",
-                                            "r + ratio test", "u,y update", "append", "removal"};
-        static const char* names_rows[9] = {"state word", "who comes in", "normal in LDS", "norms", "inverse rows x d1",
-                                            "stores + ticket", "others' r, ratio", "u, y", "reflector, lists"};
-        static const char* names_res[16] = {"price, workgroup's best", "publish + poll + election", "winner's row", "(2) row from its owner", "norms",
-                                            "r: product, publish", "r: poll", "ratio test", "step, u, y, |y|", "row joins", "row leaves",
-                                            "pass over rows", "closing barrier", "(wave 15) pass over y", "-", "-"};
-        const bool res_trace = rows_mode && qp->resident_launches > 0;
-        const char* const* names = rows_mode ? names_rows : names_iter;
-        fprintf(stderr, "[ogsqp trace] %d iterations, %lld passes, %lld removals, %d active at the end\n", hst.iters,
-                hst.tr[10], hst.tr[11], hst.q);
-        for (int e = 0; e < 9; ++e)
-            fprintf(stderr, "[ogsqp trace]   %-16s %8.2f us per iteration\n", names[e],
-                    hst.iters ? 0.01 * (double)hst.tr[e] / hst.iters : 0.0);
-        if (res_trace)
-            for (int e = 0; e < 14; ++e)
-                fprintf(stderr, "[ogsqp trace]   resident: %-22s %8.2f us per change (%lld changes, %lld partial)\n", names_res[e],
-                        hst.tr[38] ? 0.01 * (double)hst.tr[16 + e] / hst.tr[38] : 0.0, hst.tr[38], hst.tr[39]);
-    }
-#endif
-    if (hst.dbg != 0) fprintf(stderr, "[ogsqp] internal check failed: code %d aux %d (q %d, p %d)\n", hst.dbg, hst.dbg2, hst.q, hst.p);
-    if (hst.phase != 2) {
-        // (a phase that came from a lost wait is no verdict on the subproblem: the attempt is run again)
-        OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-        OG_HIP(hipStreamSynchronize(s));
-        if (hflag[2] || hflag[3]) return give_up();
-        *status = hst.phase == 3 ? OG_QP_ITERATION_LIMIT : OG_QP_INCOMPATIBLE;
-        return 0;
-    }
-    // ---- step and multipliers
-    OG_STAGE("finish");
-    hipLaunchKernelGGL(k_finish_step, dim3((nq + 3) / 4), dim3(256), 0, s, qp->Jw, ldw, meq, nq, nr, mg, qp->y, qp->deq,
-                       qp->dl, qp->du, qp->u, qp->d, qp->bm);
-    hipLaunchKernelGGL(k_dual_residual, dim3((nq + 3) / 4), dim3(256), 0, s, A, meq, mg, nq, qp->g, qp->u, qp->bm,
-                       qp->tvec);
-    if (meq) {
-        hipLaunchKernelGGL(k_gemv_cols, dim3((meq + 63) / 64), dim3(1024), 0, s, qp->Jw, (long)ldw, nq, meq, qp->tvec,
-                           qp->w1, qp->rhs);
-        launch_trsv(qp, ldw, meq, 1, 1.0, qp->rhs, qp->lam, s);
-    }
-    OG_HIP(hipGetLastError());
-    OG_HIP(hipMemcpyAsync(d, qp->d, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
-    OG_HIP(hipMemcpyAsync(bound_mult, qp->bm, sizeof(double) * nq, hipMemcpyDeviceToHost, s));
-    if (meq) OG_HIP(hipMemcpyAsync(mult, qp->lam, sizeof(double) * meq, hipMemcpyDeviceToHost, s));
-    if (mg) OG_HIP(hipMemcpyAsync(mult + meq, qp->u, sizeof(double) * mg, hipMemcpyDeviceToHost, s));
-    // (the transposed chained solve for the multipliers ran after the first look at the flags)
-    OG_HIP(hipMemcpyAsync(hflag, qp->flag, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    OG_HIP(hipStreamSynchronize(s));
-    if (hflag[2] || hflag[3]) return give_up();
-    if (rows_mode && nr > 0) {
-        // the rows active at this solution, in the numbering of og_qp_get_active: where the next subproblem starts
-        std::vector<int> act((size_t)std::max(hst.q, 1));
-        if (hst.q > 0) OG_HIP(hipMemcpy(act.data(), qp->act, sizeof(int) * hst.q, hipMemcpyDeviceToHost));
-        std::vector<int> before(qp->warm);
-        qp->warm.clear();
-        for (int j = 0; j < hst.q; ++j) {
-            const int c = act[j];
-            if (c < mg)
-                qp->warm.push_back(c);
-            else if (c < mg + nq)
-                qp->warm.push_back(mg + 2 * (c - mg));
-            else
-                qp->warm.push_back(mg + 2 * (c - mg - nq) + 1);
-        }
-        // warm-start the next solve only if this solution kept most of the previous one's rows
-        std::vector<int> now(qp->warm);
-        std::sort(now.begin(), now.end());
-        std::sort(before.begin(), before.end());
-        std::vector<int> common;
-        std::set_intersection(now.begin(), now.end(), before.begin(), before.end(), std::back_inserter(common));
-        const size_t larger = std::max(now.size(), before.size());
-        qp->warm_use = before.empty() || 10 * common.size() >= 7 * larger;
-    }
-    if (!augmented) std::swap(qp->Z, qp->Jw);   // Z Q: same B, what og_qp_bfgs updates next
-    *status = OG_QP_SOLVED;
-    return 0;
-}
-
 int og_qp_solve_dev(og_qp_handle qp, const double* d_jt, int64_t ld, const double* g, const double* c,
                     const double* dl, const double* du, int32_t augmented, double rho, double* d, double* mult,
                     double* bound_mult, int32_t* status, int32_t* iterations, void* hip_stream) {
-    int lost = 0;
-    int rc = qp_solve_attempt(qp, d_jt, ld, g, c, dl, du, augmented, rho, d, mult, bound_mult, status, iterations,
-                              hip_stream, &lost);
+    const QpCall in{d_jt, ld, g, c, dl, du, augmented, rho, d, mult, bound_mult, status, iterations, hip_stream};
+    bool lost = false;
+    int rc = qp_solve_attempt(qp, qp ? qp->forms : QpForms(), in, &lost);
     if (rc || !lost) return rc;
     if (qp->n1 > LQ_PT_MAX * LQ_CPT_MAX) {
         // rows of this length have no form that waits for nothing: the same attempt is run again, with the lanes drained -
@@ -3598,37 +3695,20 @@ int og_qp_solve_dev(og_qp_handle qp, const double* d_jt, int64_t ld, const doubl
         for (int again = 0; again < 2 && lost; ++again) {
             (void)hipDeviceSynchronize();
             ++qp->recoveries;
-            lost = 0;
-            rc = qp_solve_attempt(qp, d_jt, ld, g, c, dl, du, augmented, rho, d, mult, bound_mult, status, iterations, hip_stream,
-                                  &lost);
+            rc = qp_solve_attempt(qp, qp->forms, in, &lost);
             if (rc) return rc;
         }
         if (lost)
             return fail(7, "og_qp_solve_dev: an inter-workgroup wait gave up three times and rows of this length have no form without one");
         return 0;
     }
-    // The look-ahead sweep and the chained triangular solves hand data between workgroups of ONE launch and assume the
-    // workgroups they wait for are resident; on a device shared with other streams, ranks or tenants that may not hold,
-    // and a bounded wait gives up.  Nothing was committed: the subproblem is solved again with the forms that wait for
-    // nothing (panel and update as separate launches, a launch per block of the triangular solves) - SciPy's core has
-    // no such failure mode, so neither does this one.
-    const bool ahead = qp->lq_ahead, wide_on = qp->lq_wide, spread_on = qp->warm_spread;
-    const int trsv = qp->trsv_mode;
-    const bool resident_on = qp->resident;
-    qp->resident = false;              // (the resident active-set launch waits for every one of its workgroups)
-    qp->warm_spread = false;           // (its wait between the two products is one of the waits that can give up)
-    qp->lq_ahead = false;
-    qp->lq_wide = false;               // (its column-split panel waits too; round 2's kernels serve the long rows)
-    if (qp->trsv_mode == 0) qp->trsv_mode = 1;
+    // The look-ahead sweep, the chained triangular solves and the resident active-set launch hand data between
+    // workgroups of ONE launch and assume the workgroups they wait for are resident; on a device shared with other
+    // streams, ranks or tenants that may not hold, and a bounded wait gives up.  Nothing was committed: the subproblem is
+    // solved again with the forms that wait for nothing (forms_without_waits) - SciPy's core has no such failure mode,
+    // so neither does this one.
     ++qp->recoveries;
-    lost = 0;
-    rc = qp_solve_attempt(qp, d_jt, ld, g, c, dl, du, augmented, rho, d, mult, bound_mult, status, iterations, hip_stream,
-                          &lost);
-    qp->lq_ahead = ahead;
-    qp->resident = resident_on;
-    qp->warm_spread = spread_on;
-    qp->lq_wide = wide_on;
-    qp->trsv_mode = trsv;
+    rc = qp_solve_attempt(qp, forms_without_waits(qp->forms), in, &lost);
     if (!rc && lost) return fail(7, "og_qp_solve_dev: a wait gave up in the forms that have none (internal error)");
     return rc;
 }
