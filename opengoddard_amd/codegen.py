@@ -20,15 +20,13 @@ node), knot rows (``OpenGoddard/optimize.py:674-696``); user inequalities (``:72
 from __future__ import annotations
 
 import hashlib
+import os
 
 import numpy as np
 
 from . import trace as _tr
 
-import os
-
 HEAVY_COLUMN_ELEMENTS = 32       # columns with more dependent elements get a whole workgroup
-LIGHT_COLS = 4                   # columns per workgroup otherwise (csrc/ogk_kernels.hip OGK_LIGHT_COLS)
 
 
 def fused_cols(n):
@@ -47,9 +45,6 @@ def tile_cols():
     computes the node tile's base products).  ``OG_TILE_COLS`` overrides (timing experiments)."""
     env = os.environ.get("OG_TILE_COLS")
     return max(1, min(7, int(env))) if env else 7
-
-
-MAX_GROUP_OUTPUTS = int(os.environ.get("OG_MAX_GROUP_OUTPUTS", "1"))
 
 
 # ------------------------------------------------------------------------------ element graph
@@ -301,29 +296,31 @@ class _Lowerer:
         return len(self.P.mv) - 1
 
 
-def _leaves(eg, eid, tags, seen=None, into_sums=True):
-    """Set of leaf nodes with a tag in ``tags`` reachable from ``eid``."""
-    seen = set() if seen is None else seen
-    out = set()
-    stack = [eid]
+def _children(node):
+    """Ids of the elements an element-graph node computes its value from, in argument order.  The term blocks of a
+    ``sum`` node are not among them: every walk treats those in its own way."""
+    tag = node[0]
+    if tag in ("un", "interp"):
+        return node[2:3]
+    if tag in ("bin", "cmp", "logic"):
+        return node[2:4]
+    return node[1:] if tag == "where" else ()
+
+
+def _leaves(eg, eid, tags):
+    """Set of leaf nodes with a tag in ``tags`` reachable from ``eid`` (through the terms of sums too)."""
+    out, seen, stack = set(), set(), [eid]
     while stack:
         e = stack.pop()
         if e in seen:
             continue
         seen.add(e)
         node = eg.nodes[e]
-        tag = node[0]
-        if tag in tags:
+        if node[0] in tags:
             out.add(node)
-        if tag in ("un", "interp"):
-            stack.append(node[2])
-        elif tag in ("bin", "cmp", "logic"):
-            stack.extend(node[2:4])
-        elif tag == "where":
-            stack.extend(node[1:])
-        elif tag == "sum" and into_sums:
-            for _, body in node[1]:
-                stack.append(body)
+        stack.extend(_children(node))
+        if node[0] == "sum":
+            stack.extend(body for _, body in node[1])
     return out
 
 
@@ -389,7 +386,6 @@ def trace_problem(prob, obj):
 def _make_groups(P):
     eg = P.eg
     defect = {}
-    buckets = {}
     order = []
     for row, ln, e, kind in P.pieces:
         ys = _leaves(eg, e, ("Y",))
@@ -408,13 +404,9 @@ def _make_groups(P):
                 order.append(defect[ph])
             defect[ph].outputs.append((row, e))
             continue
-        key = (kind, ln)
-        grp = buckets.get(key)
-        if grp is None or len(grp.outputs) >= MAX_GROUP_OUTPUTS:
-            grp = Group("rows", ln)
-            buckets[key] = grp
-            order.append(grp)
+        grp = Group("rows", ln)      # one piece, one output: item_value returns a row group's value (group<g>_v)
         grp.outputs.append((row, e))
+        order.append(grp)
     for grp in order:
         if grp.kind == "defect":
             slots = set()
@@ -478,17 +470,9 @@ def _group_dependencies(P, grp, roots=None):
                 deps.add((1, node[1], grp.length))
             else:
                 deps.add((2, node[1], span))
-        elif tag in ("un", "interp"):
-            stack.append((node[2], span))
-        elif tag in ("bin", "cmp", "logic"):
-            stack.append((node[2], span))
-            stack.append((node[3], span))
-        elif tag == "where":
-            for c in node[1:]:
-                stack.append((c, span))
         elif tag == "sum":
-            for ln, body in node[1]:
-                stack.append((body, ln))
+            stack.extend((body, ln) for ln, body in node[1])
+        stack.extend((c, span) for c in _children(node))
     return sorted(deps)
 
 
@@ -531,10 +515,11 @@ class _Emitter:
             return "%d" % base
         return "%d + %s" % (base, var) if base else var
 
-    def _emit_expr(self, roots, var, lines, names, indent, ymap):
-        """Emit SSA temporaries for every node reachable from ``roots`` (topological order)."""
+    def _emit_expr(self, roots, var, names, indent):
+        """Lines of SSA temporaries for every node reachable from ``roots`` that has no name yet (topological order;
+        a collocation product is never among them: the kernels subtract the tails from it)."""
         eg = self.eg
-        order, seen = [], set()
+        order, seen, lines = [], set(), []
 
         def visit(e):
             stack = [(e, False)]
@@ -547,16 +532,7 @@ class _Emitter:
                     continue
                 seen.add(cur)
                 stack.append((cur, True))
-                node = eg.nodes[cur]
-                tag = node[0]
-                if tag in ("un", "interp"):
-                    stack.append((node[2], False))
-                elif tag in ("bin", "cmp", "logic"):
-                    stack.append((node[3], False))
-                    stack.append((node[2], False))
-                elif tag == "where":
-                    for c in reversed(node[1:]):
-                        stack.append((c, False))
+                stack.extend((c, False) for c in reversed(_children(eg.nodes[cur])))     # first argument first
         for r in roots:
             visit(r)
         pad = " " * indent
@@ -571,8 +547,6 @@ class _Emitter:
                 rhs = _cdouble(node[1])
             elif tag == "CV":
                 rhs = "cv[%s]" % self._idx(self.P.cvec_off[node[1]] + node[2], node[3], var)
-            elif tag == "Y":
-                rhs = "y[%d]" % ymap[node[1]]
             elif tag == "un":
                 rhs = _UN_C[node[1]] % names[node[2]]
             elif tag == "interp":
@@ -603,6 +577,7 @@ class _Emitter:
                 raise AssertionError(tag)
             names[e] = name
             lines.append("%s%s %s = %s;" % (pad, ctype, name, rhs))
+        return lines
 
     def _collect_sums(self, roots):
         eg, out, seen = self.eg, [], set()
@@ -612,16 +587,9 @@ class _Emitter:
             if e in seen:
                 continue
             seen.add(e)
-            node = eg.nodes[e]
-            tag = node[0]
-            if tag == "sum":
+            if eg.nodes[e][0] == "sum":
                 out.append(e)
-            elif tag in ("un", "interp"):
-                stack.append(node[2])
-            elif tag in ("bin", "cmp", "logic"):
-                stack.extend(node[2:4])
-            elif tag == "where":
-                stack.extend(node[1:])
+            stack.extend(_children(eg.nodes[e]))
         return out
 
     def _emit_sums(self, roots, lines, names, indent):
@@ -702,13 +670,10 @@ class _Emitter:
     def term_functions(self):
         """``sum_term(tb, q, x, cv)``: term q of block tb; ``sum_term_reads(tb, q, j)``: does it read p[j]?"""
         eg = self.eg
-        offs, at = [], 0
-        for ln, _ in self.term_blocks:
-            offs.append(at)
-            at += ln
+        offs = _offsets(ln for ln, _ in self.term_blocks)
         L = ["    static constexpr int N_TBLK = %d;" % len(self.term_blocks),
-             "    static constexpr int N_TERMS = %d;" % at,
-             _int_table("TERM_OFF", offs), _int_table("TERM_LEN", [ln for ln, _ in self.term_blocks]),
+             "    static constexpr int N_TERMS = %d;" % offs[-1],
+             _int_table("TERM_OFF", offs[:-1]), _int_table("TERM_LEN", [ln for ln, _ in self.term_blocks]),
              "    template <class X> OG_HDI static typename X::scalar sum_term(const int tb, const int q, const X& x, "
              "const double* cv) {",
              "        typedef typename X::scalar S;",
@@ -717,7 +682,7 @@ class _Emitter:
         for tb, (ln, body) in enumerate(self.term_blocks):
             L.append("        case %d: {" % tb)
             inner = {}
-            self._emit_expr([body], "q", L, inner, 12, {})
+            L += self._emit_expr([body], "q", inner, 12)
             L += ["            return %s;" % inner[body], "        }"]
         L += ["        default: return S(0.0);", "        }", "    }",
               # which term of block tb reads p[j]: its index, -1 none, -2 more than one (no caching for that lane)
@@ -762,7 +727,7 @@ class _Emitter:
             names = {}
             if self._emit_sums(grp.tails, lines, names, 8):
                 self.sum_groups.add(gi)
-            self._emit_expr(grp.tails, "k", lines, names, 8, {})
+            lines += self._emit_expr(grp.tails, "k", names, 8)
             for s, e in enumerate(grp.tails):
                 lines.append("        T[%d] = %s;" % (s, names[e]))
             lines.append("    }")
@@ -773,7 +738,7 @@ class _Emitter:
                           "        (void)k; (void)cv;"]
                 nm = {}
                 self._emit_sums([e], lines, nm, 8)
-                self._emit_expr([e], "k", lines, nm, 8, {})
+                lines += self._emit_expr([e], "k", nm, 8)
                 lines += ["        return %s;" % nm[e], "    }"]
             lines += ["    template <class X> OG_HDI static void group%d(const int k, const X& x, "
                       "const typename X::scalar* y, const double* cv, typename X::scalar* out) {" % gi,
@@ -783,33 +748,21 @@ class _Emitter:
                 lines.append("        out[%d] = y[%d] - T[%d];" % (s, s, s))
             lines.append("    }")
             return lines
-        roots = [e for _, e in grp.outputs]
-        if len(roots) == 1:
-            # value-returning form: no address-taken temporaries in the kernels that evaluate single items
-            lines = ["    template <class X> OG_HDI static typename X::scalar group%d_v(const int k, const X& x, "
-                     "const double* cv) {" % gi,
-                     "        typedef typename X::scalar S;",
-                     "        (void)k; (void)cv;"]
-            names = {}
-            if self._emit_sums(roots, lines, names, 8):
-                self.sum_groups.add(gi)
-            self._emit_expr(roots, "k", lines, names, 8, {})
-            lines += ["        return %s;" % names[roots[0]], "    }",
-                      "    template <class X> OG_HDI static void group%d(const int k, const X& x, "
-                      "const typename X::scalar* y, const double* cv, typename X::scalar* out) {" % gi,
-                      "        (void)y;", "        out[0] = group%d_v(k, x, cv);" % gi, "    }"]
-            return lines
-        lines = ["    template <class X> OG_HDI static void group%d(const int k, const X& x, "
-                 "const typename X::scalar* y, const double* cv, typename X::scalar* out) {" % gi,
+        # a row group has one output (_make_groups).  Value-returning form: no address-taken temporaries in the
+        # kernels that evaluate single items
+        roots = [grp.outputs[0][1]]
+        lines = ["    template <class X> OG_HDI static typename X::scalar group%d_v(const int k, const X& x, "
+                 "const double* cv) {" % gi,
                  "        typedef typename X::scalar S;",
-                 "        (void)k; (void)y; (void)cv;"]
+                 "        (void)k; (void)cv;"]
         names = {}
         if self._emit_sums(roots, lines, names, 8):
             self.sum_groups.add(gi)
-        self._emit_expr(roots, "k", lines, names, 8, {})
-        for o, (_, e) in enumerate(grp.outputs):
-            lines.append("        out[%d] = %s;" % (o, names[e]))
-        lines.append("    }")
+        lines += self._emit_expr(roots, "k", names, 8)
+        lines += ["        return %s;" % names[roots[0]], "    }",
+                  "    template <class X> OG_HDI static void group%d(const int k, const X& x, "
+                  "const typename X::scalar* y, const double* cv, typename X::scalar* out) {" % gi,
+                  "        (void)y;", "        out[0] = group%d_v(k, x, cv);" % gi, "    }"]
         return lines
 
     def operand_function(self):
@@ -821,7 +774,7 @@ class _Emitter:
         for si, slot in enumerate(self.P.mv):
             lines.append("        case %d: {" % si)
             names = {}
-            self._emit_expr([slot.operand], "k", lines, names, 12, {})
+            lines += self._emit_expr([slot.operand], "k", names, 12)
             lines.append("            return %s;" % names[slot.operand])
             lines.append("        }")
         lines += ["        default: return 0.0;", "        }", "    }"]
@@ -835,6 +788,19 @@ def _int_table(name, values):
     body = ", ".join(str(int(v)) for v in values)
     return ("    OG_HD static int %s(const int i) { constexpr int t[%d] = {%s}; return t[i]; }"
             % (name, len(values), body))
+
+
+def _offsets(lengths):
+    """[0, l0, l0 + l1, ..., total]: where each of consecutive runs of these lengths begins, and their end."""
+    out = [0]
+    for ln in lengths:
+        out.append(out[-1] + ln)
+    return out
+
+
+def max_nmv(P):
+    """``MAX_NMV``: the largest number of collocation slots (states) of a phase, at least 1."""
+    return max([len(g.mv_slots) for g in P.groups] + [1])
 
 
 def _column_items(P):
@@ -860,25 +826,93 @@ def _column_items(P):
     return col_elems
 
 
+class SweepPlan:
+    """How the sweep's work is laid out, derived once from a Program.  ``sparsity`` - which the tests, the sharding
+    and the host scatter trust - and the tables the kernels read (``_sweep_records``) are both readers of it::
+
+        items[j], col_ptr, elems    column j's sorted (group, output, element) items; their ranges in ``elems``, all the
+                                    items column after column (OGT_ELEM)
+        own[j]                      [lo, hi): rows of the collocation block column j's state slice owns (the MFMA tiles
+                                    write them), (0, 0) for every other column
+        slot_group, slot_row0       per collocation slot: its defect group, the first row of its state
+        y0_off                      per slot, and at the end the total: offset of its base product in the y0 scratch
+        mv_diag, mv_generic         does the group's dynamics term read the slot's own slice node by node / otherwise?
+        dep_kind/_base/_cnt         the groups' dependencies (Group.deps), group after group
+        g_dep0, g_ndep              each group's range in them
+        col_tile[j]                 the one (defect group, 16-node tile) column j's defect items lie in, None, or "many"
+        heavy, light_runs           columns with a workgroup (or several) of their own, by falling item count; the other
+                                    columns as [first, count, tile] runs of at most ``fused_cols`` neighbours
+
+    The packed non-zeros of column j (``og_pack_dev``, include/ogpsx.h) are its own block, then ``items[j]``: both
+    ``sparsity`` and ``packed_pos`` say so in these terms, and nothing else restates that order."""
+
+    def __init__(self, P):
+        self.items = [sorted(items) for items in _column_items(P)]
+        self.col_ptr = _offsets(len(items) for items in self.items)
+        self.elems = [item for items in self.items for item in items]
+        self.dep_kind, self.dep_base, self.dep_cnt = ([dep[f] for g in P.groups for dep in g.deps] for f in range(3))
+        self.g_ndep = [len(g.deps) for g in P.groups]
+        self.g_dep0 = _offsets(self.g_ndep)[:-1]
+        self.y0_off = _offsets(sl.length for sl in P.mv)
+        self.slot_group = [0] * len(P.mv)
+        for gi, g in enumerate(P.groups):
+            for si in g.mv_slots:
+                self.slot_group[si] = gi
+        self.own = [(0, 0)] * P.n
+        self.slot_row0, self.mv_diag, self.mv_generic = [], [], []
+        for si, sl in enumerate(P.mv):
+            g = P.groups[self.slot_group[si]]
+            row0 = g.outputs[si - g.mv_slots[0]][0]
+            self.slot_row0.append(row0)
+            for j in range(sl.leaf_base, sl.leaf_base + sl.length):
+                self.own[j] = (row0, row0 + sl.length)
+            # how does the dynamics term of this group depend on columns of the slot's own slice?
+            self.mv_diag.append(int(any(kind == 1 and base == sl.leaf_base for kind, base, cnt in g.deps)))
+            self.mv_generic.append(int(any(not (kind == 1 and base == sl.leaf_base) and
+                                           base < sl.leaf_base + sl.length and base + cnt > sl.leaf_base
+                                           for kind, base, cnt in g.deps)))
+        # the collocation tile (defect group, 16-node tile) a column's defect items live in: the fused launch
+        # gives a light workgroup the base products of exactly one such tile.  Columns whose defect items
+        # spread over more than one tile get a workgroup of their own (like the columns with many items).
+        self.col_tile = []
+        for items in self.items:
+            keys = {(gi, k >> 4) for gi, o, k in items if P.groups[gi].kind == "defect"}
+            self.col_tile.append(None if not keys else (next(iter(keys)) if len(keys) == 1 else "many"))
+        self.heavy = [j for j in range(P.n)
+                      if len(self.items[j]) > HEAVY_COLUMN_ELEMENTS or self.col_tile[j] == "many"]
+        self.heavy.sort(key=lambda j: -len(self.items[j]))
+        # light columns in runs of at most fused_cols neighbours that share a tile
+        self.light_runs, run, heavy_set = [], None, set(self.heavy)
+        for j in range(P.n):
+            if j in heavy_set:
+                run = None
+                continue
+            key = self.col_tile[j]
+            if run is not None and run[0] + run[1] == j and run[1] < fused_cols(P.n) and \
+                    (key is None or run[2] is None or run[2] == key):
+                run[1] += 1
+                run[2] = run[2] if run[2] is not None else key
+            else:
+                run = [j, 1, key]
+                self.light_runs.append(run)
+
+    def packed_pos(self, j):
+        """Position of each item of column j among the column's packed non-zeros."""
+        lo, hi = self.own[j]
+        return {item: hi - lo + i for i, item in enumerate(self.items[j])}
+
+
 def sparsity(P):
     """Static pattern of the transposed Jacobian: ``(indptr, rows)`` with ``rows[indptr[j]:indptr[j+1]]`` the
     rows of F that can depend on p[j] - for column j first the collocation block its state slice owns
     (``N`` consecutive defect rows, written by the MFMA tiles), then the row items in work-list order.
     This is the order of the packed non-zeros (``og_pack_dev``, include/ogpsx.h); every other entry of
     J_T is an exact zero in every sweep."""
-    col_elems = _column_items(P)
-    own = {}
-    for gi, g in enumerate(P.groups):
-        for o, si in enumerate(g.mv_slots):
-            sl = P.mv[si]
-            row0 = g.outputs[o][0]
-            for j in range(sl.leaf_base, sl.leaf_base + sl.length):
-                own[j] = (row0, row0 + sl.length)
+    plan = SweepPlan(P)
     indptr, rows = [0], []
     for j in range(P.n):
-        lo, hi = own.get(j, (0, 0))
-        rows.extend(range(lo, hi))
-        rows.extend(P.groups[gi].outputs[o][0] + k for gi, o, k in sorted(col_elems[j]))
+        rows.extend(range(*plan.own[j]))
+        rows.extend(P.groups[gi].outputs[o][0] + k for gi, o, k in plan.items[j])
         indptr.append(len(rows))
     return np.asarray(indptr, dtype=np.int64), np.asarray(rows, dtype=np.int32)
 
@@ -899,12 +933,12 @@ def eval_lds_bytes(P):
     """Dynamic LDS of the evaluation kernels (modes 0, 2 and 12; ``defect_lds_bytes`` of csrc/ogk_kernels.hip) without
     the cached sum terms: per defect group ``KS*64`` doubles of the D panel, ``MAX_NMV*KS*4`` of operands and 256 of
     scratch, with ``KS = ceil(N/4)``."""
-    max_nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+    nmv = max_nmv(P)
     worst = 0
     for g in P.groups:
         if g.kind == "defect":
             ks = (g.length + 3) >> 2
-            worst = max(worst, 8 * (ks * 64 + max_nmv * ks * 4 + 256))
+            worst = max(worst, 8 * (ks * 64 + nmv * ks * 4 + 256))
     return worst
 
 
@@ -923,7 +957,7 @@ def check_limits(P):
         raise LimitError("%d phases: more than %d phases (OGK_MAX_PHASE) are not supported" % (len(P.nodes), MAX_PHASES))
     need = eval_lds_bytes(P)
     if need > EVAL_LDS_BYTES:
-        nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+        nmv = max_nmv(P)
         raise LimitError("the evaluation kernel needs %d bytes of LDS, more than the %d bytes a workgroup has: with %d "
                          "states per phase a phase can have at most %d nodes, the longest has %d"
                          % (need, EVAL_LDS_BYTES, nmv, max_phase_nodes(nmv), max(g.length for g in P.groups if g.kind == "defect")))
@@ -945,15 +979,15 @@ def lds_window(P):
     ``count_sum_terms``.  A module beyond the window sweeps in two launches (``og_one_launch``, include/ogpsx.h); ``eval_fits`` False is
     what ``check_limits`` refuses."""
     n_terms = count_sum_terms(P)
-    max_nmv = max([len(g.mv_slots) for g in P.groups] + [1])
+    nmv = max_nmv(P)
     term_doubles = n_terms + 16 if 0 < n_terms <= TERM_CACHE_MAX else 0
     eval_bytes = max(eval_lds_bytes(P), 8 * term_doubles)
     max_nodes = max(P.nodes)
     npad = 4 * ((max_nodes + 3) // 4)
-    fused_bytes = 8 * ((npad // 4) * 64 + max_nmv * (npad + max_nodes) + term_doubles)
+    fused_bytes = 8 * ((npad // 4) * 64 + nmv * (npad + max_nodes) + term_doubles)
     fill_bytes = 4 * ((P.m + 31) // 32)
     return {"eval_bytes": eval_bytes, "fused_bytes": fused_bytes, "fill_bytes": fill_bytes,
-            "max_nmv": max_nmv, "max_nodes": max_nodes, "n_terms": n_terms, "term_doubles": term_doubles,
+            "max_nmv": nmv, "max_nodes": max_nodes, "n_terms": n_terms, "term_doubles": term_doubles,
             "eval_fits": eval_bytes <= EVAL_LDS_BYTES,
             "one_launch": max(eval_bytes, fused_bytes, fill_bytes) <= LDS_BYTES}
 
@@ -976,337 +1010,281 @@ def count_sum_terms(P):
     return sum(ln for ln, _ in em.term_blocks)
 
 
+def _constants(P, plan):
+    """First section of ``struct OgGen``: the program's sizes and its small tables as host+device accessors."""
+    max_out = max(len(g.outputs) for g in P.groups)
+    rows = [g.outputs[o][0] if o < len(g.outputs) else 0 for g in P.groups for o in range(max_out)]
+    # prefix of row-group item counts: row item ri -> (group, k)
+    item0 = _offsets(g.length if g.kind == "rows" else 0 for g in P.groups)
+    return ["// generated by opengoddard_amd.codegen -- do not edit",
+            "#pragma once",
+            "#include \"og_math.h\"",
+            "",
+            "struct OgGen {",
+            "    static constexpr int N_VAR = %d;" % P.n,
+            "    static constexpr int M = %d;" % P.m,
+            "    static constexpr int M_EQ = %d;" % P.m_eq,
+            "    static constexpr int M_INEQ = %d;" % P.m_ineq,
+            "    static constexpr int N_PHASE = %d;" % len(P.nodes),
+            "    static constexpr int N_MV = %d;" % len(P.mv),
+            "    static constexpr int MAX_NODES = %d;" % max(P.nodes),
+            "    static constexpr int N_GROUPS = %d;" % len(P.groups),
+            "    static constexpr int N_CVEC = %d;" % P.cvec.shape[0],
+            "    static constexpr int MAX_OUT = %d;" % max_out,
+            "    static constexpr int MAX_NMV = %d;" % max_nmv(P),
+            "    static constexpr int N_ROW_ITEMS = %d;" % item0[-1],
+            _int_table("PHASE_NODES", P.nodes),
+            _int_table("MV_LEAF", [s.leaf_base for s in P.mv]),
+            _int_table("G_KIND", [1 if g.kind == "defect" else 0 for g in P.groups]),
+            _int_table("G_LEN", [g.length for g in P.groups]),
+            _int_table("G_NOUT", [len(g.outputs) for g in P.groups]),
+            _int_table("G_PHASE", [g.phase for g in P.groups]),
+            _int_table("G_MV0", [g.mv_slots[0] if g.mv_slots else 0 for g in P.groups]),
+            _int_table("G_NMV", [len(g.mv_slots) for g in P.groups]),
+            _int_table("G_ROW_FLAT", rows),
+            "    OG_HD static int G_ROW(const int g, const int o) { return G_ROW_FLAT(g * MAX_OUT + o); }",
+            _int_table("G_ITEM0", [at if g.kind == "rows" else -1 for g, at in zip(P.groups, item0)]),
+            _int_table("DEP_KIND", plan.dep_kind), _int_table("DEP_BASE", plan.dep_base),
+            _int_table("DEP_CNT", plan.dep_cnt),
+            "    static constexpr int N_HEAVY = %d;" % len(plan.heavy),
+            _int_table("MV_Y0", plan.y0_off[:-1]),
+            "    static constexpr int N_Y0 = %d;" % max(plan.y0_off[-1], 1)]
+
+
+def _switch(signature, on, cases, default="break;"):
+    """A dispatcher of one statement per case."""
+    return [signature, "        switch (%s) {" % on] + ["        case %d: %s" % case for case in cases] + \
+           ["        default: %s" % default, "        }", "    }"]
+
+
+# One J_T entry's worth of work, in two forms (name: arguments, unused ones, a defect item, a row item, no such item).
+# item_value: value of output o of group g at element k, and its row.  item_tail: the same split in two - everything
+# of an item except the base collocation product it subtracts from (row items: the whole value, *yoff = -1), the long
+# chain that does not depend on the product, and the offset of that product in the y0 scratch:
+# value = yoff >= 0 ? y0[yoff] - tail : tail.
+_ITEM_FORMS = {
+    "item_value": ("const double* y0, const double* cv, int* row", "(void)o; (void)y0;",
+                   "*row = %(row)d + k; return S(x.ldy(y0 + %(y0)d + k)) - tail%(g)d_%(s)d(k, x, cv);",
+                   "*row = %(row)d + k; return group%(g)d_v(k, x, cv);", ["*row = 0;"]),
+    "item_tail": ("const double* cv, int* row, int* yoff", "(void)o;",
+                  "*row = %(row)d + k; *yoff = %(y0)d + k; return tail%(g)d_%(s)d(k, x, cv);",
+                  "*row = %(row)d + k; *yoff = -1; return group%(g)d_v(k, x, cv);", ["*row = 0;", "*yoff = -1;"])}
+
+
+def _item_dispatcher(P, plan, name):
+    """``switch (g)`` over the groups and, in a defect group, ``switch (o)`` over its states (``_ITEM_FORMS``)."""
+    args, unused, defect, rows, none = _ITEM_FORMS[name]
+    L = ["    template <class X> OG_HDI static typename X::scalar %s(const int g, const int o, "
+         "const int k, const X& x, %s) {" % (name, args),
+         "        typedef typename X::scalar S;", "        " + unused, "        switch (g) {"]
+    for gi, g in enumerate(P.groups):
+        L.append("        case %d: {" % gi)
+        if g.kind == "defect":
+            L.append("            switch (o) {")
+            L += ["            case %d: " % s + defect % {"row": g.outputs[s][0], "y0": plan.y0_off[g.mv_slots[s]], "g": gi, "s": s}
+                  for s in range(len(g.tails))]
+            L += ["            default: break;", "            }", "            break;"]
+        else:
+            L.append("            " + rows % {"row": g.outputs[0][0], "g": gi})
+        L.append("        }")
+    return L + ["        default: break;", "        }"] + ["        " + line for line in none] + \
+        ["        return S(0.0);", "    }"]
+
+
+def _dispatchers(P, plan):
+    """The switches from a runtime group / slot number to the group, operand and tail functions; closes ``OgGen``."""
+    defect = [(gi, g) for gi, g in enumerate(P.groups) if g.kind == "defect"]
+    L = _switch("    template <class X> OG_HDI static void defect_tail(const int g, const int k, "
+                "const X& x, const double* cv, typename X::scalar* T) {", "g",
+                [(gi, "tail%d(k, x, cv, T); break;" % gi) for gi, g in defect])
+    L += [""] + _item_dispatcher(P, plan, "item_value") + [""] + _item_dispatcher(P, plan, "item_tail") + [""]
+    # the dynamics term of one collocation slot (one state) at node k
+    L += _switch("    template <class X> OG_HDI static typename X::scalar tail_one(const int slot, const int k, "
+                 "const X& x, const double* cv) {", "slot",
+                 [(sl, "return tail%d_%d(k, x, cv);" % (gi, si)) for gi, g in defect for si, sl in enumerate(g.mv_slots)],
+                 "return typename X::scalar(0.0);")
+    L += [""] + _switch("    template <class X> OG_HDI static void group_eval(const int g, const int k, "
+                        "const X& x, const typename X::scalar* y, const double* cv, typename X::scalar* out) {", "g",
+                        [(gi, "group%d(k, x, y, cv, out); break;" % gi) for gi in range(len(P.groups))])
+    return L + ["};"]
+
+
 def emit_header(P):
     """C++17 source of ``struct OgGen`` for this program (host+device, no includes of its own
     beyond og_math.h).  Raises ``LimitError`` for a program beyond the limits of a module (``check_limits``)."""
     check_limits(P)
-    em = _Emitter(P)
-    max_out = max(len(g.outputs) for g in P.groups)
-    n_rowitems = sum(g.length for g in P.groups if g.kind == "rows")
-    L = ["// generated by opengoddard_amd.codegen -- do not edit",
-         "#pragma once",
-         "#include \"og_math.h\"",
-         "",
-         "struct OgGen {",
-         "    static constexpr int N_VAR = %d;" % P.n,
-         "    static constexpr int M = %d;" % P.m,
-         "    static constexpr int M_EQ = %d;" % P.m_eq,
-         "    static constexpr int M_INEQ = %d;" % P.m_ineq,
-         "    static constexpr int N_PHASE = %d;" % len(P.nodes),
-         "    static constexpr int N_MV = %d;" % len(P.mv),
-         "    static constexpr int MAX_NODES = %d;" % max(P.nodes),
-         "    static constexpr int N_GROUPS = %d;" % len(P.groups),
-         "    static constexpr int N_CVEC = %d;" % P.cvec.shape[0],
-         "    static constexpr int MAX_OUT = %d;" % max_out,
-         "    static constexpr int MAX_NMV = %d;" % max([len(g.mv_slots) for g in P.groups] + [1]),
-         "    static constexpr int N_ROW_ITEMS = %d;" % n_rowitems,
-         _int_table("PHASE_NODES", P.nodes),
-         _int_table("MV_LEAF", [s.leaf_base for s in P.mv]),
-         _int_table("G_KIND", [1 if g.kind == "defect" else 0 for g in P.groups]),
-         _int_table("G_LEN", [g.length for g in P.groups]),
-         _int_table("G_NOUT", [len(g.outputs) for g in P.groups]),
-         _int_table("G_PHASE", [g.phase for g in P.groups]),
-         _int_table("G_MV0", [g.mv_slots[0] if g.mv_slots else 0 for g in P.groups]),
-         _int_table("G_NMV", [len(g.mv_slots) for g in P.groups])]
-    rows = []
-    for g in P.groups:
-        r = [row for row, _ in g.outputs]
-        rows += r + [0] * (max_out - len(r))
-    L.append(_int_table("G_ROW_FLAT", rows))
-    L.append("    OG_HD static int G_ROW(const int g, const int o) { return G_ROW_FLAT(g * MAX_OUT + o); }")
-    # prefix of row-group item counts: row item ri -> (group, k)
-    starts, at = [], 0
-    for g in P.groups:
-        starts.append(at if g.kind == "rows" else -1)
-        if g.kind == "rows":
-            at += g.length
-    L.append(_int_table("G_ITEM0", starts))
-    # dependency table (group-major) and per-group ranges into it
-    dep_g, dep_kind, dep_base, dep_cnt, g_dep0, g_ndep = [], [], [], [], [], []
-    for gi, g in enumerate(P.groups):
-        g_dep0.append(len(dep_g))
-        g_ndep.append(len(g.deps))
-        for kind, base, cnt in g.deps:
-            dep_g.append(gi), dep_kind.append(kind), dep_base.append(base), dep_cnt.append(cnt)
-    L += [_int_table("DEP_KIND", dep_kind), _int_table("DEP_BASE", dep_base),
-          _int_table("DEP_CNT", dep_cnt)]
-    # collocation slots: owning group, offset of their base product in the y0 scratch
-    slot_group = [0] * len(P.mv)
-    for gi, g in enumerate(P.groups):
-        for sl in g.mv_slots:
-            slot_group[sl] = gi
-    y0_off, at = [], 0
-    for sl in P.mv:
-        y0_off.append(at)
-        at += sl.length
-    col_elems = _column_items(P)
-    col_ptr, elem_g, elem_o, elem_k = [0], [], [], []
-    for j in range(P.n):
-        for gi, o, k in sorted(col_elems[j]):
-            elem_g.append(gi), elem_o.append(o), elem_k.append(k)
-        col_ptr.append(len(elem_g))
-    counts = np.diff(col_ptr)
-    # the collocation tile (defect group, 16-node tile) a column's defect items live in: the fused launch
-    # gives a light workgroup the base products of exactly one such tile.  Columns whose defect items
-    # spread over more than one tile get a workgroup of their own (like the columns with many items).
-    col_tile = []
-    for j in range(P.n):
-        keys = {(gi, k >> 4) for gi, o, k in col_elems[j] if P.groups[gi].kind == "defect"}
-        col_tile.append(None if not keys else (next(iter(keys)) if len(keys) == 1 else "many"))
-    heavy = [int(j) for j in range(P.n) if counts[j] > HEAVY_COLUMN_ELEMENTS or col_tile[j] == "many"]
-    heavy.sort(key=lambda j: -counts[j])
-    # light columns in runs of at most LIGHT_COLS neighbours that share a tile
-    light_groups, run, heavy_set = [], None, set(heavy)
-    for j in range(P.n):
-        if j in heavy_set:
-            run = None
-            continue
-        key = col_tile[j]
-        if run is not None and run[0] + run[1] == j and run[1] < fused_cols(P.n) and \
-                (key is None or run[2] is None or run[2] == key):
-            run[1] += 1
-            run[2] = run[2] if run[2] is not None else key
-        else:
-            run = [j, 1, key]
-            light_groups.append(run)
-    # rows of a J_T row written by the MFMA tiles (j inside a collocated state slice)
-    own_lo, own_hi = [0] * P.n, [0] * P.n
-    mv_diag, mv_generic = [], []
-    for si, sl in enumerate(P.mv):
-        g = P.groups[slot_group[si]]
-        row0 = g.outputs[si - g.mv_slots[0]][0]
-        for j in range(sl.leaf_base, sl.leaf_base + sl.length):
-            own_lo[j], own_hi[j] = row0, row0 + sl.length
-        # how does the dynamics term of this group depend on columns of the slot's own slice?
-        diag = any(kind == 1 and base == sl.leaf_base for kind, base, cnt in g.deps)
-        other = any(not (kind == 1 and base == sl.leaf_base) and
-                    base < sl.leaf_base + sl.length and base + cnt > sl.leaf_base
-                    for kind, base, cnt in g.deps)
-        mv_diag.append(int(diag))
-        mv_generic.append(int(other))
-    L.append("    static constexpr int N_HEAVY = %d;" % len(heavy))
-    L += [_int_table("MV_Y0", y0_off),
-          "    static constexpr int N_Y0 = %d;" % max(at, 1)]
-    L.append("")
-    L += _emit_functions(em, P)
-    L.append("")
-    L += em.term_functions()
-    L.append("")
-    L.append("    template <class X> OG_HDI static void defect_tail(const int g, const int k, "
-             "const X& x, const double* cv, typename X::scalar* T) {")
-    L.append("        switch (g) {")
-    for gi, g in enumerate(P.groups):
-        if g.kind == "defect":
-            L.append("        case %d: tail%d(k, x, cv, T); break;" % (gi, gi))
-    L += ["        default: break;", "        }", "    }", ""]
-    # one J_T entry's worth of work: value of output o of group g at element k, and its row
-    L.append("    template <class X> OG_HDI static typename X::scalar item_value(const int g, const int o, "
-             "const int k, const X& x, const double* y0, const double* cv, int* row) {")
-    L.append("        typedef typename X::scalar S;")
-    L.append("        (void)o; (void)y0;")
-    L.append("        switch (g) {")
-    for gi, g in enumerate(P.groups):
-        L.append("        case %d: {" % gi)
-        if g.kind == "defect":
-            L.append("            switch (o) {")
-            for si in range(len(g.tails)):
-                L.append("            case %d: *row = %d + k; return S(x.ldy(y0 + %d + k)) - tail%d_%d(k, x, cv);"
-                         % (si, g.outputs[si][0], y0_off[g.mv_slots[si]], gi, si))
-            L += ["            default: break;", "            }", "            break;"]
-        else:
-            if len(g.outputs) != 1:
-                raise _tr.TraceError("row groups must have one output (OG_MAX_GROUP_OUTPUTS=1)")
-            L += ["            *row = %d + k; return group%d_v(k, x, cv);" % (g.outputs[0][0], gi)]
-        L.append("        }")
-    L += ["        default: break;", "        }", "        *row = 0;", "        return S(0.0);", "    }", ""]
-    # the same split in two: everything of an item except the base collocation product it subtracts from
-    # (row items: the whole value, *yoff = -1) - the long chain that does not depend on the product - and the
-    # offset of that product in the y0 scratch.  value = yoff >= 0 ? y0[yoff] - tail : tail.
-    L.append("    template <class X> OG_HDI static typename X::scalar item_tail(const int g, const int o, "
-             "const int k, const X& x, const double* cv, int* row, int* yoff) {")
-    L.append("        typedef typename X::scalar S;")
-    L.append("        (void)o;")
-    L.append("        switch (g) {")
-    for gi, g in enumerate(P.groups):
-        L.append("        case %d: {" % gi)
-        if g.kind == "defect":
-            L.append("            switch (o) {")
-            for si in range(len(g.tails)):
-                L.append("            case %d: *row = %d + k; *yoff = %d + k; return tail%d_%d(k, x, cv);"
-                         % (si, g.outputs[si][0], y0_off[g.mv_slots[si]], gi, si))
-            L += ["            default: break;", "            }", "            break;"]
-        else:
-            L += ["            *row = %d + k; *yoff = -1; return group%d_v(k, x, cv);" % (g.outputs[0][0], gi)]
-        L.append("        }")
-    L += ["        default: break;", "        }", "        *row = 0;", "        *yoff = -1;", "        return S(0.0);",
-          "    }", ""]
-    # the dynamics term of one collocation slot (one state) at node k
-    L.append("    template <class X> OG_HDI static typename X::scalar tail_one(const int slot, const int k, "
-             "const X& x, const double* cv) {")
-    L.append("        switch (slot) {")
-    for gi, g in enumerate(P.groups):
-        for si, sl in enumerate(g.mv_slots):
-            L.append("        case %d: return tail%d_%d(k, x, cv);" % (sl, gi, si))
-    L += ["        default: return typename X::scalar(0.0);", "        }", "    }", ""]
-    L.append("    template <class X> OG_HDI static void group_eval(const int g, const int k, "
-             "const X& x, const typename X::scalar* y, const double* cv, typename X::scalar* out) {")
-    L.append("        switch (g) {")
-    for gi in range(len(P.groups)):
-        L.append("        case %d: group%d(k, x, y, cv, out); break;" % (gi, gi))
-    L += ["        default: break;", "        }", "    }", "};", ""]
-    L += _sweep_records(P, col_ptr, elem_g, elem_o, elem_k, own_lo, own_hi, heavy, slot_group,
-                        y0_off, mv_diag, mv_generic, g_dep0, g_ndep, light_groups, em.sum_groups)
-    return "\n".join(L)
+    em, plan = _Emitter(P), SweepPlan(P)
+    sections = [_constants(P, plan),
+                _emit_functions(em, P),         # (finds the sequential sums: before term_functions and the records)
+                em.term_functions(),
+                _dispatchers(P, plan),
+                _sweep_records(P, plan, em.sum_groups)]
+    return "\n".join(line for section in sections for line in section + [""])
 
 
 SWEEP_WAVES = 8          # wavefronts per ogk_sweep workgroup (csrc/ogk_kernels.hip)
 
 
-def _sweep_records(P, col_ptr, elem_g, elem_o, elem_k, own_lo, own_hi, heavy, slot_group, y0_off,
-                   mv_diag, mv_generic, g_dep0, g_ndep, light_groups, sum_groups=()):
+# ---- packed fields of the records: field widths lowest bit first, next to the line of csrc/ogk_kernels.hip that
+# ---- decodes them.  A value that does not fit its field is a LimitError, never a corrupted neighbour.
+def _pack(what, *fields):
+    """One int of (name, value, bits) fields, the first in the lowest bits."""
+    word, at = 0, 0
+    for name, value, bits in fields:
+        if not 0 <= value < 1 << bits:
+            raise LimitError("%s: %s = %d does not fit its %d bits" % (what, name, value, bits))
+        word |= int(value) << at
+        at += bits
+    return word
+
+
+def _col_w(own_hi, heavy):           # :658  HEAVY_FLAG = 1 << 30;  :711  own_hi = col.w & ~HEAVY_FLAG
+    return _pack("OGT_COL.w", ("own_hi", own_hi, 30), ("heavy", heavy, 1))
+
+
+def _slot_v7(dep0, ndep):            # :824, :1369  dep0 = rec.v[7] >> 12, ndep = rec.v[7] & 0xfff
+    return _pack("OGT_SLOT.v[7]", ("ndep", ndep, 12), ("dep0", dep0, 19))
+
+
+def _lgrp_v7(phase, terms):          # :1191  phase = grp.v[7] & 0xffff;  :1192  terms = (grp.v[7] >> 16) != 0
+    return _pack("OGT_LGRP.v[7]", ("phase", phase, 16), ("terms", terms, 1))
+
+
+def _hpart_v7(N, phase, terms):      # :1281  N = rec.v[7] & 0xfffff, phase = (rec.v[7] >> 20) & 0x3ff;  :1282  bit 30
+    return _pack("OGT_HPART.v[7]", ("N", N, 20), ("phase", phase, 10), ("terms", terms, 1))
+
+
+def _rowwave_w(terms):               # :606  terms = terms || OGT_ROWWAVE[w2].w != 0
+    return _pack("OGT_ROWWAVE.w", ("terms", terms, 1))
+
+
+def _table(ctype, name, rows):
+    """``static __device__ const int4 | ogt_int8 NAME[n] = {rows};`` - an empty table gets one row of zeros."""
+    width, row = (4, "    {%s}") if ctype == "int4" else (8, "    {{%s}}")
+    rows = rows or [[0] * width]
+    return ["static __device__ const %s %s[%d] = {" % (ctype, name, len(rows)),
+            ",\n".join(row % ", ".join(str(int(v)) for v in r) for r in rows), "};"]
+
+
+def _array(ctype, name, values):
+    """``static <ctype> NAME[n] = {values};`` - an empty one gets a single 0."""
+    values = list(values) or [0]
+    return "static %s %s[%d] = {%s};" % (ctype, name, len(values), ", ".join(str(int(v)) for v in values))
+
+
+def _light_records(P, plan, sum_groups):
+    """Fused launch: OGT_LGRP {first column, columns, y0 offset, node tile, first slot, slots, nodes, phase | sum} per
+    light workgroup - everything it needs about its tile in ONE record: index tables looked up with a runtime group
+    number end up as stack copies in the kernel - and OGT_LRNG {items begin, end, entries of the column's own
+    collocation block (they precede its items in the packed order)} per (workgroup, column).  Third: which workgroups
+    have an item that contains a sum (their base terms are then cached in LDS)."""
+    lgrp, lrng, has_sum = [], [], []
+    for j0, cnt, key in plan.light_runs:
+        for j in range(j0, j0 + fused_cols(P.n)):
+            lrng.append([plan.col_ptr[j], plan.col_ptr[j + 1], plan.own[j][1] - plan.own[j][0], 0]
+                        if j < j0 + cnt else [0, 0, 0, 0])
+        has_sum.append(any(gi in sum_groups for gi, o, k in plan.elems[plan.col_ptr[j0]:plan.col_ptr[j0 + cnt]]))
+        if key:
+            g = P.groups[key[0]]
+            lgrp.append([j0, cnt, plan.y0_off[g.mv_slots[0]], key[1], g.mv_slots[0], len(g.mv_slots), g.length,
+                         _lgrp_v7(g.phase, has_sum[-1])])
+        else:
+            lgrp.append([j0, cnt, 0, 0, 0, 0, 0, _lgrp_v7(0, has_sum[-1])])
+    return lgrp, lrng, has_sum
+
+
+def _heavy_records(P, plan, sum_groups):
+    """Heavy columns of the fused launch are cut into parts that look like light workgroups: one part per
+    (defect group, 16-node tile) the column has items in - the tile's D^T panel and the group's operands go
+    through LDS, one wavefront runs the tile's base products - plus one tile-less part for its row items.
+    A part's items come in *slots*: runs of at most 16 (defect: one output over the tile's nodes) or 32 (rows:
+    one row group) items that share their code, one wavefront each (lanes: items at x0 + h e_j | the same at x0).
+    OGT_HELEM {group, output, element, position in the column's packed order} holds the heavy columns' items in
+    that order (OGT_ELEM keeps the order mode 1 uses); OGT_HSLOT {first item in OGT_HELEM, items} per slot."""
+    hpart, hslot, helem = [], [], []
+
+    def part(j, ppos, runs, tile):
+        first_slot = len(hslot)
+        for (gi, o), ks in sorted(runs.items()):
+            for c0 in range(0, len(ks), 32):
+                hslot.append([len(helem), len(ks[c0:c0 + 32]), 0, 0])
+                helem.extend([gi, o, k, ppos[(gi, o, k)]] for k in ks[c0:c0 + 32])
+        hpart.append([j, first_slot, len(hslot)] + tile)
+
+    for j in plan.heavy:
+        ppos = plan.packed_pos(j)
+        tiles_of, rows_by_group = {}, {}
+        for gi, o, k in plan.items[j]:                      # (sorted: every run's elements ascend)
+            if P.groups[gi].kind == "defect":
+                tiles_of.setdefault((gi, k >> 4), {}).setdefault((gi, o), []).append(k)
+            else:
+                rows_by_group.setdefault((gi, o), []).append(k)
+        for (gi, nt), by_out in sorted(tiles_of.items()):
+            g = P.groups[gi]
+            part(j, ppos, by_out, [plan.y0_off[g.mv_slots[0]], nt, g.mv_slots[0], len(g.mv_slots),
+                                   _hpart_v7(g.length, g.phase, gi in sum_groups)])
+        if rows_by_group:
+            terms = any(gi in sum_groups for gi, _ in rows_by_group)
+            part(j, ppos, rows_by_group, [0, 0, 0, 0, _hpart_v7(0, 0, terms)])
+    return hpart, hslot, helem
+
+
+def _tile_records(P):
+    """The MFMA tile workgroups: OGT_TILE {slot, tile group, node tile}; fused launch: OGT_FTILE {slot, first column
+    tile, node tile, column tiles} - at most SWEEP_WAVES - 1 column tiles per workgroup (the last wavefront computes
+    the base products of the node tile), spread evenly."""
+    tiles, ftiles = [], []
+    for si, sl in enumerate(P.mv):
+        t16 = (sl.length + 15) // 16
+        tiles += [[si, mtg, nt, 0] for mtg in range((t16 + SWEEP_WAVES - 1) // SWEEP_WAVES) for nt in range(t16)]
+        ngrp = -(-t16 // tile_cols())
+        per = -(-t16 // ngrp)
+        ftiles += [[si, c0, nt, min(per, t16 - c0)] for c0 in range(0, t16, per) for nt in range(t16)]
+    return tiles, ftiles
+
+
+def _sweep_records(P, plan, sum_groups):
     """Wide, aligned device tables so that a workgroup of the structured sweep learns everything
     about its column / item / MFMA tile from ONE load each (every dependent global load costs
     a few hundred cycles, and the sweep of a small problem is a chain of them)."""
-    def table(ctype, name, rows):
-        rows = rows or [[0] * (4 if ctype == "int4" else 8)]
-        body = ",\n".join("    {%s}" % ", ".join(str(int(v)) for v in r) for r in rows)
-        return ["static __device__ const %s %s[%d] = {" % (ctype, name, len(rows)), body, "};"]
-    heavy_set = set(heavy)
-    col = [[col_ptr[j], col_ptr[j + 1], own_lo[j], own_hi[j] | ((1 << 30) if j in heavy_set else 0)]
+    heavy_set = set(plan.heavy)
+    col = [[plan.col_ptr[j], plan.col_ptr[j + 1], plan.own[j][0], _col_w(plan.own[j][1], j in heavy_set)]
            for j in range(P.n)]
-    elem = [[g, o, k, P.groups[g].outputs[max(o, 0)][0] + k] for g, o, k in zip(elem_g, elem_o, elem_k)]
-    tiles, slots = [], []
-    for si, sl in enumerate(P.mv):
-        t16 = (sl.length + 15) // 16
-        for mtg in range((t16 + SWEEP_WAVES - 1) // SWEEP_WAVES):
-            for nt in range(t16):
-                tiles.append([si, mtg, nt, 0])
-        gi = slot_group[si]
-        g = P.groups[gi]
-        row0 = g.outputs[si - g.mv_slots[0]][0]
-        slots.append([sl.length, gi, sl.leaf_base, row0, y0_off[si], sl.phase,
-                      mv_diag[si] | (mv_generic[si] << 1), (g_dep0[gi] << 12) | g_ndep[gi]])
-    rowwaves = []
-    for gi, g in enumerate(P.groups):
-        if g.kind == "rows":
-            for k0 in range(0, g.length, 64):
-                rowwaves.append([gi, k0, g.length, 1 if gi in sum_groups else 0])   # .w: its code contains a sum
-    evalblk = []
-    for gi, g in enumerate(P.groups):
-        if g.kind == "defect":
-            for nt in range((g.length + 15) // 16):
-                evalblk.append([gi, nt, g.mv_slots[0], len(g.mv_slots)])
-    L = ["#if defined(__HIPCC__)"]
-    L += table("int4", "OGT_EVALBLK", evalblk)
-    L.append("static constexpr int OGT_N_EVALBLK = %d;" % len(evalblk))
-    # fused launch: {first column, columns, defect group or -1, node tile} per light workgroup; the first
-    # columns again as a host table (ogk_launch picks the groups a column range touches)
-    # (everything a workgroup needs about its tile in ONE record: index tables looked up with a runtime
-    # group number end up as stack copies in the kernel)
-    lgrp, lrng = [], []
-    for j0, cnt, key in light_groups:
-        for c in range(fused_cols(P.n)):
-            # {items begin, end, entries of the column's own collocation block (they precede its items in the
-            #  packed order)}
-            lrng.append([col_ptr[j0 + c], col_ptr[j0 + c + 1], own_hi[j0 + c] - own_lo[j0 + c], 0]
-                        if c < cnt else [0, 0, 0, 0])
-        # bit 16 of the last field: some item of the workgroup contains a sum (base terms are then cached in LDS)
-        terms = int(any(elem_g[e] in sum_groups for e in range(col_ptr[j0], col_ptr[j0 + cnt]))) << 16
-        if key:
-            g = P.groups[key[0]]
-            lgrp.append([j0, cnt, y0_off[g.mv_slots[0]], key[1], g.mv_slots[0], len(g.mv_slots), g.length,
-                         g.phase | terms])
-        else:
-            lgrp.append([j0, cnt, 0, 0, 0, 0, 0, terms])
-    # heavy columns of the fused launch are cut into parts that look like light workgroups: one part per
-    # (defect group, 16-node tile) the column has items in - the tile's D^T panel and the group's operands go
-    # through LDS, one wavefront runs the tile's base products - plus one tile-less part for its row items.
-    # A part's items come in *slots*: runs of at most 16 (defect: one output over the tile's nodes) or 32 (rows:
-    # one row group) items that share their code, one wavefront each (lanes: items at x0 + h e_j | the same at x0).
-    # OGT_HELEM holds the heavy columns' items in that order (OGT_ELEM keeps the order mode 1 uses).
-    hpart, hslot, helem = [], [], []
-    for j in heavy:
-        entries = [(elem_g[e], elem_o[e], elem_k[e]) for e in range(col_ptr[j], col_ptr[j + 1])]
-        # position of an item in the column's packed order (codegen.sparsity): own block first, then OGT_ELEM order
-        ppos = {ent: (own_hi[j] - own_lo[j]) + i for i, ent in enumerate(entries)}
-        tiles_of = {}
-        for gi, o, k in entries:
-            if P.groups[gi].kind == "defect":
-                tiles_of.setdefault((gi, k >> 4), {}).setdefault(o, []).append(k)
-        for (gi, nt_), by_out in sorted(tiles_of.items()):
-            g = P.groups[gi]
-            first_slot = len(hslot)
-            for o, ks in sorted(by_out.items()):
-                hslot.append([len(helem), len(ks), 0, 0])
-                helem += [[gi, o, k, ppos[(gi, o, k)]] for k in sorted(ks)]
-            hpart.append([j, first_slot, len(hslot), y0_off[g.mv_slots[0]], nt_, g.mv_slots[0], len(g.mv_slots),
-                          g.length | (g.phase << 20) | ((1 << 30) if gi in sum_groups else 0)])
-        rows_by_group = {}
-        for gi, o, k in entries:
-            if P.groups[gi].kind != "defect":
-                rows_by_group.setdefault((gi, o), []).append(k)
-        if rows_by_group:
-            first_slot = len(hslot)
-            for (gi, o), ks in sorted(rows_by_group.items()):
-                ks = sorted(ks)
-                for c0 in range(0, len(ks), 32):
-                    chunk = ks[c0:c0 + 32]
-                    hslot.append([len(helem), len(chunk), 0, 0])
-                    helem += [[gi, o, k, ppos[(gi, o, k)]] for k in chunk]
-            hpart.append([j, first_slot, len(hslot), 0, 0, 0, 0,
-                          (1 << 30) if any(gi in sum_groups for gi, _ in rows_by_group) else 0])
-    L += ["struct ogt_int8 { int v[8]; };",
-          "static __device__ const ogt_int8 OGT_HPART[%d] = {" % max(len(hpart), 1),
-          ",\n".join("    {{%s}}" % ", ".join(str(int(v)) for v in r) for r in (hpart or [[0] * 8])),
-          "};",
-          "static constexpr int OGT_N_HPART = %d;" % len(hpart),
-          "static constexpr int OGT_LGRP_COLS = %d;" % fused_cols(P.n),
-          "static __device__ const ogt_int8 OGT_LGRP[%d] = {" % max(len(lgrp), 1),
-          ",\n".join("    {{%s}}" % ", ".join(str(int(v)) for v in r) for r in (lgrp or [[0] * 8])),
-          "};"]
-    # OGT_HELEM: {group, output, element, position in the column's packed order}
-    L += table("int4", "OGT_HSLOT", hslot)    # {first item in OGT_HELEM, items} per slot of a heavy part
-    L += table("int4", "OGT_HELEM", helem)
-    L += table("int4", "OGT_LRNG", lrng)      # {items begin, end} per (group, column)
-    L += ["static constexpr int OGT_N_LGRP = %d;" % len(light_groups),
-          "static const int OGH_LGRP_J[%d] = {%s};" % (len(light_groups) + 1, ", ".join(
-              [str(r[0]) for r in light_groups] + [str(P.n)]))]
+    elem = [[gi, o, k, P.groups[gi].outputs[o][0] + k] for gi, o, k in plan.elems]
+    slots = [[sl.length, gi, sl.leaf_base, plan.slot_row0[si], plan.y0_off[si], sl.phase,
+              _pack("OGT_SLOT.v[6]", ("diag", plan.mv_diag[si], 1), ("generic", plan.mv_generic[si], 1)),
+              _slot_v7(plan.g_dep0[gi], plan.g_ndep[gi])]
+             for si, (sl, gi) in enumerate(zip(P.mv, plan.slot_group))]
+    rowwaves = [[gi, k0, g.length, _rowwave_w(gi in sum_groups)]          # .w: its code contains a sum
+                for gi, g in enumerate(P.groups) if g.kind == "rows" for k0 in range(0, g.length, 64)]
+    evalblk = [[gi, nt, g.mv_slots[0], len(g.mv_slots)]
+               for gi, g in enumerate(P.groups) if g.kind == "defect" for nt in range((g.length + 15) // 16)]
+    lgrp, lrng, has_sum = _light_records(P, plan, sum_groups)
+    hpart, hslot, helem = _heavy_records(P, plan, sum_groups)
+    tiles, ftiles = _tile_records(P)
+    L = ["#if defined(__HIPCC__)"] + _table("int4", "OGT_EVALBLK", evalblk)
+    L += ["static constexpr int OGT_N_EVALBLK = %d;" % len(evalblk), "struct ogt_int8 { int v[8]; };"]
+    L += _table("ogt_int8", "OGT_HPART", hpart)
+    L += ["static constexpr int OGT_N_HPART = %d;" % len(hpart),
+          "static constexpr int OGT_LGRP_COLS = %d;" % fused_cols(P.n)]
+    L += _table("ogt_int8", "OGT_LGRP", lgrp) + _table("int4", "OGT_HSLOT", hslot) + \
+        _table("int4", "OGT_HELEM", helem) + _table("int4", "OGT_LRNG", lrng)
     # Light workgroups whose items contain a sequential sum (a running cost: a chain of as many dependent additions
     # as the sum has terms) are the longest of the launch: they are dispatched FIRST among the light workgroups - the
     # launch's block index is mapped through these two lists (the groups with a sum, the others, each in column order;
-    # the host passes how many of the first lie below the launch's column range, ogk_launch)
-    with_sum = [i for i, r in enumerate(lgrp) if r[7] & (1 << 16)]
-    without = [i for i, r in enumerate(lgrp) if not r[7] & (1 << 16)]
-    L += ["static __device__ const int OGT_LSUM[%d] = {%s};" % (max(len(with_sum), 1), ", ".join(map(str, with_sum or [0]))),
-          "static __device__ const int OGT_LPLAIN[%d] = {%s};" % (max(len(without), 1), ", ".join(map(str, without or [0]))),
-          "static const unsigned char OGH_LGRP_SUM[%d] = {%s};" % (max(len(lgrp), 1), ", ".join(
-              "1" if r[7] & (1 << 16) else "0" for r in (lgrp or [[0] * 8])))]
-    L += table("int4", "OGT_ROWWAVE", rowwaves)
-    L.append("static constexpr int OGT_N_ROWWAVES = %d;" % len(rowwaves))
-    L += table("int4", "OGT_COL", col)
-    L += table("int4", "OGT_ELEM", elem)
-    L += table("int4", "OGT_TILE", tiles)
-    # fused launch: {slot, first column tile, node tile, column tiles} - at most SWEEP_WAVES - 1 column tiles
-    # per workgroup (the last wavefront computes the base products of the node tile), spread evenly
-    ftiles = []
-    for si, sl in enumerate(P.mv):
-        t16 = (sl.length + 15) // 16
-        ngrp = -(-t16 // tile_cols())
-        per = -(-t16 // ngrp)
-        for c0 in range(0, t16, per):
-            for nt in range(t16):
-                ftiles.append([si, c0, nt, min(per, t16 - c0)])
-    L += table("int4", "OGT_FTILE", ftiles)
-    L.append("static constexpr int OGT_N_FTILES = %d;" % len(ftiles))
-    L += table("ogt_int8", "OGT_SLOT", [[r] for r in []] or None) if False else \
-        ["static __device__ const ogt_int8 OGT_SLOT[%d] = {" % max(len(slots), 1),
-         ",\n".join("    {{%s}}" % ", ".join(str(int(v)) for v in r) for r in (slots or [[0] * 8])),
-         "};"]
-    L += ["static constexpr int OGT_N_TILES = %d;" % len(tiles),
-          "static __device__ const int OGT_HEAVY[%d] = {%s};" % (
-              max(len(heavy), 1), ", ".join(str(j) for j in heavy) or "0"),
-          "#endif", ""]
-    return L
+    # the host passes how many of the first lie below the launch's column range, ogk_launch).  OGH_LGRP_J: the
+    # workgroups' first columns again as a host table (ogk_launch picks the groups a column range touches)
+    L += ["static constexpr int OGT_N_LGRP = %d;" % len(lgrp),
+          _array("const int", "OGH_LGRP_J", [run[0] for run in plan.light_runs] + [P.n]),
+          _array("__device__ const int", "OGT_LSUM", [b for b, s in enumerate(has_sum) if s]),
+          _array("__device__ const int", "OGT_LPLAIN", [b for b, s in enumerate(has_sum) if not s]),
+          _array("const unsigned char", "OGH_LGRP_SUM", has_sum)]
+    L += _table("int4", "OGT_ROWWAVE", rowwaves) + ["static constexpr int OGT_N_ROWWAVES = %d;" % len(rowwaves)]
+    L += _table("int4", "OGT_COL", col) + _table("int4", "OGT_ELEM", elem) + _table("int4", "OGT_TILE", tiles)
+    L += _table("int4", "OGT_FTILE", ftiles) + ["static constexpr int OGT_N_FTILES = %d;" % len(ftiles)]
+    L += _table("ogt_int8", "OGT_SLOT", slots)
+    return L + ["static constexpr int OGT_N_TILES = %d;" % len(tiles),
+                _array("__device__ const int", "OGT_HEAVY", plan.heavy), "#endif"]
 
 
 def program_hash(source):

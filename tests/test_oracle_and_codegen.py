@@ -541,6 +541,31 @@ def test_fused_launch_work_lists_partition_the_sweep(name):
     assert covered == want
 
 
+def _packed_order_corpus():
+    import test_edge_problems
+    import test_random_layouts
+    cases = [pytest.param(lambda name=name: problems.build(name), id=name) for name in problems.NAMES]
+    cases += [pytest.param(make, id="edge-" + name) for name, make in sorted(test_edge_problems.CASES.items())]
+    return cases + [pytest.param(lambda seed=seed, shape=shape: test_random_layouts.make_problem(shape, seed), id="layout-%d" % seed)
+                    for seed, shape in test_random_layouts.CASES]
+
+
+@pytest.mark.parametrize("make", _packed_order_corpus())
+def test_sparsity_is_the_packed_order_of_the_emitted_tables(make):
+    """The pattern the tests, the sharding and the host scatter trust (codegen.sparsity) and the tables the kernels
+    read state ONE packed order: for every column j, sparsity's rows are the column's own collocation block
+    ``[OGT_COL[j].z, OGT_COL[j].w & ~HEAVY_FLAG)`` followed by the rows (``.w``) of its items
+    ``OGT_ELEM[OGT_COL[j].x : OGT_COL[j].y]``, read back from the emitted text."""
+    P = codegen.trace_problem(*make())
+    src = codegen.emit_header(P)
+    col, elem = _table(src, "OGT_COL"), _table(src, "OGT_ELEM")
+    indptr, rows = codegen.sparsity(P)
+    assert len(col) == P.n and len(indptr) == P.n + 1 and indptr[0] == 0 and indptr[-1] == len(rows)
+    for j, (e0, e1, own_lo, w) in enumerate(col):
+        want = list(range(own_lo, w & ~(1 << 30))) + [r[3] for r in elem[e0:e1]]
+        assert rows[indptr[j]:indptr[j + 1]].tolist() == want, j
+
+
 @pytest.mark.parametrize("name", ["goddard", "polar_tsto_shipped", "table_ascent", "low_thrust_shipped"])
 def test_batch_last_baseline_matches_the_column_loop(name):
     """oracle/batch_last.py (bench.py's cpu_baseline_batch_last): ONE evaluation of the unmodified callbacks on
