@@ -129,7 +129,8 @@ def running_cost_shapes():
     """Sequential sums of every shape the cached-term path distinguishes (codegen ``sum_term_q``, kernels
     ``XColT``): a two-phase running cost whose integrand reads two variables at the same node (one perturbed
     term per column), the phase's final time (every term is perturbed: evaluated in place), and a constant
-    vector; plus a user sum inside a constraint row."""
+    vector.  No constraint row here contains a sum; a Python ``sum()`` of traced scalars in a row is lowered to a plain
+    chain of additions, not to a term block (tests/test_sequential_sums.py: ``python_sum_row``)."""
     def dynamics(prob, obj, section):
         dx = Dynamics(prob, section)
         dx[0] = prob.states(1, section)
