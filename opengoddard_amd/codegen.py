@@ -790,6 +790,18 @@ def _int_table(name, values):
             % (name, len(values), body))
 
 
+def dfrag_offsets(nodes):
+    """Where each phase's D^T operand image begins in the packed image of all phases, in doubles (csrc/ogk.h:
+    ``ogk_frag_size`` = 16-node tiles x 4-sample steps x 64 lanes per phase, the phases one after the other)."""
+    return _offsets(((N + 15) // 16) * ((N + 3) // 4) * 64 for N in nodes)[:-1]
+
+
+def _dfrag_off_function(nodes):
+    """``OgGen::DFRAG_OFF(phase)``: the panel offset the sweep workgroups used to fetch from the launch arguments, as a
+    constant table of the header."""
+    return _int_table("DFRAG_OFF", dfrag_offsets(nodes))
+
+
 def _offsets(lengths):
     """[0, l0, l0 + l1, ..., total]: where each of consecutive runs of these lengths begins, and their end."""
     out = [0]
@@ -1034,6 +1046,7 @@ def _constants(P, plan):
             "    static constexpr int MAX_NMV = %d;" % max_nmv(P),
             "    static constexpr int N_ROW_ITEMS = %d;" % item0[-1],
             _int_table("PHASE_NODES", P.nodes),
+            _dfrag_off_function(P.nodes),
             _int_table("MV_LEAF", [s.leaf_base for s in P.mv]),
             _int_table("G_KIND", [1 if g.kind == "defect" else 0 for g in P.groups]),
             _int_table("G_LEN", [g.length for g in P.groups]),

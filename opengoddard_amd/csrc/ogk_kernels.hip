@@ -955,10 +955,10 @@ __device__ __forceinline__ void tile_body(const ogk_args& a, const int bx) {
 // third of a step at the sizes of this engine; loads from another workgroup's results inside one kernel would
 // have to bypass the (per-XCD, mutually incoherent) L2s, which is slower still (both measured, round 1).
 //   fz_light_body   a run of <= 16 neighbouring columns whose defect items lie in one (defect group, 16-node
-//                   tile): the whole workgroup stages the tile's D^T panel and the group's operands in LDS,
-//                   one wavefront runs the tile's MFMA chain, the others evaluate the items' long parts
-//                   meanwhile (lane = column, perturbed | base; wavefront = item slot).
-//   fz_heavy_part   one (defect group, node tile) of a column with many items, staged the same way; slots of
+//                   tile): the item wavefronts put the group's operands into LDS, a slot each, and go on into
+//                   their items' long parts without waiting (lane = column, perturbed | base; wavefront = item
+//                   slot); one wavefront runs the tile's MFMA chain with the D^T panel straight from memory.
+//   fz_heavy_part   one (defect group, node tile) of a column with many items, served the same way; slots of
 //                   items that share their code, one wavefront each (lanes = items, perturbed | base).
 //   fz_tile_body    d(defect_s)/d(state_s): <= 7 column tiles per workgroup share ONE base product / base
 //                   dynamics term / diagonal term, computed by otherwise idle wavefronts.
@@ -967,8 +967,8 @@ __device__ __forceinline__ void tile_body(const ogk_args& a, const int bx) {
 // the rows from z around those positions (finish_eval).  The launch arguments are pointers only.
 // ------------------------------------------------------------------------------------------
 // Timing experiments only: -DOGK_FZ=<mask> removes pieces of ogk_fused - 2 = no base-product chain in the light
-// workgroups, 4 = no operand staging there, 16 = evaluation workgroups do nothing, 32 = heavy columns skipped,
-// 2048 = no light items.  Results are wrong with any bit set.
+// workgroups, 4 = no operand staging there (and their service wavefronts do not wait for it), 16 = evaluation
+// workgroups do nothing, 32 = heavy columns skipped, 2048 = no light items.  Results are wrong with any bit set.
 #ifndef OGK_FZ
 #define OGK_FZ 0
 #endif
@@ -1036,50 +1036,58 @@ __device__ __forceinline__ void finish_eval(const ogk_args& a, const unsigned n_
     if (s_last) fz_fill_from_z(a, bits);
 }
 
-// base collocation products of one (defect group, node tile) on one wavefront: states are the rows of the
-// A operand (xt[state][NP] in LDS or global), D^T panel straight from the operand image.  The k-ordered
-// chain of ogk_eval.  store(state, node, value) for the live entries.
-template <class Store>
-__device__ __forceinline__ void base_products_tile(const double* panel, const int N, const int nt,
-                                                   const int nmv, const double* xt, const int xstride,
-                                                   const Store& store) {
-    const int lane = (int)threadIdx.x & 63, lk = lane >> 4, srow = lane & 15;
-    const int KS = (N + 3) >> 2;
-    const double* bsrc = panel + lane;                  // the tile's [KS][64] operand panel
-    const bool live = srow < nmv;
-    const double* xrow = xt + (live ? srow : 0) * xstride;
-    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-    constexpr int CH = 8;
-    double bv[CH], av[CH];
+// One chunk [ks0, ks0 + CH) of a node tile's D^T panel, straight from the operand image into registers.  Every load
+// is issued whatever KS is - a k-step past the panel reads the panel's last step again and is replaced by zero - so
+// the requests of a chunk leave back to back, with no scalar branch between them.
+template <int CH>
+__device__ __forceinline__ void fz_load_panel(const double* bsrc, const int ks0, const int KS, double (&bv)[CH]) {
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
-        const int l = u * 4 + lk;
-        bv[u] = u < KS ? bsrc[u * 64] : 0.0;
-        av[u] = (u < KS && live && l < N) ? xrow[l] : 0.0;
+        const int ks = ks0 + u;
+        const double v = bsrc[(ks < KS ? ks : KS - 1) * 64];
+        bv[u] = ks < KS ? v : 0.0;
     }
-    for (int ks0 = 0; ks0 < KS; ks0 += CH) {
-        // the next chunk's operands are requested before this chunk's MFMAs issue
-        double bn[CH], an[CH];
+}
+
+// the first two chunks of a panel: asked for as soon as the record that names the panel is there
+template <int CH>
+__device__ __forceinline__ void fz_load_first(const double* bsrc, const int KS, double (&b0)[CH], double (&b1)[CH]) {
+    fz_load_panel<CH>(bsrc, 0, KS, b0);
+    if (CH < KS) fz_load_panel<CH>(bsrc, CH, KS, b1);
+}
+
+// The k-ordered chain of ogk_eval over a node tile in chunks of CH k-steps.  bsrc: the tile's [KS][64] panel in the
+// operand image (+ lane); aop(ks): this lane's A operand of step ks (0 for ks >= KS).  The panel is requested a chunk
+// ahead through two register buffers that take turns (no copies; fz_load_first fills them).  A whole chunk is CH
+// MFMAs back to back, operands read unconditionally, no branch per k-step; only the last chunk, when KS is no multiple
+// of CH, steps over the k-steps it does not have (an MFMA on zero operands would leave the accumulator as it is, bit
+// for bit, but costs its 8 passes of the matrix pipe: a quarter more of them at 128 nodes in chunks of 10).
+template <int CH, class AOp>
+__device__ __forceinline__ v4f64 fz_chain(const double* bsrc, const int KS, double (&b0)[CH], double (&b1)[CH],
+                                          const AOp& aop) {
+    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+    const auto steps = [&](const double (&bv)[CH], const int ks0) {
+        double av[CH];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int ks = ks0 + CH + u;
-            const int l = ks * 4 + lk;
-            bn[u] = ks < KS ? bsrc[ks * 64] : 0.0;
-            an[u] = (ks < KS && live && l < N) ? xrow[l] : 0.0;
+        for (int u = 0; u < CH; ++u) av[u] = aop(ks0 + u);
+        if (ks0 + CH <= KS) {
+#pragma unroll
+            for (int u = 0; u < CH; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
+        } else {                        // the last chunk when it is not whole: its own steps only
+#pragma unroll
+            for (int u = 0; u < CH; ++u)
+                if (ks0 + u < KS) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
         }
-#pragma unroll
-        for (int u = 0; u < CH; ++u)
-            if (ks0 + u < KS) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-#pragma unroll
-        for (int u = 0; u < CH; ++u) { bv[u] = bn[u]; av[u] = an[u]; }
+    };
+    for (int ks0 = 0;; ks0 += 2 * CH) {
+        steps(b0, ks0);
+        if (ks0 + CH >= KS) break;
+        if (ks0 + 2 * CH < KS) fz_load_panel<CH>(bsrc, ks0 + 2 * CH, KS, b0);
+        steps(b1, ks0 + CH);
+        if (ks0 + 2 * CH >= KS) break;
+        if (ks0 + 3 * CH < KS) fz_load_panel<CH>(bsrc, ks0 + 3 * CH, KS, b1);
     }
-    // C/D layout: node = lane & 15, state = (lane >> 4) + 4 * reg
-    const int k = nt * 16 + (lane & 15);
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-        const int st = lk + 4 * reg;
-        if (st < nmv && k < N) store(st, k, acc[reg]);
-    }
+    return acc;
 }
 
 constexpr int FZ_COLS = OGT_LGRP_COLS;          // columns of a light workgroup of the fused launch (tracer)
@@ -1102,27 +1110,17 @@ constexpr int FZ_NP = ((FZ_MAXN + 3) / 4) * 4;
 constexpr int FZ_ROUNDS = 2;                                    // items per column and wavefront evaluated ahead of the base products
 constexpr int FZ_ITEM_WAVES = SWEEP_WAVES - 1;                 // item slots of a light workgroup (the last wavefront
                                                                // runs the MFMA chain instead)
-// LDS of a light workgroup: D panel of the tile [KS][64] | operands [state][NP] | base products [state][N]
+// LDS of a light workgroup: [KS][64] (where the tile's D panel was staged until the chain took it from memory; the
+// window keeps its size) | operands [state][NP] | base products [state][N]
 constexpr size_t FZ_TILE_DOUBLES = (size_t)(FZ_NP / 4) * 64 + (size_t)OgGen::MAX_NMV * (FZ_NP + FZ_MAXN);
 // ... | base terms of the program's sequential sums [N_TERMS] (workgroups with such items)
 constexpr size_t FZ_LDS_BYTES = (FZ_TILE_DOUBLES + TERM_DOUBLES) * sizeof(double);
-
-// flag the service wavefront raises in LDS for the other wavefronts of its workgroup
-__device__ __forceinline__ void lds_flag_raise(int* flag, const int value) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    *reinterpret_cast<volatile int*>(flag) = value;
-}
-__device__ __forceinline__ int lds_flag_wait(int* flag) {
-    int v;
-    while ((v = *reinterpret_cast<volatile int*>(flag)) == 0) __builtin_amdgcn_s_sleep(1);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    return v;
-}
 
 #if OGK_TRACE                           // tools/trace_fused.py: phase stamps of every wavefront, next to the results
 #define FZ_TRACE_DECL(kind_) long long tr_[6] = {(long long)__builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0, 0}; \
     const int tr_kind_ = (kind_)
 #define FZ_STAMP(i) tr_[i] = (long long)__builtin_amdgcn_s_memrealtime()
+#define FZ_STAMP_SET(i, v) tr_[i] = (v)
 #define FZ_TRACE_OUT(a_)                                                                                   \
     do {                                                                                                   \
         if (((int)threadIdx.x & 63) == 0 && (a_).trace) {                                                  \
@@ -1135,12 +1133,13 @@ __device__ __forceinline__ int lds_flag_wait(int* flag) {
 #else
 #define FZ_TRACE_DECL(kind_) do { } while (0)
 #define FZ_STAMP(i) do { } while (0)
+#define FZ_STAMP_SET(i, v) (void)(v)
 #define FZ_TRACE_OUT(a_) do { } while (0)
 #endif
 
 // LDS of a workgroup that owns one (defect group, node tile): what its service wavefront needs
 struct FzTile {
-    double* dpanel;     // [KS][64] D^T panel of the tile in operand order
+    double* dpanel;     // [KS][64] not used by the light workgroups and heavy parts any more
     double* xt;         // [state][NP] operands of the group
     double* yb;         // [state][N] base products (the tile's nodes)
 };
@@ -1151,39 +1150,84 @@ __device__ __forceinline__ FzTile fz_tile_lds(double* lds) {
     t.yb = t.xt + OgGen::MAX_NMV * FZ_NP;
     return t;
 }
-// everybody requests the tile's D^T panel and the group's operands and parks them in LDS; the caller's barrier
-// publishes them to the service wavefront
-__device__ __forceinline__ void fz_stage_tile(const ogk_args& a, const FzTile& t, const int nt, const int mv0,
-                                              const int nmv, const int N, const int phase) {
+// Hand-overs inside a sweep workgroup go through words in LDS, and LDS keeps what the previous workgroup left there:
+// the words are cleared behind ONE barrier at the very top of the workgroup, ahead of its first load, where it costs the
+// spread of the wavefronts' starts and nothing else.  After it nobody waits for anybody except for the data itself.
+__device__ __forceinline__ void fz_sync_reset(int* words, const int n) {
+    if ((int)threadIdx.x < n) words[threadIdx.x] = 0;
+    lds_barrier();
+}
+// a producer's results are in LDS: one more of them
+__device__ __forceinline__ void lds_count_up(int* word) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");     // (LDS only: loads in flight stay in flight)
+    __hip_atomic_fetch_add(word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// wait until `need` producers have counted up
+__device__ __forceinline__ void lds_count_wait(int* word, const int need) {
+    while (*reinterpret_cast<volatile int*>(word) < need) __builtin_amdgcn_s_sleep(1);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// A wavefront's share of the operands of its workgroup's (defect group, node tile): the group's slots wave,
+// wave + SWEEP_WAVES, ... as [NP] rows of t.xt, zero-padded to NP - a slot per wavefront, no divergence - and one
+// count for the service wavefront.  An item wavefront does not wait for anything: its items' long parts come next.
+// (The service wavefront has a slot of its own only in a group of SWEEP_WAVES states or more: nobody does two.)
+__device__ __forceinline__ void fz_stage_operands(const ogk_args& a, const FzTile& t, const int mv0, const int nmv,
+                                                  const int N, int* staged) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int KS = (N + 3) >> 2, NP = KS << 2;
-    constexpr int ST_D = (FZ_NP / 4 * 64 + SWEEP_THREADS - 1) / SWEEP_THREADS;
+    const int NP = ((N + 3) >> 2) << 2;
     constexpr int ST_S = (OgGen::MAX_NMV + SWEEP_WAVES - 1) / SWEEP_WAVES, ST_L = (FZ_NP + 63) / 64;
     const XCol xbase{a.x0, -1, 0.0};
-    double st_d[ST_D];
-    const double* src = a.dfrag + a.dfrag_off[phase] + (long)nt * KS * 64;
+    if (wave >= nmv) return;
 #pragma unroll
-    for (int u = 0; u < ST_D; ++u) {
-        const int i = tid + u * SWEEP_THREADS;
-        st_d[u] = i < KS * 64 ? src[i] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < ST_S; ++u)                             // a slot per wavefront: no divergence
+    for (int u = 0; u < ST_S; ++u)
 #pragma unroll
         for (int q = 0; q < ST_L; ++q) {
             const int sl = wave + u * SWEEP_WAVES, l = lane + q * 64;
             if (sl < nmv && l < NP) t.xt[sl * NP + l] = l < N ? OgGen::mv_operand(mv0 + sl, l, xbase, a.cvec) : 0.0;
         }
-#pragma unroll
-    for (int u = 0; u < ST_D; ++u) {
-        const int i = tid + u * SWEEP_THREADS;
-        if (i < KS * 64) t.dpanel[i] = st_d[u];
-    }
+    if (lane == 0) lds_count_up(staged);
 }
 
+// The service wavefront of a light workgroup or heavy part: the tile's D^T panel straight from the operand image into
+// registers - asked for before it waits for the operands, which the wavefronts with a slot (the first
+// min(nmv, SWEEP_WAVES) of them) put into LDS -, the chain, the base products [state][N] of the tile's nodes into t.yb.
+__device__ __forceinline__ long long fz_service_tile(const ogk_args& a, const FzTile& t, const int nt, const int nmv,
+                                                     const int N, const int phase, int* staged) {
+    const int lane = (int)threadIdx.x & 63, lk = lane >> 4, srow = lane & 15;
+    const int KS = (N + 3) >> 2, NP = KS << 2;
+    constexpr int CH = 8;
+    const double* bsrc = a.dfrag + OgGen::DFRAG_OFF(phase) + (long)nt * KS * 64 + lane;
+    double b0[CH], b1[CH];
+    fz_load_first<CH>(bsrc, KS, b0, b1);
+    if (!(OGK_FZ & 4)) lds_count_wait(staged, nmv < SWEEP_WAVES ? nmv : SWEEP_WAVES);
+    const long long t_seen = OGK_TRACE ? (long long)__builtin_amdgcn_s_memrealtime() : 0;     // (-> the caller's stamp)
+    const bool live = srow < nmv;
+    const double* xrow = t.xt + (live ? srow : 0) * NP + lk;
+    const v4f64 acc = fz_chain<CH>(bsrc, KS, b0, b1, [&](const int ks) {
+        const bool on = live && ks < KS;
+        const double v = xrow[on ? ks * 4 : 0];
+        return on ? v : 0.0;
+    });
+    // C/D layout: node = lane & 15, state = (lane >> 4) + 4 * reg
+    const int k = nt * 16 + (lane & 15);
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+        const int st = lk + 4 * reg;
+        if (st < nmv && k < N) t.yb[st * N + k] = acc[reg];
+    }
+    return t_seen;
+}
+
+// A light workgroup.  No barrier stands between a wavefront and its work (fz_sync_reset apart): an item wavefront
+// puts its slot of the group's operands into LDS, counts up and goes on into the long parts of its items; the service
+// wavefront has the tile's panel on its way meanwhile, starts the chain when the count is full and counts the base
+// products in; the item wavefronts look for that only when their tails are in registers.  A workgroup whose items
+// contain a sequential sum keeps a barrier behind which the sum's base terms are in LDS.
 __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, double* lds) {
-    __shared__ int s_flag;              // base products of the tile are in LDS
+    __shared__ int s_sync[2];           // [0] slots of operands in LDS, [1] base products of the tile in LDS
     FZ_TRACE_DECL(1);
+    fz_sync_reset(s_sync, 2);
     // {first column, columns, y0 offset of the tile's first slot, node tile, first slot, slots (0: no defect
     //  items), nodes, phase}
     const ogt_int8 grp = OGT_LGRP[b];
@@ -1195,6 +1239,7 @@ __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, do
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const bool service = wave == SWEEP_WAVES - 1;   // no items: the tile's MFMA chain
+    const FzTile t = fz_tile_lds(lds);
     // items: lanes 0..FZ_COLS-1 evaluate at x0 + h e_j, the next FZ_COLS lanes the same items at x0 -
     // one instruction stream, so the base value of a row item costs no time; wavefront = item slot
     const int cl = lane % FZ_COLS;
@@ -1207,19 +1252,18 @@ __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, do
     int4 item = make_int4(0, 0, 0, 0);
     const bool has_item = item_on && coli.x + wave < coli.y;
     if (has_item) item = OGT_ELEM[coli.x + wave];
-
-    const FzTile t = fz_tile_lds(lds);
-    if (tid == 0) s_flag = 0;
-    if (has_tile && !(OGK_FZ & 4)) fz_stage_tile(a, t, nt, mv0, nmv, N, phase);
-    if (terms) fill_terms<SWEEP_THREADS>(a, tc);
-    lds_barrier();            // (only LDS data crosses it: global loads in flight stay in flight)
+    // a wavefront first puts its slot of the group's operands into LDS; then, in a workgroup whose items contain a
+    // sequential sum, everybody fills the sum's base terms and meets at the barrier that publishes them
+    if (has_tile && !(OGK_FZ & 4)) fz_stage_operands(a, t, mv0, nmv, N, &s_sync[0]);
+    if (terms) {                                    // (uniform over the workgroup)
+        fill_terms<SWEEP_THREADS>(a, tc);
+        lds_barrier();        // (only LDS data crosses it: global loads in flight stay in flight)
+    }
     FZ_STAMP(1);
     if (service) {
-        if (has_tile && !(OGK_FZ & 2))
-            base_products_tile(t.dpanel, N, nt, nmv, t.xt, ((N + 3) >> 2) << 2,
-                               [&](const int st, const int k, const double v) { t.yb[st * N + k] = v; });
+        if (has_tile && !(OGK_FZ & 2)) FZ_STAMP_SET(1, fz_service_tile(a, t, nt, nmv, N, phase, &s_sync[0]));
         FZ_STAMP(2);
-        if (lane == 0) lds_flag_raise(&s_flag, 1);
+        if (lane == 0) lds_count_up(&s_sync[1]);
         FZ_TRACE_OUT(a);
         return;
     }
@@ -1233,7 +1277,7 @@ __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, do
         const XColT xa = make_xcolt(a, base_role ? -1 : ji, xj, terms ? tc : nullptr);
         // The long part of an item - its dynamics term, or the whole value of a row item - does not depend on
         // the base products: the first FZ_ROUNDS items of every column are evaluated while the service
-        // wavefront is still in its chain; only the subtraction from the product waits for the flag.
+        // wavefront is still in its chain; only the subtraction from the product waits for it.
         double tv[FZ_ROUNDS];
         int trow[FZ_ROUNDS], tyo[FZ_ROUNDS];
 #pragma unroll
@@ -1245,7 +1289,7 @@ __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, do
                 tv[r] = OgGen::item_tail(it.x, it.y, it.z, xa, a.cvec, &trow[r], &tyo[r]);
             }
         }
-        lds_flag_wait(&s_flag);
+        lds_count_wait(&s_sync[1], 1);
         FZ_STAMP(3);
 #pragma unroll
         for (int r = 0; r < FZ_ROUNDS; ++r) {
@@ -1268,15 +1312,16 @@ __device__ __forceinline__ void fz_light_body(const ogk_args& a, const int b, do
 }
 
 // One part of a heavy column (a phase's final time, say: it moves every defect row of the phase): the column's
-// items in ONE (defect group, node tile), staged exactly like a light workgroup, or its row items (no tile).
+// items in ONE (defect group, node tile), served exactly like a light workgroup, or its row items (no tile).
 // A slot = up to 32 items with the same code (one output over the tile's nodes / one row group): lanes 0..31 at
 // x0 + h e_j, lanes 32..63 the same items at x0, one wavefront per slot.
 __device__ __forceinline__ void fz_heavy_part(const ogk_args& a, const int pidx, double* lds) {
-    __shared__ int s_flag;
+    __shared__ int s_sync[2];           // as in fz_light_body
     FZ_TRACE_DECL(2);
     const ogt_int8 rec = OGT_HPART[pidx];      // {column, slots begin, end, y0 offset, node tile, first slot, slots, nodes | phase << 20}
     const int j = rec.v[0];
     if (j < a.col_lo || j >= a.col_hi) return;
+    fz_sync_reset(s_sync, 2);
     const int y0_first = rec.v[3], nt = rec.v[4], mv0 = rec.v[5], nmv = rec.v[6];
     const int N = rec.v[7] & 0xfffff, phase = (rec.v[7] >> 20) & 0x3ff;
     const bool terms = TERM_CACHE && ((rec.v[7] >> 30) & 1) != 0;
@@ -1285,6 +1330,7 @@ __device__ __forceinline__ void fz_heavy_part(const ogk_args& a, const int pidx,
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const bool service = wave == SWEEP_WAVES - 1;
+    const FzTile t = fz_tile_lds(lds);
     const double xb = a.x0[j];
     const double hh = a.h[j];
     const int il = lane & 31;
@@ -1295,18 +1341,16 @@ __device__ __forceinline__ void fz_heavy_part(const ogk_args& a, const int pidx,
         slot = OGT_HSLOT[rec.v[1] + wave];
         item = OGT_HELEM[slot.x + (il < slot.y ? il : 0)];
     }
-    const FzTile t = fz_tile_lds(lds);
-    if (tid == 0) s_flag = 0;
-    if (has_tile) fz_stage_tile(a, t, nt, mv0, nmv, N, phase);
-    if (terms) fill_terms<SWEEP_THREADS>(a, tc);
-    lds_barrier();
+    if (has_tile) fz_stage_operands(a, t, mv0, nmv, N, &s_sync[0]);
+    if (terms) {
+        fill_terms<SWEEP_THREADS>(a, tc);
+        lds_barrier();
+    }
     FZ_STAMP(1);
     if (service) {
-        if (has_tile)
-            base_products_tile(t.dpanel, N, nt, nmv, t.xt, ((N + 3) >> 2) << 2,
-                               [&](const int st, const int k, const double v) { t.yb[st * N + k] = v; });
+        if (has_tile) FZ_STAMP_SET(1, fz_service_tile(a, t, nt, nmv, N, phase, &s_sync[0]));
         FZ_STAMP(2);
-        if (lane == 0) lds_flag_raise(&s_flag, 1);
+        if (lane == 0) lds_count_up(&s_sync[1]);
         FZ_TRACE_OUT(a);
         return;
     }
@@ -1333,7 +1377,7 @@ __device__ __forceinline__ void fz_heavy_part(const ogk_args& a, const int pidx,
                 }
             }
             if (s0 == rec.v[1] + wave) {
-                lds_flag_wait(&s_flag);
+                lds_count_wait(&s_sync[1], 1);
                 FZ_STAMP(3);
             }
 #pragma unroll
@@ -1357,10 +1401,16 @@ __device__ __forceinline__ void fz_heavy_part(const ogk_args& a, const int pidx,
 // accumulator, its MFMA chain and, on the diagonal tile only, the perturbed dynamics term.  What every column
 // tile of the node tile shares - the base product and the base dynamics term of the 16 nodes - is computed
 // ONCE per workgroup by the last wavefront (and the one before it when it is free), in parallel, and handed
-// over through LDS; the column wavefronts meet it only at their epilogue.
+// over through LDS; the column wavefronts meet it only at their epilogue.  No barrier but fz_sync_reset's: the slot's
+// operand vector xt[NP] is put into LDS by the last wavefront (which needs it first and has nothing else to do) and,
+// beyond 64 operands, by the first ones, 64 operands each, and counted in; only the wavefronts that run a chain wait for
+// that count - with the panel, their own samples of x0 and h and their own perturbed operand already asked for - while
+// the wavefronts that compute the dynamics terms, the longest chains of the workgroup, start at once.
 __device__ __forceinline__ void fz_tile_body(const ogk_args& a, const int bx, double* lds) {
-    __shared__ int s_flags[3];          // [0] base products of the node tile, [1] base dynamics terms, [2] diagonal terms
+    __shared__ int s_flags[4];          // [0] base products of the node tile, [1] base dynamics terms, [2] diagonal terms,
+                                        // [3] wavefronts whose part of the operand vector is in LDS
     FZ_TRACE_DECL(3);
+    fz_sync_reset(s_flags, 4);
     const int4 tile = OGT_FTILE[bx];                   // {slot, first column tile, node tile, column tiles}
     const int slot = tile.x, ct0 = tile.y, nt = tile.z, nct = tile.w;
     const ogt_int8 rec = OGT_SLOT[slot];
@@ -1375,12 +1425,9 @@ __device__ __forceinline__ void fz_tile_body(const ogk_args& a, const int bx, do
     double* tb = yb + 16;                               // [16] base dynamics terms
     double* td = tb + 16;                               // [16] dynamics terms with the node's own sample perturbed
     const XCol xbase{a.x0, -1, 0.0};
-    for (int l = tid; l < KS * 4; l += SWEEP_THREADS)
-        xt[l] = l < N ? OgGen::mv_operand(slot, l, xbase, a.cvec) : 0.0;
-    if (tid < 3) s_flags[tid] = 0;
     const int k = nt * 16 + kk;                         // output node of this lane
     const bool k_on = k < N;
-    const double* bsrc = a.dfrag + a.dfrag_off[rec.v[5]] + (long)nt * KS * 64 + lane;
+    const double* bsrc = a.dfrag + OgGen::DFRAG_OFF(rec.v[5]) + (long)nt * KS * 64 + lane;
     constexpr int CH = 10;                              // k-steps per chunk
     const int prod_wave = SWEEP_WAVES - 1;
     const int term_wave = nct < SWEEP_WAVES - 1 ? SWEEP_WAVES - 2 : SWEEP_WAVES - 1;
@@ -1389,12 +1436,36 @@ __device__ __forceinline__ void fz_tile_body(const ogk_args& a, const int bx, do
     const bool diag_here = diag && nt >= ct0 && nt < ct0 + nct;
     const int diag_wave = nct < SWEEP_WAVES - 2 ? SWEEP_WAVES - 3 : -1;
     const bool col_wave = wave < nct;
-    double bv[CH];
-    if (col_wave || wave == prod_wave) {
+    const int l0 = (ct0 + wave) * 16;                   // first slice offset of a column wavefront's tile
+    const bool col_on = col_wave && !(l0 >= N || leaf + l0 >= a.col_hi || leaf + l0 + 16 <= a.col_lo);
+    const int la = l0 + kk;                             // A-operand row of this lane
+    const bool a_on = col_on && la < N;
+    double b0[CH], b1[CH], xbv[4], hv[4], xa_b = 0.0, xa_h = 0.0;
+    if (col_on || wave == prod_wave) fz_load_first<CH>(bsrc, KS, b0, b1);
+    if (col_on) {
+        xa_b = a.x0[a_on ? leaf + la : leaf];
+        xa_h = a.h[a_on ? leaf + la : leaf];
 #pragma unroll
-        for (int u = 0; u < CH; ++u) bv[u] = (u < KS) ? bsrc[u * 64] : 0.0;
+        for (int reg = 0; reg < 4; ++reg) {
+            const int lc = l0 + lk + 4 * reg;
+            const int jj = leaf + ((k_on && lc < N) ? lc : 0);
+            xbv[reg] = a.x0[jj];
+            hv[reg] = a.h[jj];
+        }
     }
-    lds_barrier();
+    const int NP = KS << 2, stage_l = (((wave + 1) & (SWEEP_WAVES - 1)) << 6) + lane;     // wavefront 7, 0, 1, ...
+    const int n_stage = (NP + 63) >> 6 < SWEEP_WAVES ? (NP + 63) >> 6 : SWEEP_WAVES;
+    if (stage_l - lane < NP) {
+        for (int l = stage_l; l < NP; l += SWEEP_THREADS)
+            xt[l] = l < N ? OgGen::mv_operand(slot, l, xbase, a.cvec) : 0.0;
+        if (lane == 0) lds_count_up(&s_flags[3]);
+    }
+    double hit_v = 0.0;
+    if (a_on) {
+        const XCol xa{a.x0, leaf + la, xa_b + xa_h};
+        hit_v = OgGen::mv_operand(slot, la, xa, a.cvec);
+    }
+    if (col_on || wave == prod_wave) lds_count_wait(&s_flags[3], n_stage);
     FZ_STAMP(1);
     if (!col_wave) {
         if (wave == diag_wave) {
@@ -1404,50 +1475,25 @@ __device__ __forceinline__ void fz_tile_body(const ogk_args& a, const int bx, do
                 const XCol xd{a.x0, jd, xbd + a.h[jd]};
                 td[kk] = OgGen::tail_one(slot, k, xd, a.cvec);
             }
-            if (lane == 0) lds_flag_raise(&s_flags[2], 1);
+            if (lane == 0) lds_count_up(&s_flags[2]);
         }
         if (wave == term_wave && lk == 0) tb[kk] = k_on ? OgGen::tail_one(slot, k, xbase, a.cvec) : 0.0;
-        if (wave == term_wave && lane == 0) lds_flag_raise(&s_flags[1], 1);
+        if (wave == term_wave && lane == 0) lds_count_up(&s_flags[1]);
         if (wave == prod_wave) {
-                v4f64 accb = {0.0, 0.0, 0.0, 0.0};
-            for (int ks0 = 0; ks0 < KS; ks0 += CH) {
-                double bn[CH];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int ks = ks0 + CH + u;
-                    bn[u] = (ks < KS) ? bsrc[ks * 64] : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int ks = ks0 + u;
-                    if (ks < KS) accb = __builtin_amdgcn_mfma_f64_16x16x4f64(xt[ks * 4 + lk], bv[u], accb, 0, 0, 0);
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) bv[u] = bn[u];
-            }
+            const v4f64 accb = fz_chain<CH>(bsrc, KS, b0, b1, [&](const int ks) {
+                const double v = xt[(ks < KS ? ks : 0) * 4 + lk];
+                return ks < KS ? v : 0.0;
+            });
             if (lk == 0) yb[kk] = accb[0];              // every row of accb holds the base product of node k
             FZ_STAMP(2);
-            if (lane == 0) lds_flag_raise(&s_flags[0], 1);
+            if (lane == 0) lds_count_up(&s_flags[0]);
         }
         FZ_TRACE_OUT(a);
         return;
     }
-    const int l0 = (ct0 + wave) * 16;                   // first slice offset of this wave's tile
-    if (l0 >= N || leaf + l0 >= a.col_hi || leaf + l0 + 16 <= a.col_lo) return;
-    const int la = l0 + kk;                             // A-operand row of this lane
-    const bool a_on = la < N;
-    const double xa_b = a.x0[a_on ? leaf + la : leaf];
-    const double xa_h = a.h[a_on ? leaf + la : leaf];
+    if (!col_on) return;
     const int row = row0 + (k_on ? k : 0);
-    double xbv[4], hv[4];
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-        const int lc = l0 + lk + 4 * reg;
-        const int jj = leaf + ((k_on && lc < N) ? lc : 0);
-        xbv[reg] = a.x0[jj];
-        hv[reg] = a.h[jj];
-    }
-    // the perturbed dynamics term on the diagonal: its chain runs while the loads are in flight
+    // the perturbed dynamics term on the diagonal
     double t_diag = 0.0;
     bool have_diag = false;
     {
@@ -1462,35 +1508,16 @@ __device__ __forceinline__ void fz_tile_body(const ogk_args& a, const int bx, do
             t_diag = OgGen::tail_one(slot, k, xd, a.cvec);
         }
     }
-    double hit_v = 0.0;
-    if (a_on) {
-        const XCol xa{a.x0, leaf + la, xa_b + xa_h};
-        hit_v = OgGen::mv_operand(slot, la, xa, a.cvec);
-    }
-    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-    for (int ks0 = 0; ks0 < KS; ks0 += CH) {
-        double bn[CH];
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int ks = ks0 + CH + u;
-            bn[u] = (ks < KS) ? bsrc[ks * 64] : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < CH; ++u) {
-            const int ks = ks0 + u;
-            if (ks < KS) {
-                const double aop = (ks * 4 + lk == la) ? hit_v : xt[ks * 4 + lk];
-                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(aop, bv[u], acc, 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < CH; ++u) bv[u] = bn[u];
-    }
+    const v4f64 acc = fz_chain<CH>(bsrc, KS, b0, b1, [&](const int ks) {
+        const int l = (ks < KS ? ks : 0) * 4 + lk;
+        const double v = xt[l];
+        return ks < KS ? (l == la ? hit_v : v) : 0.0;
+    });
     FZ_STAMP(2);
-    lds_flag_wait(&s_flags[1]);
-    lds_flag_wait(&s_flags[0]);
+    lds_count_wait(&s_flags[1], 1);
+    lds_count_wait(&s_flags[0], 1);
     if (diag_wave >= 0 && l0 == nt * 16) {              // (the diagonal tile: wavefront-uniform)
-        lds_flag_wait(&s_flags[2]);
+        lds_count_wait(&s_flags[2], 1);
         if (have_diag) t_diag = td[kk];
     }
     FZ_STAMP(3);

@@ -82,13 +82,13 @@ for kind in (0, 1, 2, 3):
     if kind == 0:
         line("results out", r[r[:, 2] > 0][:, 2])
     if kind == 1:
-        line("after the barrier", r[r[:, 2] > 0][:, 2])
+        line("operands in LDS | seen", r[r[:, 2] > 0][:, 2])
         s = r[r[:, 3] > 0]
         if len(s): line("service: chain done", s[:, 3])
         it = r[r[:, 4] > 0]
-        if len(it): line("items: flag seen", it[:, 4])
+        if len(it): line("items: base products seen", it[:, 4])
     if kind == 2:
-        line("operands staged", r[r[:, 2] > 0][:, 2]); line("base products done", r[r[:, 3] > 0][:, 3])
+        line("operands in LDS | seen", r[r[:, 2] > 0][:, 2]); line("base products done", r[r[:, 3] > 0][:, 3])
     if kind == 3:
         line("operands staged", r[r[:, 2] > 0][:, 2]); line("MFMA chain done", r[r[:, 3] > 0][:, 3])
     line("end", r[:, 7])
@@ -106,6 +106,6 @@ if len(light):
     # return before the items' stamps: column 6 is 0 for them)
     it = np.where((rec[:, 0] == 1) & (rec[:, 6] > 0))[0]
     it = it[np.argsort(-rec[it, 7])[:10]]
-    print("   slowest item wavefronts (light): wg / start / barrier / operands of the column / tails of the first rounds / flag seen / items done / end")
+    print("   slowest item wavefronts (light): wg / start / operands in LDS / - / - / base products seen / items done / end")
     for i in it:
         print("      wg %4d  %s" % (wg[i], "  ".join("%6.2f" % us(rec[i, c]) for c in (1, 2, 3, 6, 4, 5, 7))))
