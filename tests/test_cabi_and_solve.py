@@ -265,8 +265,14 @@ def test_auto_falls_back_to_scipys_core_when_the_hip_core_cannot_take_the_proble
         pass
     assert "16384" in sqp.prepare(types.SimpleNamespace(n=17000, m_eq=10))
     assert "null space" in sqp.prepare(types.SimpleNamespace(n=8000, m_eq=100))
-    reason = sqp.prepare(types.SimpleNamespace(n=300, m_eq=100))
-    assert reason is not None and ("GPU" in reason or "torch" in reason)
+    # the edges themselves (og_qp_create refuses the same two shapes: tests/test_qp_wide_rows.py, on the device): one
+    # variable beyond the longest row with the null space at its limit, and the longest row with one equality too few
+    assert (sqp.MAX_N1, sqp.MAX_NULL_SPACE) == (16384, 6736)
+    assert "16384" in sqp.prepare(types.SimpleNamespace(n=16384, m_eq=9649))
+    assert "null space of the equalities (6737)" in sqp.prepare(types.SimpleNamespace(n=16383, m_eq=9647))
+    for accepted in (types.SimpleNamespace(n=16383, m_eq=9648), types.SimpleNamespace(n=300, m_eq=100)):
+        reason = sqp.prepare(accepted)                # (inside both limits: the next question is the device)
+        assert reason is not None and ("GPU" in reason or "torch" in reason)
 
     class Engine(np_path.NumpyEngine):                # an engine "auto" would give the HIP core (n >= AUTO_HIP_FROM)
         def __init__(self, prob, obj):
