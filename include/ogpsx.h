@@ -333,6 +333,43 @@ int og_jacobian_exact_batch_dev(og_batch b, int32_t count, const double* d_X, do
 int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* F0, double* vals,
                             int32_t* nonfinite);
 
+/* ---- run-time parameters --------------------------------------------------------------------------
+ * A problem may declare scalar model constants as PARAMETERS (opengoddard_amd: Problem.parameter): the generated
+ * functions then read them from the tail of the constant table - cvec[n_cvec - n_par + i] is parameter i, in the order
+ * of declaration - instead of carrying them as literals, and the calls below rewrite that tail on the device.  A trade
+ * study or a continuation in a constant then runs on ONE module: no trace, no compiler between two values.  The
+ * pattern, the registered persistent-zero buffers and the mapped-host path are structural and stay as they are; every
+ * later evaluation and sweep of the handle reads the new values.  NaN and infinities are legal values (rows that
+ * become non-finite follow the non-finite protocol of the sweep).
+ * og_parameter_count: n_par of the handle's module (0: it declares none).
+ * og_set_parameters: host pointer, blocking, ordered after everything the device was asked for before (it synchronises
+ * the device).  og_set_parameters_dev: d_theta[n_par] on the handle's device, asynchronous on hip_stream, capturable:
+ * one small launch of the runtime (one double per thread).  count must be n_par: anything else is hipErrorInvalidValue
+ * (1) with a message in og_last_error; on a handle without parameters count = 0 (and d_theta = NULL) succeed and do
+ * nothing.  Both also rewrite every lane of every batch of the handle: a handle-level set reaches everything.
+ * og_get_parameters: the values on the device now (blocking).
+ * A batch of a module with parameters gives every lane a copy of the constant table of its own (capacity x n_cvec
+ * doubles, made by og_batch_create from the handle's current table; without parameters the lanes share the handle's).
+ * og_parameters_batch_dev scatters d_TH[count][n_par] into the tails of lanes 0 .. count-1 in one launch; lanes count ..
+ * capacity-1 keep what they had.  d_TH = NULL: EVERY lane of the batch takes the handle's current values.  The lanes'
+ * parameters are device state, like a lane's J_T: they hold until the next such call or the next og_set_parameters(_dev)
+ * of the handle, the host keeps no copy, and a captured graph of {og_parameters_batch_dev, og_batch_fd_sweep_dev}
+ * replays on new contents of d_TH.  og_parameters_batch: host pointer (or NULL), blocking.  The rule of the batch calls
+ * stands: calls on a batch and on its handle must not overlap.
+ * og_multi_set_parameters: og_set_parameters on every sub-handle of a multi-device handle.
+ * (og_parameters_batch*, like og_jacobian_exact_batch*, are calls ON a batch that are named after what they do: the
+ * og_batch_ prefix stays the closed set of the section above.)
+ * None of these has a reference counterpart: the reference reads its constants as attributes of a Python object at
+ * every callback evaluation (OpenGoddard/optimize.py:670-733 call the user's functions with `obj`), so changing one is
+ * an attribute assignment there; here it is what saves a second trace and a second compilation. */
+int og_parameter_count(og_handle h);
+int og_set_parameters(og_handle h, const double* theta, int32_t count);
+int og_set_parameters_dev(og_handle h, const double* d_theta, void* hip_stream);
+int og_get_parameters(og_handle h, double* theta, int32_t count);
+int og_parameters_batch_dev(og_batch b, int32_t count, const double* d_TH, void* hip_stream);
+int og_parameters_batch(og_batch b, int32_t count, const double* TH);
+int og_multi_set_parameters(og_multi mh, const double* theta, int32_t count);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

@@ -95,6 +95,12 @@ class Program:
         self.cvec_off = []            # table id -> offset into cvec
         self.tables = []              # linear lookup tables (trace.Graph.tables)
         self.table_len = []
+        # run-time parameters (Problem.parameter): the LAST constant table, cvec[par_off + i] = parameter i.  Nothing
+        # from here to the header looks at these values: a parameterised header is a function of the structure only
+        self.n_par = 0
+        self.par_off = 0
+        self.par_names = ()
+        self.par_table = None         # the table's id (cvec_off[par_table] == par_off)
 
     @property
     def m(self):
@@ -188,6 +194,8 @@ class _Lowerer:
             out = [(node[2], self.eg.add(("P", node[1], 1)))]
         elif tag == "const":
             out = [(None, self.eg.add(("C", node[1])))]
+        elif tag == "par":
+            out = [(None, self.eg.add(("CV", self.P.par_table, node[1], 0)))]     # stride 0: fix() never folds it
         elif tag == "cvec":
             out = [(length, self.eg.add(("CV", node[1], 0, 1)))]
         elif tag in ("un", "interp"):
@@ -330,6 +338,9 @@ def trace_problem(prob, obj):
     n = int(prob.number_of_variables)
     sym_p = _tr.new_decision_vector(n)
     graph = sym_p.g
+    par_names = tuple(getattr(prob, "_par_names", ()))
+    if par_names:
+        graph.par_table = prob._par_values
     saved = prob.p
     prob.p = sym_p
     try:
@@ -353,6 +364,12 @@ def trace_problem(prob, obj):
     P = Program()
     P.n = n
     P.nodes = [int(v) for v in prob.nodes]
+    if par_names:
+        # one more table after the constant tables, appended past Graph.cvec's index of contents: a constant vector
+        # that happens to hold the same numbers stays a table of its own
+        P.n_par, P.par_names, P.par_table = len(par_names), par_names, len(graph.cvecs)
+        P.par_off = int(sum(v.shape[0] for v in graph.cvecs))
+        graph.cvecs.append(np.array([float(v) for v in prob._par_values], dtype=np.float64))
     low = _Lowerer(graph, P)
 
     cost = as_sym(cost, "cost")
@@ -380,6 +397,18 @@ def trace_problem(prob, obj):
         else:
             P.m_ineq = row - start
     _make_groups(P)
+    if par_names:
+        read = {leaf[2] for _, _, e, _ in P.pieces for leaf in _leaves(P.eg, e, ("CV",)) if leaf[1] == P.par_table}
+        read |= {leaf[2] for sl in P.mv for leaf in _leaves(P.eg, sl.operand, ("CV",)) if leaf[1] == P.par_table}
+        idle = [name for i, name in enumerate(par_names) if i not in read]
+        if idle:
+            import warnings
+            warnings.warn("parameter%s %s %s declared but the traced callbacks never read %s: set_parameter will change "
+                          "nothing the solver sees (a quantity derived from it in set-up code is a plain float - declare "
+                          "that quantity as a parameter, or compute it inside the callback)"
+                          % ("s" if len(idle) > 1 else "", ", ".join(repr(v) for v in idle),
+                             "are" if len(idle) > 1 else "is", "them" if len(idle) > 1 else "it"),
+                          RuntimeWarning, stacklevel=2)
     return P
 
 
@@ -1041,8 +1070,10 @@ def _constants(P, plan):
             "    static constexpr int N_MV = %d;" % len(P.mv),
             "    static constexpr int MAX_NODES = %d;" % max(P.nodes),
             "    static constexpr int N_GROUPS = %d;" % len(P.groups),
-            "    static constexpr int N_CVEC = %d;" % P.cvec.shape[0],
-            "    static constexpr int MAX_OUT = %d;" % max_out,
+            "    static constexpr int N_CVEC = %d;" % P.cvec.shape[0]] + \
+           (["    static constexpr int N_PAR = %d;" % P.n_par,          # (a header without parameters has neither line)
+             "    static constexpr int PAR_OFF = %d;" % P.par_off] if P.n_par else []) + \
+           ["    static constexpr int MAX_OUT = %d;" % max_out,
             "    static constexpr int MAX_NMV = %d;" % max_nmv(P),
             "    static constexpr int N_ROW_ITEMS = %d;" % item0[-1],
             _int_table("PHASE_NODES", P.nodes),

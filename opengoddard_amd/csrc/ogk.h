@@ -4,7 +4,7 @@
 #pragma once
 #include <stdint.h>
 
-#define OGK_ABI 13
+#define OGK_ABI 14
 #define OGK_MAX_PHASE 32
 
 // MFMA operand image of a differentiation matrix D (N x N, row-major [k][l]) for
@@ -79,11 +79,18 @@ typedef struct ogk_info {
     int32_t fused_ok;       // OGK_FUSED runs as ONE launch on this module (its LDS fits); else the caller uses OGK_EVAL + OGK_SWEEP
 } ogk_info;
 
+// Run-time parameters: cvec[par_off + i], i in [0, n_par), the tail of the constant table.  The generated functions read
+// them like every other table entry; the runtime rewrites them on the device (og_set_parameters, include/ogpsx.h).
+// A record of its own, asked for with a call of its own: ogk_info keeps its size.
+typedef struct ogk_par_info {
+    int32_t n_par, par_off;
+} ogk_par_info;
+
 typedef struct ogk_args {
     const double* x0;       // [n] decision vector (device)
     const double* h;        // [n] signed FD steps (device; unused for a plain evaluation)
     const double* dfrag;    // packed D fragments of all phases (device)
-    const double* cvec;     // constant table (device, may be NULL when n_cvec == 0)
+    const double* cvec;     // constant table (device, may be NULL when n_cvec == 0); its tail: the run-time parameters
     double* f0;             // [m] F(x0): written by OGK_EVAL, read by OGK_SWEEP and OGK_DENSE
     double* y0;             // [n_y0] base collocation products   (written by OGK_EVAL)
     double* xop;            // [n_y0] base collocation operands   (written by OGK_EVAL)
@@ -128,8 +135,9 @@ typedef struct ogk_args {
 
 // A batch (og_batch_*, include/ogpsx.h): B points of one problem in one launch, lane = blockIdx.y.  A lane is one
 // ogk_args record in a device table that the runtime writes when the batch is created: its own scratch, ticket,
-// counters and persistent-zero jt with its own jt_state / jt_launches words; dfrag, cvec and the pattern tables are
-// the handle's.  The table holds OGK_BATCH_SETS record sets of `capacity` lanes each: set 0 is what the one-launch
+// counters and persistent-zero jt with its own jt_state / jt_launches words; dfrag and the pattern tables are
+// the handle's, and so is cvec unless the module has run-time parameters: then every lane has a copy of the constant
+// table of its own.  The table holds OGK_BATCH_SETS record sets of `capacity` lanes each: set 0 is what the one-launch
 // sweep (OGK_BATCH_FUSED) runs; sets 1 and 2 are what the evaluation (OGK_BATCH_EVAL) runs, with jt_bump = 0 and 1.  What changes
 // from call to call - where the caller's X, H, F0 and packed values are - is written into the records by OGK_BATCH_BIND
 // (one thread per record) ahead of EVERY OGK_BATCH_FUSED / OGK_BATCH_EVAL launch, stream-ordered before it, so that those launches take
@@ -154,6 +162,7 @@ extern "C" {
 #endif
 // exported by every callback module
 int ogk_get_info(ogk_info* out);
+int ogk_get_par_info(ogk_par_info* out);    // part 0 (<module>.so) only needs to answer; every part does
 // OGK_EVAL: evaluate F(x0) into f0 (+ scratch y0/t0/z).  OGK_SWEEP: structured FD sweep over
 // [col_lo, col_hi) into jt (needs OGK_EVAL's outputs at the same x0).  OGK_DENSE: dense FD sweep.
 // OGK_EXACT_DENSE / OGK_EXACT: exact Jacobian, dense / structured (needs OGK_EVAL).  OGK_FUSED: OGK_EVAL + OGK_SWEEP

@@ -1848,6 +1848,20 @@ int fused_light_order(long workgroups, int n_sum) { return workgroups <= 512 ? -
 
 }  // namespace
 
+// N_PAR and PAR_OFF are in the generated header only when the problem declares run-time parameters
+namespace {
+template <class G> constexpr auto gen_n_par(int) -> decltype(G::N_PAR) { return G::N_PAR; }
+template <class G> constexpr int gen_n_par(long) { return 0; }
+template <class G> constexpr auto gen_par_off(int) -> decltype(G::PAR_OFF) { return G::PAR_OFF; }
+template <class G> constexpr int gen_par_off(long) { return G::N_CVEC; }
+}  // namespace
+
+extern "C" int ogk_get_par_info(ogk_par_info* out) {
+    out->n_par = gen_n_par<OgGen>(0);
+    out->par_off = gen_par_off<OgGen>(0);
+    return 0;
+}
+
 extern "C" int ogk_get_info(ogk_info* out) {
     out->abi = OGK_ABI;
     out->n_eval_blocks = defect_blocks() + eval_row_blocks();

@@ -99,6 +99,9 @@ struct og_problem_s {
     ogk_module launch;
     double* d_dfrag = nullptr;
     double* d_cvec = nullptr;
+    // run-time parameters: d_cvec[par_off + i], i in [0, n_par): the tail of the constant table (og_set_parameters)
+    int n_cvec = 0, n_par = 0, par_off = 0;
+    double* d_theta = nullptr;          // [n_par] staging of the host-pointer setter
     int64_t dfrag_off[OGK_MAX_PHASE] = {0};
     // staging buffers for the host-pointer entry points
     double* d_x = nullptr;
@@ -588,6 +591,24 @@ int sweep_download(og_problem_s* p, int lo, int hi, double* JT, double* F0) {
 // launch-floor probe (og_probe_launch): a kernel that does nothing, in the geometry asked for
 __global__ void og_probe_kernel(int unused) { (void)unused; }
 
+// Run-time parameters (og_set_parameters_dev, og_parameters_batch_dev): the tail of a constant table is rewritten on the
+// device, one double per thread.  tail[i] = theta[i], i in [0, n_par).
+__global__ void og_par_set_kernel(double* tail, const double* theta, int n_par) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n_par) tail[i] = theta[i];
+}
+
+// The same for `count` lanes of a batch, each with a table of n_cvec doubles of its own whose tail begins at par_off:
+// lane k takes TH[k * n_par + i], or - TH == nullptr - shared[i] (the handle's values) like every other lane.
+__global__ void og_par_lanes_kernel(double* lane_cvec, long n_cvec, int par_off, int n_par, int count, const double* TH,
+                                    const double* shared) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)count * n_par) return;
+    const long k = idx / n_par;
+    const int i = (int)(idx - k * n_par);
+    lane_cvec[k * n_cvec + par_off + i] = TH ? TH[idx] : shared[i];
+}
+
 extern "C" {
 
 const char* og_last_error(void) { return g_error.c_str(); }
@@ -694,6 +715,12 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
               info.m_ineq == desc->m_ineq && info.n_phase == desc->n_phase &&
               info.n_cvec == desc->n_cvec;
     for (int i = 0; ok && i < desc->n_phase; ++i) ok = info.phase_nodes[i] == desc->nodes[i];
+    ogk_par_info par;
+    memset(&par, 0, sizeof par);
+    typedef int (*ogk_get_par_info_fn)(ogk_par_info*);
+    ogk_get_par_info_fn get_par = (ogk_get_par_info_fn)dlsym(mod, "ogk_get_par_info");
+    ok = ok && get_par && get_par(&par) == 0;
+    ok = ok && par.n_par >= 0 && par.par_off >= 0 && par.par_off + par.n_par == info.n_cvec;       // the table's tail
     if (!ok) {
         dlclose(mod);
         return fail(5, "og_problem_create: descriptor does not match the compiled module");
@@ -705,6 +732,9 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
     p->m = info.m;
     p->m_eq = info.m_eq;
     p->m_ineq = info.m_ineq;
+    p->n_cvec = info.n_cvec;
+    p->n_par = par.n_par;
+    p->par_off = par.par_off;
     p->module = mod;
     p->launch.part[0] = launch;
     p->launch.handle[0] = mod;
@@ -772,6 +802,7 @@ int og_problem_create(const og_desc* desc, og_handle* out) {
             e = hipMemcpy(p->d_cvec, desc->cvec, sizeof(double) * (size_t)desc->n_cvec,
                           hipMemcpyHostToDevice);
     }
+    if (e == hipSuccess && p->n_par > 0) e = hipMalloc(&p->d_theta, sizeof(double) * (size_t)p->n_par);
     if (e == hipSuccess) e = hipMalloc(&p->d_x, sizeof(double) * 2 * (size_t)p->n);      // [x | h]
     if (e == hipSuccess) p->d_h = p->d_x + p->n;
     if (e == hipSuccess) e = hipMalloc(&p->d_f0, sizeof(double) * (size_t)p->m);
@@ -821,6 +852,7 @@ void og_problem_destroy(og_handle p) {
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
     hipFree(p->d_cvec);
+    hipFree(p->d_theta);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1346,6 +1378,10 @@ struct og_batch_s {
     double *d_xh = nullptr, *d_f = nullptr, *d_vals = nullptr;
     double *h_up = nullptr, *h_down = nullptr;
     int* h_flags = nullptr;
+    // a module with run-time parameters: every lane's own copy of the constant table ([capacity][n_cvec]; the lane
+    // records' cvec point into it), and [capacity][n_par] staging of the host-pointer og_parameters_batch
+    double* d_cvec = nullptr;
+    double *d_th = nullptr, *h_th = nullptr;
 };
 
 namespace {
@@ -1519,6 +1555,9 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_xh);
     hipFree(b->d_f);
     hipFree(b->d_vals);
+    hipFree(b->d_cvec);
+    hipFree(b->d_th);
+    if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
     if (b->h_flags) hipHostFree(b->h_flags);
@@ -1568,6 +1607,15 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
     if (e == hipSuccess) e = hipHostMalloc(&b->h_up, sizeof(double) * 2 * cap * n, hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc(&b->h_down, sizeof(double) * cap * (nnz + m), hipHostMallocDefault);
     if (e == hipSuccess) e = hipHostMalloc(&b->h_flags, sizeof(int) * OGK_FLAG_WORDS * cap, hipHostMallocDefault);
+    if (p->n_par > 0) {
+        // every lane's own constant table, filled with the handle's (its parameters at their current values)
+        const size_t nc = (size_t)p->n_cvec, np_ = (size_t)p->n_par;
+        if (e == hipSuccess) e = hipMalloc(&b->d_cvec, sizeof(double) * cap * nc);
+        for (size_t k = 0; e == hipSuccess && k < cap; ++k)
+            e = hipMemcpyAsync(b->d_cvec + k * nc, p->d_cvec, sizeof(double) * nc, hipMemcpyDeviceToDevice, p->stream);
+        if (e == hipSuccess) e = hipMalloc(&b->d_th, sizeof(double) * cap * np_);
+        if (e == hipSuccess) e = hipHostMalloc(&b->h_th, sizeof(double) * cap * np_, hipHostMallocDefault);
+    }
     if (e == hipSuccess) {
         // per lane {state: no NaN fill, launches so far: 0}
         std::vector<uint32_t> st(2 * cap);
@@ -1587,6 +1635,7 @@ int og_batch_create(og_handle p, int32_t capacity, const char* batch_part_path, 
                 a.t0 = scr + 2 * b->n_y0;
                 a.z = a.t0 + m;
                 a.trace = nullptr;
+                if (b->d_cvec) a.cvec = b->d_cvec + k * (size_t)p->n_cvec;
                 a.jt = b->d_jt + k * n * m;
                 a.jt_sparse = 1;
                 a.jt_state = b->d_state + 2 * k;
@@ -1696,6 +1745,100 @@ int og_batch_fd_sweep(og_batch b, int32_t count, const double* X, const double* 
     if (!rc) rc = og_batch_fd_sweep_dev(b, count, b->d_xh, b->d_xh + (size_t)b->capacity * (size_t)p->n, d_f, d_vals, p->stream);
     if (rc) return rc;
     return batch_results(b, (size_t)count, in_place, F0, vals, nonfinite);
+}
+
+// ---- run-time parameters (include/ogpsx.h) ----
+int og_parameter_count(og_handle p) { return p ? p->n_par : 0; }
+
+// every lane of batch b takes shared[0 .. n_par) (device), on stream s
+static int batch_lanes_take(og_batch_s* b, const double* shared, hipStream_t s) {
+    const og_problem_s* p = b->p;
+    const long total = (long)b->capacity * p->n_par;
+    hipLaunchKernelGGL(og_par_lanes_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, b->d_cvec, (long)p->n_cvec,
+                       p->par_off, p->n_par, b->capacity, (const double*)nullptr, shared);
+    OG_HIP(hipGetLastError());
+    b->last_stream = s;
+    return 0;
+}
+
+int og_set_parameters_dev(og_handle p, const double* d_theta, void* hip_stream) {
+    if (!p) return fail(1, "og_set_parameters_dev: null handle");
+    if (p->n_par == 0) return d_theta ? fail((int)hipErrorInvalidValue, "og_set_parameters_dev: the module has no parameters") : 0;
+    if (!d_theta) return fail(1, "og_set_parameters_dev: null argument");
+    hipStream_t s = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(og_par_set_kernel, dim3((unsigned)((p->n_par + 63) / 64)), dim3(64), 0, s, p->d_cvec + p->par_off,
+                       d_theta, p->n_par);
+    OG_HIP(hipGetLastError());
+    // a handle-level set reaches everything: every lane of every batch of the handle, from the table just written
+    for (og_batch_s* b : p->batches) {
+        const int rc = batch_lanes_take(b, p->d_cvec + p->par_off, s);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+static int parameter_count_check(const og_problem_s* p, int32_t count, const char* who) {
+    if (count == p->n_par) return 0;
+    return fail((int)hipErrorInvalidValue, std::string(who) + ": count " + std::to_string(count) + ", the module has " +
+                                               std::to_string(p->n_par) + " parameters");
+}
+
+int og_set_parameters(og_handle p, const double* theta, int32_t count) {
+    if (!p) return fail(1, "og_set_parameters: null handle");
+    int rc = parameter_count_check(p, count, "og_set_parameters");
+    if (rc || count == 0) return rc;
+    if (!theta) return fail(1, "og_set_parameters: null argument");
+    OG_HIP(hipSetDevice(p->device));
+    OG_HIP(hipDeviceSynchronize());             // after everything the handle was asked for, on whatever stream
+    OG_HIP(hipMemcpy(p->d_theta, theta, sizeof(double) * (size_t)count, hipMemcpyHostToDevice));
+    rc = og_set_parameters_dev(p, p->d_theta, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_get_parameters(og_handle p, double* theta, int32_t count) {
+    if (!p) return fail(1, "og_get_parameters: null handle");
+    const int rc = parameter_count_check(p, count, "og_get_parameters");
+    if (rc || count == 0) return rc;
+    if (!theta) return fail(1, "og_get_parameters: null argument");
+    OG_HIP(hipSetDevice(p->device));
+    OG_HIP(hipDeviceSynchronize());
+    OG_HIP(hipMemcpy(theta, p->d_cvec + p->par_off, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int og_parameters_batch_dev(og_batch b, int32_t count, const double* d_TH, void* hip_stream) {
+    int rc = batch_check(b, count, "og_parameters_batch_dev");
+    if (rc) return rc;
+    og_problem_s* p = b->p;
+    if (p->n_par == 0)
+        return d_TH ? fail((int)hipErrorInvalidValue, "og_parameters_batch_dev: the module has no parameters") : 0;
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!d_TH) return batch_lanes_take(b, p->d_cvec + p->par_off, s);
+    const long total = (long)count * p->n_par;
+    hipLaunchKernelGGL(og_par_lanes_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, b->d_cvec, (long)p->n_cvec,
+                       p->par_off, p->n_par, (int)count, d_TH, (const double*)nullptr);
+    OG_HIP(hipGetLastError());
+    b->last_stream = s;
+    return 0;
+}
+
+int og_parameters_batch(og_batch b, int32_t count, const double* TH) {
+    int rc = batch_check(b, count, "og_parameters_batch");
+    if (rc) return rc;
+    og_problem_s* p = b->p;
+    OG_HIP(hipSetDevice(p->device));
+    if (TH && p->n_par > 0) {
+        const size_t bytes = sizeof(double) * (size_t)count * (size_t)p->n_par;
+        OG_HIP(hipStreamSynchronize(p->stream));        // (the staging buffers are free again)
+        memcpy(b->h_th, TH, bytes);
+        OG_HIP(hipMemcpyAsync(b->d_th, b->h_th, bytes, hipMemcpyHostToDevice, p->stream));
+    }
+    rc = og_parameters_batch_dev(b, count, (TH && p->n_par > 0) ? b->d_th : TH, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 // ---- the exact Jacobian of a batch (include/ogpsx.h) ----
@@ -2144,6 +2287,15 @@ int og_multi_fd_sweep(og_multi mh, const double* x, const double* hstep, double*
 int og_multi_jt_register_host(og_multi mh, double* JT) {
     if (!mh) return fail(1, "og_multi_jt_register_host: null handle");
     return og_jt_register_host(mh->sub[0], JT, 0, mh->n);
+}
+
+int og_multi_set_parameters(og_multi mh, const double* theta, int32_t count) {
+    if (!mh) return fail(1, "og_multi_set_parameters: null handle");
+    for (og_problem_s* sub : mh->sub) {
+        const int rc = og_set_parameters(sub, theta, count);
+        if (rc) return rc;
+    }
+    return 0;
 }
 
 int og_multi_eval(og_multi mh, const double* x, double* F) {

@@ -42,6 +42,8 @@ class HipEngine:
         self.module_path = build.build_module(self.header, self.digest)
         P = self.program
         self.n, self.m, self.m_eq, self.m_ineq = P.n, P.m, P.m_eq, P.m_ineq
+        # run-time parameters (Problem.parameter): the tail of the constant table, at the values of the trace
+        self.n_par, self.parameter_names = int(P.n_par), tuple(P.par_names)
         self.device = int(device)
 
         self._nodes = (C.c_int32 * len(P.nodes))(*P.nodes)
@@ -52,7 +54,7 @@ class HipEngine:
         self._Dptr = (dp * len(self._D))(*[
             None if (d.shape == (n, n) and np.array_equal(d, _native.lgl(n)[2]))
             else d.ctypes.data_as(dp) for d, n in zip(self._D, P.nodes)])
-        self._cvec = np.ascontiguousarray(P.cvec, dtype=np.float64)
+        self._cvec = np.array(P.cvec, dtype=np.float64)          # (a copy: set_parameters keeps it current, the program stays)
         desc = _native.OgDesc(
             abi_version=_native.OG_ABI_VERSION, device=self.device, n=P.n, m_eq=P.m_eq,
             m_ineq=P.m_ineq, n_phase=len(P.nodes), nodes=self._nodes, D=self._Dptr,
@@ -96,6 +98,50 @@ class HipEngine:
             self.close()
         except Exception:
             pass
+
+    # ------------------------------------------------------------------ run-time parameters
+    def _theta(self, values):
+        if isinstance(values, dict):
+            unknown = [k for k in values if k not in self.parameter_names]
+            if unknown:
+                raise ValueError("unknown parameter %s (declared: %s)" % (", ".join(repr(k) for k in unknown),
+                                                                         ", ".join(self.parameter_names) or "none"))
+            theta = self.get_parameters()
+            for k, v in values.items():
+                theta[self.parameter_names.index(k)] = float(v)
+            return theta
+        theta = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        if theta.size != self.n_par:
+            raise ValueError("%d values for %d parameters" % (theta.size, self.n_par))
+        return theta
+
+    def _forget(self):
+        self._val_key = self._jac_key = None            # what values() / jacobians() remember was at the old parameters
+
+    def set_parameters(self, values):
+        """New values of the run-time parameters - all of them in declaration order, or ``{name: value}`` - on the
+        device (``og_set_parameters``; with ``devices=[...]`` on every sub-handle, ``og_multi_set_parameters``): the
+        same module, no trace, no compiler.  Every lane of every batch of this engine takes them too."""
+        theta = self._theta(values)
+        _native.check(self._lib.og_set_parameters(self._handle, _native.dptr(theta), self.n_par), "og_set_parameters")
+        if self._multi.value:
+            _native.check(self._lib.og_multi_set_parameters(self._multi, _native.dptr(theta), self.n_par),
+                          "og_multi_set_parameters")
+        if self.n_par:
+            self._cvec[self.program.par_off:] = theta
+        self._forget()
+
+    def set_parameters_dev(self, d_theta, stream=0):
+        """``og_set_parameters_dev``: ``d_theta`` is the device address of ``n_par`` doubles (an int from
+        ``torch.Tensor.data_ptr()``); asynchronous on ``stream``, capturable.  The single device's handle only."""
+        _native.check(self._lib.og_set_parameters_dev(self._handle, d_theta, stream), "og_set_parameters_dev")
+        self._forget()
+
+    def get_parameters(self):
+        """The parameter values on the device, in declaration order (``og_get_parameters``)."""
+        theta = np.empty(self.n_par)
+        _native.check(self._lib.og_get_parameters(self._handle, _native.dptr(theta), self.n_par), "og_get_parameters")
+        return theta
 
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
@@ -308,6 +354,27 @@ class BatchSweep:
     @property
     def nnz(self):
         return int(self.pattern[0][-1])
+
+    # -------------------------------------------------------------- run-time parameters
+    def set_parameters(self, TH):
+        """Per-lane values of the engine's run-time parameters: ``TH[count, n_par]`` in declaration order - lane ``k`` of
+        the later calls works at ``TH[k]``; lanes ``count .. capacity - 1`` keep what they had - or ``None``: every lane
+        takes the engine's current values (``og_parameters_batch``).  The lanes hold them until the next such call or
+        the next ``HipEngine.set_parameters``."""
+        if TH is None:
+            _native.check(self._lib.og_parameters_batch(self._handle, self.capacity, None), "og_parameters_batch")
+            return
+        TH = np.ascontiguousarray(TH, dtype=np.float64)
+        if TH.ndim != 2 or TH.shape[1] != self.engine.n_par or not 1 <= TH.shape[0] <= self.capacity:
+            raise ValueError("BatchSweep: parameters must have shape [1..%d, %d], got %s"
+                             % (self.capacity, self.engine.n_par, TH.shape))
+        _native.check(self._lib.og_parameters_batch(self._handle, TH.shape[0], _native.dptr(TH)), "og_parameters_batch")
+
+    def set_parameters_dev(self, count, d_TH, stream=0):
+        """``og_parameters_batch_dev``: ``d_TH`` ``[count, n_par]`` on the device (an int from
+        ``torch.Tensor.data_ptr()``), or None for the engine's values in every lane; asynchronous, capturable."""
+        _native.check(self._lib.og_parameters_batch_dev(self._handle, int(count), d_TH, stream),
+                      "og_parameters_batch_dev")
 
     def _points(self, P, what="P"):
         P = np.ascontiguousarray(P, dtype=np.float64)

@@ -60,7 +60,8 @@ class BatchResult:
     ``rows[indptr[j]:indptr[j + 1]]``.  ``nonfinite[B]`` counts the non-finite rows of ``F`` per point.
     ``jacobian`` says what ``values`` and ``gradient`` hold: ``None`` (no Jacobians were asked for), ``"fd"`` (forward
     differences) or ``"exact"`` (forward-mode derivatives of the traced callbacks; there is no step, ``steps`` is
-    ``None``)."""
+    ``None``).  ``parameters[B, n_par]`` are the values of the problem's run-time parameters each point was evaluated
+    with, in declaration order (``n_par`` is 0 for a problem that declares none)."""
 
     def __init__(self, F, m_eq):
         F = np.asarray(F, dtype=float)
@@ -71,6 +72,7 @@ class BatchResult:
         self.nonfinite = np.sum(~np.isfinite(F), axis=1).astype(np.int32)
         self.gradient = self.steps = self.values = self.pattern = None
         self.jacobian = None
+        self.parameters = None          # [B, n_par]: the parameter values every point was evaluated with
 
     def __len__(self):
         return self.cost.shape[0]
@@ -143,6 +145,112 @@ class Problem:
         self.inequality = None
         for i in range(self.number_of_section):
             self.set_time_final(i, time_init[i + 1])
+        self._par_names = []            # run-time parameters in declaration order (parameter / set_parameter)
+        self._par_values = []           # their current values: the list every Parameter of this problem reads
+
+    # ------------------------------------------------------------------ run-time parameters
+    def parameter(self, name, value):
+        """Declare a scalar model constant that can change WITHOUT a new trace and a new module and return it
+        (:class:`opengoddard_amd.trace.Parameter`): ``obj.T_max = prob.parameter("T_max", 3.5)``.  The callbacks use it
+        like the number it replaces; in the compiled module it is entry ``index`` (the order of declaration) of a table
+        on the device that ``set_parameter`` rewrites, so a trade study or a continuation in it re-solves on the same
+        kernels, and ``evaluate_batch(..., parameters=...)`` gives every point of a batch values of its own.  The
+        reference has no counterpart (its constants are attributes of ``obj``, read by Python at every call).
+
+        Outside the callbacks a parameter is its current value (guesses, bounds, plots).  Set-up code is NOT followed:
+        ``obj.c = 0.5 * np.sqrt(obj.g0)`` in ``__init__`` is a float at the value of that moment - such a quantity is a
+        parameter itself, or it is computed inside the callback.  Scalars only; table values and interpolation knots
+        stay constants.  A parameter no callback reads gives a ``RuntimeWarning`` when the problem is traced."""
+        name = str(name)
+        if name in self._par_names:
+            raise ValueError("parameter %r is already declared" % name)
+        self._par_names.append(name)
+        self._par_values.append(float(value))
+        return _tr.Parameter(name, len(self._par_names) - 1, self._par_values)
+
+    @property
+    def parameters(self):
+        """``{name: current value}`` of the declared parameters, in declaration order."""
+        return dict(zip(self._par_names, self._par_values))
+
+    def set_parameters(self, values):
+        """New values for declared parameters: ``{name: value}``, or all of them as a sequence in declaration order.
+        A live engine (of an earlier ``solve`` / ``evaluate_batch``) is updated too, every lane of its batches
+        included; the next ``solve`` loads the same module - no compiler runs - and starts from ``prob.p``."""
+        if isinstance(values, dict):
+            unknown = [k for k in values if k not in self._par_names]
+            if unknown:
+                raise ValueError("unknown parameter%s %s (declared: %s)" % ("s" if len(unknown) > 1 else "",
+                                 ", ".join(repr(k) for k in unknown), ", ".join(self._par_names) or "none"))
+            items = [(self._par_names.index(k), float(v)) for k, v in values.items()]
+        else:
+            vec = np.asarray(values, dtype=float).reshape(-1)
+            if vec.size != len(self._par_names):
+                raise ValueError("%d values for %d declared parameters" % (vec.size, len(self._par_names)))
+            items = list(enumerate(float(v) for v in vec))
+        for i, v in items:
+            self._par_values[i] = v                      # (in place: the Parameter objects read this list)
+        engine = getattr(self, "_engine", None)
+        closed = engine is not None and hasattr(engine, "_handle") and not engine._handle.value      # (a closed HipEngine)
+        if engine is not None and items and hasattr(engine, "set_parameters") and not closed:
+            engine.set_parameters(list(self._par_values))
+
+    def set_parameter(self, name, value):
+        """``set_parameters({name: value})``."""
+        self.set_parameters({name: value})
+
+    def _batch_parameters(self, parameters, B):
+        """``parameters`` of ``evaluate_batch`` -> ``[B', n_par]`` array (B' = B, or any when B == 1), or None."""
+        n_par = len(self._par_names)
+        if parameters is None:
+            return None
+        if n_par == 0:
+            raise ValueError("parameters= given, but this problem declares no parameter")
+        if isinstance(parameters, dict):
+            unknown = [k for k in parameters if k not in self._par_names]
+            if unknown:
+                raise ValueError("unknown parameter%s %s (declared: %s)" % ("s" if len(unknown) > 1 else "",
+                                 ", ".join(repr(k) for k in unknown), ", ".join(self._par_names)))
+            cols = {k: np.asarray(v, dtype=float) for k, v in parameters.items()}
+            sizes = {c.size for c in cols.values() if c.ndim > 0}
+            if any(c.ndim > 1 for c in cols.values()) or len(sizes) > 1:
+                raise ValueError("parameters: every entry must be a scalar or one [B] array")
+            rows = sizes.pop() if sizes else B
+            TH = np.tile(np.asarray(self._par_values, dtype=float), (rows, 1))
+            for k, c in cols.items():
+                TH[:, self._par_names.index(k)] = c
+        else:
+            TH = np.array(parameters, dtype=float)
+            if TH.ndim != 2 or TH.shape[1] != n_par:
+                raise ValueError("parameters must have shape [B, %d] (declaration order: %s), got %s"
+                                 % (n_par, ", ".join(self._par_names), TH.shape))
+        if TH.shape[0] != B and B != 1:
+            raise ValueError("parameters has %d rows for %d points" % (TH.shape[0], B))
+        if TH.shape[0] < 1:
+            raise ValueError("parameters holds no row")
+        return np.ascontiguousarray(TH)
+
+    def parameter_sensitivity(self, obj, p=None):
+        """``dF/dtheta`` of ``F = [cost | c_eq | c_ineq]`` at the decision vector ``p`` (default ``prob.p``) and the
+        current parameter values, shape ``[n_par, m]``, by forward differences: ONE batched evaluation of ``n_par + 1``
+        lanes at the same point - lane 0 at ``theta``, lane ``k + 1`` at ``theta + h_k e_k`` with SciPy's step rule
+        (``og_fd_step`` without bounds) - and row ``k`` is ``(F(theta + h_k e_k) - F(theta)) / h_k``, formed on the host.
+        The lanes are not chunked: ``evaluate_batch`` re-creates the problem's batch with ``n_par + 1`` lanes when the one
+        it has is smaller (a lane owns a dense n x m matrix on the device).  Exact derivatives with respect to parameters
+        do not exist."""
+        from . import _native
+        n_par = len(self._par_names)
+        if n_par == 0:
+            raise ValueError("this problem declares no parameter")
+        theta = np.asarray(self._par_values, dtype=float)
+        inf = np.full(n_par, np.inf)
+        h = _native.fd_step(theta, -inf, inf)
+        TH = np.tile(theta, (n_par + 1, 1))
+        TH[np.arange(1, n_par + 1), np.arange(n_par)] += h
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(1, -1)
+        res = self.evaluate_batch(obj, point, parameters=TH)
+        F = np.hstack([res.cost[:, None], res.equality, res.inequality])
+        return (F[1:] - F[0]) / h[:, None]
 
     @staticmethod
     def _phase_grid(ta, tb, tau):
@@ -544,7 +652,7 @@ class Problem:
             self.iterator += 1
 
     # ------------------------------------------------------------------ many points at once
-    def evaluate_batch(self, obj, points, jacobian=False):
+    def evaluate_batch(self, obj, points, jacobian=False, parameters=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -559,7 +667,14 @@ class Problem:
 
         The engine of an earlier ``solve`` is reused when there is one.  A stand-in engine (``ENGINE_FACTORY``) without
         a ``batch`` method is served point by point through its ``values`` / ``jacobians`` (``exact_stacked`` for the
-        exact Jacobians: an engine without one has no exact mode, a ``ValueError``)."""
+        exact Jacobians: an engine without one has no exact mode, a ``ValueError``).
+
+        ``parameters`` gives every point values of the declared run-time parameters of its own (a dispersion in the
+        vehicle, a scan of a constant): a ``[B, n_par]`` array in declaration order, or a dict from name to a scalar or a
+        ``[B]`` array (names not given keep their current value).  ``None``: every point is evaluated at the current
+        values.  ``points`` with ONE row is repeated for every row of ``parameters`` - a scan at one trajectory.  A
+        stand-in engine is served point by point through its ``set_parameters`` (without one: ``ValueError``).
+        ``BatchResult.parameters`` holds the values used."""
         points = np.asarray(points, dtype=float)
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
@@ -574,35 +689,50 @@ class Problem:
                 raise ValueError("jacobian must be 'fd' or 'exact', got %r" % (jacobian,))
         else:
             jacobian = "fd" if jacobian else None
+        TH = self._batch_parameters(parameters, points.shape[0])
 
         engine = getattr(self, "_engine", None)
         if engine is None:
             engine = ENGINE_FACTORY(self, obj) if ENGINE_FACTORY is not None else _default_engine(self, obj)
             self._engine = engine
             self._engine_of_batch = True         # (solve closes an engine that was only made for batches)
+        if TH is not None and TH.shape[0] != points.shape[0]:
+            points = np.repeat(points, TH.shape[0], axis=0)          # one trajectory, scanned
         points = np.ascontiguousarray(points)
         B, n = points.shape
+        used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
         if jacobian == "exact" and not hasattr(engine, "exact_stacked"):
             raise ValueError("this engine has no exact-Jacobian mode")
 
         if not hasattr(engine, "batch"):
+            if TH is not None and not hasattr(engine, "set_parameters"):
+                raise ValueError("this engine cannot change parameters (it has no set_parameters)")
+
+            def lanes():
+                for k, p in enumerate(points):
+                    if TH is not None:
+                        engine.set_parameters(TH[k])
+                    yield p
             saved = self.p
             try:
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
-                            for p in points]
-                    return BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[0])[1]).size))
+                            for p in lanes()]
+                    # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
+                    res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
+                    res.parameters = used
+                    return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
-                    for p in points:
+                    for p in lanes():
                         F0, JT = engine.exact_stacked(p)
                         rows.append(np.array(F0, dtype=float, copy=True))
                         dense.append(np.array(JT, dtype=float, copy=True))
-                    m_eq = int(np.atleast_1d(engine.values(points[0])[1]).size)
+                    m_eq = int(np.atleast_1d(engine.values(points[-1])[1]).size)
                 else:
-                    for p in points:
+                    for p in lanes():
                         (grad, jeq, jineq), h = engine.jacobians(p, lb, ub)
                         rows.append(np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)]))
                         dense.append(np.vstack([np.atleast_2d(grad), np.atleast_2d(jeq), np.atleast_2d(jineq)]).T.copy())
@@ -610,7 +740,10 @@ class Problem:
                     m_eq = int(np.atleast_2d(jeq).shape[0])
             finally:
                 self.p = saved
+                if TH is not None:
+                    engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
+            res.parameters = used
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -625,14 +758,20 @@ class Problem:
             if batch is not None:
                 batch.close()
             batch = self._batch = engine.batch(B)
+        if getattr(engine, "n_par", 0):
+            # (None binds the handle's values to every lane: per-lane values of an earlier call do not leak into this one)
+            batch.set_parameters(TH)
         if not jacobian:
-            return BatchResult(batch.values(points), engine.m_eq)
+            res = BatchResult(batch.values(points), engine.m_eq)
+            res.parameters = used
+            return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
             H = None
         else:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
+        res.parameters = used
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost

@@ -19,6 +19,7 @@ Anything else raises :class:`TraceError` - there is no silent CPU fallback.
 from __future__ import annotations
 
 import numbers
+import operator
 import os
 import threading
 
@@ -27,6 +28,10 @@ import numpy as np
 
 # what to write instead, by what the message is about (there is no CPU fallback: the error has to say how to go on)
 _HINTS = (
+    # (first: such a message also names the control flow / float() it met)
+    ("a parameter is a run-time value", "np.where / np.maximum / np.minimum for a switch on it, np.sqrt / np.exp / ... in "
+                                        "place of the math module; a size, an index or a branch of the PROGRAM cannot "
+                                        "depend on it - such a quantity stays a plain number"),
     ("control flow", "use np.where(condition, a, b) (both branches are evaluated), np.maximum / np.minimum / np.clip, or a "
                      "mask assignment `v[v < lo] = lo`; a condition on a CONSTANT (problem data, a node count) is fine"),
     ("NumPy routine", "traceable are the elementwise ufuncs, np.where / clip / hstack / concatenate / append / stack / vstack, "
@@ -99,6 +104,7 @@ class Graph:
         self.cvecs = []          # constant vectors referenced by ("cvec", i)
         self._cvec_index = {}
         self.tables = []         # linear lookup tables: (cvec id of x grid, cvec id of y, mode, lo, hi)
+        self.par_table = None    # the traced problem's parameter values (Parameter._table): ("par", i) reads entry i
 
     def add(self, node, length, isbool=False):
         key = (node, length, isbool)
@@ -115,6 +121,13 @@ class Graph:
         value = float(value)
         # key on the bit pattern so that -0.0 and 0.0, and NaNs, stay distinct / hashable
         return self.add(("const", np.float64(value).tobytes()), None)
+
+    def par(self, param):
+        """The scalar leaf of a declared run-time parameter.  Its VALUE is never looked at: not here, not by
+        ``concrete_value``, not by the lowering."""
+        if param._table is not self.par_table:
+            raise TraceError("parameter %r was declared on another Problem than the one being traced" % (param.name,))
+        return self.add(("par", int(param.index)), None)
 
     def cvec(self, arr):
         arr = np.ascontiguousarray(arr, dtype=np.float64)
@@ -352,37 +365,41 @@ class Sym:
         """NumPy value when this expression is a constant of the trace (see :func:`concrete_value`), else None."""
         return concrete_value(self.g, self.id)
 
+    def _of_parameter(self):
+        """What to add to an error about this value when it depends on a declared parameter (else "")."""
+        return _PARAMETER_WHY if reads_parameter(self.g, self.id) else ""
+
     def __bool__(self):
         v = self._concrete()
         if v is not None:
             return bool(v)                               # (NumPy's own rule for arrays of more than one element)
         raise TraceError("Python control flow on a traced value (if/while/and/or on the decision "
-                         "variables) cannot be turned into a GPU kernel")
+                         "variables) cannot be turned into a GPU kernel" + self._of_parameter())
 
     def __float__(self):
         v = self._concrete()
         if v is not None:
             return float(v)
-        raise TraceError("float() of a traced value: the callback needs a concrete number")
+        raise TraceError("float() of a traced value: the callback needs a concrete number" + self._of_parameter())
 
     def __int__(self):
         v = self._concrete()
         if v is not None:
             return int(v)
-        raise TraceError("int() of a traced value: the callback needs a concrete number")
+        raise TraceError("int() of a traced value: the callback needs a concrete number" + self._of_parameter())
 
     def __index__(self):
         v = self._concrete()
         if v is not None and np.ndim(v) == 0 and float(v) == int(v):
             return int(v)
-        raise TraceError("a traced value used as an index: the callback needs a concrete integer")
+        raise TraceError("a traced value used as an index: the callback needs a concrete integer" + self._of_parameter())
 
     def __array__(self, *a, **k):
         v = self._concrete()
         if v is not None:
             return np.array(v, *a, **{key: val for key, val in k.items() if key == "dtype"})
         raise TraceError("a traced value was passed to a NumPy routine the tracer does not "
-                         "understand (only elementwise ufuncs, hstack/concatenate/append, where)")
+                         "understand (only elementwise ufuncs, hstack/concatenate/append, where)" + self._of_parameter())
 
     def __repr__(self):
         return "Sym(#%d, len=%s)" % (self.id, self.length)
@@ -429,6 +446,8 @@ class Sym:
             if other.g is not self.g:
                 raise TraceError("mixing values from two different traces")
             return other
+        if isinstance(other, Parameter):
+            return Sym(self.g, self.g.par(other))        # (never its value: set_parameter would silently do nothing)
         if isinstance(other, (numbers.Real, np.bool_)):
             return Sym(self.g, self.g.const(other))
         if isinstance(other, np.ndarray):
@@ -1416,6 +1435,8 @@ class SymMat:
     def _operand_rows(self, other):
         """The other operand of an elementwise operation, row by row (NumPy broadcasting against (r, c))."""
         r, c = self.shape
+        if isinstance(other, Parameter):
+            other = Sym(self.g, self.g.par(other))
         if isinstance(other, SymMat):
             if other.shape == (r, c):
                 return other.rows
@@ -1540,6 +1561,157 @@ class SymMat:
     def prod(self, axis=None): return self._reduce("prod", axis)
     def min(self, axis=None): return self._reduce("min", axis)
     def max(self, axis=None): return self._reduce("max", axis)
+
+
+# ----------------------------------------------------------------------------- run-time parameters
+_PARAMETER_WHY = (" - the value depends on a declared parameter, and a parameter is a run-time value: use np.where / "
+                  "np.sqrt ... on it")
+
+
+def _trace_children(node):
+    """Ids of the trace-graph nodes a node is computed from."""
+    kind = node[0]
+    if kind in ("un", "interp", "mv"):
+        return (node[2],)
+    if kind in ("bin", "cmp", "logic"):
+        return node[2:4]
+    if kind == "where":
+        return node[1:4]
+    if kind in ("idx", "slice", "seqsum"):
+        return (node[1],)
+    return node[1] if kind == "cat" else ()
+
+
+def reads_parameter(g, nid):
+    """Does node ``nid`` depend on a declared parameter?  (Only error messages ask.)"""
+    seen, stack = set(), [nid]
+    while stack:
+        cur = stack.pop()
+        if cur in seen:
+            continue
+        seen.add(cur)
+        node = g.nodes[cur]
+        if node[0] == "par":
+            return True
+        stack.extend(_trace_children(node))
+    return False
+
+
+def _tracing_graph():
+    """The graph of the trace that is running on THIS thread, or None."""
+    if _ACTIVE_GRAPH is not None and threading.get_ident() == _TRACING_THREAD:
+        return _ACTIVE_GRAPH
+    return None
+
+
+def _plain(v, depth=0):
+    """``v`` with every Parameter in it (lists and tuples looked into) replaced by what it stands for right now."""
+    if isinstance(v, Parameter):
+        return v._now()
+    if isinstance(v, (list, tuple)) and depth < 3 and any(isinstance(it, (Parameter, list, tuple)) for it in v):
+        return type(v)(_plain(it, depth + 1) for it in v)
+    return v
+
+
+def _par_op(fn, reflected=False):
+    def op(self, other):
+        a, b = self._now(), _plain(other)
+        return fn(b, a) if reflected else fn(a, b)
+    return op
+
+
+class Parameter:
+    """A named scalar constant of a problem that can be changed WITHOUT a new trace and a new module
+    (``Problem.parameter`` / ``Problem.set_parameter``).
+
+    Outside a trace it is its current value: arithmetic and NumPy functions on it give plain floats, ``float(p)``,
+    ``math.sqrt(p)`` and ``if p > 0:`` work - guesses, bounds, plots and a callback run on plain arrays see a number.
+    While the callbacks are traced (on the tracing thread) it is a traced scalar leaf, entry ``index`` of the
+    program's parameter table: every operator, its reflected form, every ufunc and ``np.where`` on it give traced
+    values, and whatever needs a concrete number then - ``float(p)``, ``int(p)``, ``math.sqrt(p)``, ``if p > 0:``, an
+    index, a length - raises :class:`TraceError`.  It is not a ``float``: a float would be baked into the module and
+    later ``set_parameter`` calls would silently do nothing.
+
+    Only what the CALLBACKS compute from it is followed.  ``obj.c = 0.5 * np.sqrt(obj.g0)`` in set-up code is a float
+    at the value of that moment; such a quantity is a parameter itself, or it is computed inside the callback."""
+
+    __array_priority__ = 2000.0
+    __slots__ = ("name", "index", "_table")
+
+    def __init__(self, name, index, table):
+        self.name, self.index, self._table = str(name), int(index), table
+
+    @property
+    def value(self):
+        return float(self._table[self.index])
+
+    def _now(self):
+        """The traced leaf while a trace runs on this thread, else the current value."""
+        g = _tracing_graph()
+        return self.value if g is None else Sym(g, g.par(self))
+
+    def _number(self, what):
+        if _tracing_graph() is not None:
+            raise TraceError("%s of parameter %r: a parameter is a run-time value: use np.where / np.sqrt ... on it, "
+                             "the callback cannot have its number" % (what, self.name))
+        return self.value
+
+    def __repr__(self):
+        return "Parameter(%r, %r)" % (self.name, self.value)
+
+    def __float__(self):
+        return self._number("float()")
+
+    def __int__(self):
+        return int(self._number("int()"))
+
+    def __index__(self):
+        v = self._number("an index or a length made")
+        if v != int(v):
+            raise TypeError("parameter %r = %r cannot be used as an integer" % (self.name, v))
+        return int(v)
+
+    def __bool__(self):
+        return bool(self._number("Python control flow on the value"))
+
+    def __array__(self, *a, **k):
+        return np.array(self._number("a plain array made"), *a, **{key: val for key, val in k.items() if key == "dtype"})
+
+    def __round__(self, ndigits=None):
+        return round(self._number("round()"), ndigits)
+
+    def __neg__(self): return -self._now()
+    def __pos__(self): return +self._now()
+    def __abs__(self): return abs(self._now())
+    __add__ = _par_op(operator.add)
+    __radd__ = _par_op(operator.add, True)
+    __sub__ = _par_op(operator.sub)
+    __rsub__ = _par_op(operator.sub, True)
+    __mul__ = _par_op(operator.mul)
+    __rmul__ = _par_op(operator.mul, True)
+    __truediv__ = _par_op(operator.truediv)
+    __rtruediv__ = _par_op(operator.truediv, True)
+    __pow__ = _par_op(operator.pow)
+    __rpow__ = _par_op(operator.pow, True)
+    __mod__ = _par_op(operator.mod)
+    __rmod__ = _par_op(operator.mod, True)
+    __floordiv__ = _par_op(operator.floordiv)       # (outside a trace; a traced value has no floor division: TypeError)
+    __rfloordiv__ = _par_op(operator.floordiv, True)
+    __divmod__ = _par_op(divmod)
+    __rdivmod__ = _par_op(divmod, True)
+    __lt__ = _par_op(operator.lt)
+    __le__ = _par_op(operator.le)
+    __gt__ = _par_op(operator.gt)
+    __ge__ = _par_op(operator.ge)
+    __eq__ = _par_op(operator.eq)
+    __ne__ = _par_op(operator.ne)
+    __hash__ = None                                     # (== is the value's, or a traced comparison)
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        return getattr(ufunc, method)(*_plain(inputs), **{k: _plain(v) for k, v in kwargs.items()})
+
+    def __array_function__(self, func, types, args, kwargs):
+        return func(*_plain(args), **{k: _plain(v) for k, v in kwargs.items()})
 
 
 # ----------------------------------------------------------------------------- NumPy constructors while tracing
