@@ -370,6 +370,37 @@ int og_parameters_batch_dev(og_batch b, int32_t count, const double* d_TH, void*
 int og_parameters_batch(og_batch b, int32_t count, const double* TH);
 int og_multi_set_parameters(og_multi mh, const double* theta, int32_t count);
 
+/* ---- exact dF/dtheta for the run-time parameters ------------------------------------------------
+ * dF[k][r] = d F_r / d theta_k of F = [cost | c_eq | c_ineq], [n_par][m] row-major and dense, by forward-mode
+ * differentiation of the traced callbacks with the unit seed on the parameter's table entry (as og_jacobian_exact has it
+ * on a decision variable): no step and no forward-difference noise.  Every call writes all n_par * m doubles, an exact
+ * +0.0 wherever the structure says the row cannot read the parameter (opengoddard_amd.codegen.parameter_sparsity).
+ * Load rule: the kernels live in a part of the callback module of its own (par_part_path:
+ * opengoddard_amd.build.build_parameter_part).  og_parameter_jacobian_load loads it once per handle - a later call is a
+ * no-op and may pass NULL - and og_problem_destroy closes it; error 4: the part is missing or cannot be loaded, 5: it
+ * belongs to another module.  The other four fail with error 4 while it is not loaded, and all five with error 1 (and a
+ * message in og_last_error) on a handle whose module has no parameters.
+ * og_parameter_jacobian_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own
+ * array when d_F0 is NULL; og_nonfinite_rows counts its non-finite rows) and the derivative kernel, one workgroup per
+ * parameter.  Asynchronous and capturable like og_set_parameters_dev: a captured graph {og_set_parameters_dev,
+ * og_parameter_jacobian_dev} replays on new contents of d_theta and d_x.  No J_T is written and no registered buffer's
+ * bookkeeping moves.  A non-finite parameter gives what the dual-number rules give (NaN where the parameter enters a
+ * product); the next call at finite values is clean.
+ * og_parameter_jacobian: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane k works at X[k] and at the lane's own parameters (og_parameters_batch*), and writes
+ * dF[k][n_par][m] and F0[k][m] (d_F0 / F0 may be NULL); bit for bit the single-point call at that point and those
+ * values.  Three launches whatever count is: bind, the batched evaluation, the derivative kernel.  Lanes count ..
+ * capacity-1, their slices of the output and every lane's J_T with its state words are not touched.
+ * A multi-device handle (og_multi_*) has no form of this call and does not split it: the result is n_par * m doubles, and
+ * the handle of the first device serves it (with og_multi_set_parameters keeping its parameters in step).
+ * No reference counterpart: the reference has no derivative with respect to a model constant at all. */
+int og_parameter_jacobian_load(og_handle h, const char* par_part_path);
+int og_parameter_jacobian_dev(og_handle h, const double* d_x, double* d_dF, double* d_F0, void* hip_stream);
+int og_parameter_jacobian(og_handle h, const double* x, double* dF, double* F0);
+int og_parameter_jacobian_batch_dev(og_batch b, int32_t count, const double* d_X, double* d_F0, double* d_dF,
+                                    void* hip_stream);
+int og_parameter_jacobian_batch(og_batch b, int32_t count, const double* X, double* F0, double* dF);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

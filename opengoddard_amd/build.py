@@ -70,7 +70,7 @@ def _core_sources():
 
 
 def _kernel_sources():
-    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h")]
+    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -186,6 +186,21 @@ def build_batch_exact_part(header_source, force=False):
     batches evaluations or FD sweeps only builds and loads what they did before.  Built when an exact Jacobian of a
     batch is first asked for (``BatchSweep.exact``)."""
     return _build_on_demand_part(header_source, BATCH_EXACT_PART, batch_exact_part_path, force)
+
+
+PARAMETER_PART = 6              # OGK_PART_PAR, <module>.par.so: exact dF/dtheta for run-time parameters
+
+
+def parameter_part_path(out):
+    return out[:-3] + ".par.so"
+
+
+def build_parameter_part(header_source, force=False):
+    """``ogk_exact_par`` / ``ogk_exact_par_batch`` (``OGK_PART=6``) -> path of ``<module>.par.so``.  A part of its own,
+    built when an exact parameter Jacobian is first asked for (``HipEngine.parameter_jacobian``,
+    ``BatchSweep.parameter_jacobian``): the module and the two batch parts are what they were, and a user who never asks
+    builds and loads what they did before."""
+    return _build_on_demand_part(header_source, PARAMETER_PART, parameter_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

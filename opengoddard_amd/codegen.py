@@ -574,6 +574,10 @@ class _Emitter:
                 rhs = "x(%s)" % self._idx(node[1], node[2], var)
             elif tag == "C":
                 rhs = _cdouble(node[1])
+            elif tag == "CV" and node[1] == self.P.par_table and node[3] == 0:
+                # a run-time parameter: through the hook of the parameter section (cv[i], or cv[i] with a unit
+                # derivative when the accessor carries a parameter seed)
+                rhs = "par_leaf(x, cv, %d, 0)" % (self.P.cvec_off[node[1]] + node[2])
             elif tag == "CV":
                 rhs = "cv[%s]" % self._idx(self.P.cvec_off[node[1]] + node[2], node[3], var)
             elif tag == "un":
@@ -943,6 +947,87 @@ class SweepPlan:
         return {item: hi - lo + i for i, item in enumerate(self.items[j])}
 
 
+def _parameters_read(P, eid):
+    """Indices of the run-time parameters the element ``eid`` reads (through the terms of sums too)."""
+    if not P.n_par:
+        return set()
+    return {leaf[2] for leaf in _leaves(P.eg, eid, ("CV",)) if leaf[1] == P.par_table and leaf[3] == 0}
+
+
+class ParameterPlan:
+    """Which rows of F read which run-time parameter, from the graph (as ``SweepPlan`` says it for ``x``).  A parameter
+    leaf does not depend on the element index, so a group's output reads a parameter at every element or at none::
+
+        rows[k]     the row groups whose value reads parameter k
+        slots[k]    [(slot, defect group, reads)] the collocation slots (states) whose defect rows read it: bit 0 of
+                    ``reads`` - the dynamics term does (``tail_one``), bit 1 - the collocation operand does
+                    (``mv_operand``: a state's unit that is a parameter); the row then also gets D times the operand's
+                    derivative
+        entries[k]  how many entries of dF/dtheta_k that is: the row groups' lengths, then the slots' node counts
+
+    ``parameter_sparsity`` and the header's work lists (``_parameter_section``) are both readers of it."""
+
+    def __init__(self, P):
+        self.rows = [[] for _ in range(P.n_par)]
+        self.slots = [[] for _ in range(P.n_par)]
+        for gi, g in enumerate(P.groups):
+            if g.kind == "rows":
+                for k in sorted(_parameters_read(P, g.outputs[0][1])):
+                    self.rows[k].append(gi)
+                continue
+            for s, si in enumerate(g.mv_slots):
+                tail, operand = _parameters_read(P, g.tails[s]), _parameters_read(P, P.mv[si].operand)
+                for k in sorted(tail | operand):
+                    self.slots[k].append((si, gi, int(k in tail) | (int(k in operand) << 1)))
+        self.entries = [sum(P.groups[gi].length for gi in self.rows[k]) + sum(P.mv[si].length for si, _, _ in self.slots[k])
+                        for k in range(P.n_par)]
+
+
+def parameter_sparsity(P):
+    """Static pattern of ``dF/dtheta``: bool ``[n_par, m]``, entry ``[k, r]`` set when row r of F can depend on run-time
+    parameter k.  Every other entry of ``og_parameter_jacobian`` (include/ogpsx.h) is an exact ``+0.0``."""
+    plan = ParameterPlan(P)
+    out = np.zeros((P.n_par, P.m), dtype=bool)
+    for k in range(P.n_par):
+        for gi in plan.rows[k]:
+            g = P.groups[gi]
+            out[k, g.outputs[0][0]:g.outputs[0][0] + g.length] = True
+        for si, gi, _ in plan.slots[k]:
+            g = P.groups[gi]
+            row0 = g.outputs[si - g.mv_slots[0]][0]
+            out[k, row0:row0 + g.length] = True
+    return out
+
+
+def _parameter_section(P):
+    """The header's parameter section (only a header with ``N_PAR > 0`` has one): the hook every parameter leaf is read
+    through, and per parameter the work lists of ``dF/dtheta`` (``ParameterPlan``; csrc/og_par.h walks them)."""
+    plan = ParameterPlan(P)
+    flat_rows = [gi for k in range(P.n_par) for gi in plan.rows[k]]
+    flat_slots = [rec for k in range(P.n_par) for rec in plan.slots[k]]
+    return ["    // ---- run-time parameters: cv[PAR_OFF + i].  A parameter leaf is read through par_leaf: the table entry, the",
+            "    // same bits as the bare subscript - or, for an accessor with a member par_seed (the table index of the",
+            "    // parameter a derivative is taken along; csrc/og_par.h), the entry with a unit derivative on that index",
+            "#define OG_GEN_HAS_PAR 1",
+            "    template <class X> OG_HDI static auto par_leaf(const X& x, const double* cv, const int i, int) -> "
+            "decltype((void)x.par_seed, typename X::scalar()) {",
+            "        return typename X::scalar(cv[i], i == x.par_seed ? 1.0 : 0.0);",
+            "    }",
+            "    template <class X> OG_HDI static typename X::scalar par_leaf(const X&, const double* cv, const int i, long) "
+            "{ return cv[i]; }",
+            "    // dF/dtheta_k, work lists: the row groups PAR_ROW_G(PAR_ROW_PTR(k) ..) - every element of each is one entry, in",
+            "    // the form item_value takes - then the collocation slots PAR_SLOT(PAR_SLOT_PTR(k) ..) of group PAR_SLOT_G, one",
+            "    // entry per node; PAR_SLOT_READS bit 0: the dynamics term reads the parameter, bit 1: the operand does",
+            _int_table("PAR_ROW_PTR", _offsets(len(r) for r in plan.rows)),
+            _int_table("PAR_ROW_G", flat_rows),
+            _int_table("PAR_SLOT_PTR", _offsets(len(r) for r in plan.slots)),
+            _int_table("PAR_SLOT", [si for si, _, _ in flat_slots]),
+            _int_table("PAR_SLOT_G", [gi for _, gi, _ in flat_slots]),
+            _int_table("PAR_SLOT_READS", [rd for _, _, rd in flat_slots]),
+            _int_table("PAR_ENTRIES", plan.entries),
+            "    static constexpr int PAR_MAX_ENTRIES = %d;" % max(plan.entries + [0])]
+
+
 def sparsity(P):
     """Static pattern of the transposed Jacobian: ``(indptr, rows)`` with ``rows[indptr[j]:indptr[j+1]]`` the
     rows of F that can depend on p[j] - for column j first the collocation block its state slice owns
@@ -1158,7 +1243,7 @@ def emit_header(P):
     beyond og_math.h).  Raises ``LimitError`` for a program beyond the limits of a module (``check_limits``)."""
     check_limits(P)
     em, plan = _Emitter(P), SweepPlan(P)
-    sections = [_constants(P, plan),
+    sections = [_constants(P, plan)] + ([_parameter_section(P)] if P.n_par else []) + [
                 _emit_functions(em, P),         # (finds the sequential sums: before term_functions and the records)
                 em.term_functions(),
                 _dispatchers(P, plan),

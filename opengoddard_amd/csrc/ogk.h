@@ -46,7 +46,15 @@ enum ogk_mode {
     OGK_BATCH_EXACT = 14    // OGK_EXACT for `count` lanes
 };
 
-// The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART).
+// The two modes of the parameter part (OGK_PART_PAR; macros, so that no other part's text changes): exact dF/dtheta for
+// the run-time parameters of one point (ogk_launch) and of `count` lanes (ogk_launch_batch).  Both need an evaluation
+// at the same point before them on the same stream (OGK_EVAL / OGK_BATCH_EVAL: y0), write [n_par][m] doubles - every
+// one of them, +0.0 where the structure says zero - to args->jt (a lane: to its record's pvals), and touch no
+// jt_state / jt_launches word.  A module without parameters answers hipErrorInvalidValue.
+#define OGK_PAR_JAC 15
+#define OGK_BATCH_PAR_JAC 16
+
+// The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -54,6 +62,7 @@ enum ogk_mode {
 #define OGK_PART_SWEEP 3        /* <module>.p2.so: OGK_SWEEP */
 #define OGK_PART_BATCH 4        /* <module>.batch.so, on demand: OGK_BATCH_FUSED, OGK_BATCH_EVAL, OGK_BATCH_BIND */
 #define OGK_PART_BATCH_EXACT 5  /* <module>.batchx.so, on demand: OGK_BATCH_EXACT */
+#define OGK_PART_PAR 6          /* <module>.par.so, on demand: OGK_PAR_JAC, OGK_BATCH_PAR_JAC */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

@@ -200,6 +200,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #if defined(OGK_PART) && OGK_PART == OGK_PART_BATCH_EXACT
 #define OGK_HAS_BATCH_EXACT 1    // OGK_BATCH_EXACT: the exact Jacobian of a batch of points; built on demand
 #endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_PAR
+#define OGK_HAS_PAR 1        // OGK_PAR_JAC, OGK_BATCH_PAR_JAC: exact dF/dtheta for run-time parameters; built on demand
+#endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
 // ------------------------------------------------------------------------------------------
@@ -1578,7 +1581,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // through the constant address space (scalar loads, as it reads a launch's argument block) - a copy of a 500-byte
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
-#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT)
+#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -1695,6 +1698,42 @@ __global__ __launch_bounds__(XB_THREADS) void ogk_exact_struct_batch(const ogk_a
     }
     if (j < 0) return;
     exact_column(a, j, heavy ? tid : (tid & 63), heavy ? XB_THREADS : 64);
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Modes 15 and 16 (the parameter part, OGK_PART_PAR): exact dF/dtheta for the run-time parameters, dF[n_par][m] dense
+// and row-major.  blockIdx.y is the parameter, one workgroup per (parameter, lane): it zero-fills row kp of dF - all m
+// doubles, every call; the result is small - and then its threads run over the parameter's work lists (the generated
+// header's parameter section), one thread per entry: og_par_entry (og_par.h, the source a host probe shares) computes an
+// entry from x0, y0, cvec and the D image alone, so the mapping cannot change a bit of it.  y0 is the evaluation's
+// (OGK_EVAL / OGK_BATCH_EVAL before this launch on the same stream).  The parameter index is the workgroup's, so the
+// ranges of its work lists are scalar loads; a parameter nothing reads is a fill and nothing else.
+// ------------------------------------------------------------------------------------------
+#if defined(OGK_HAS_PAR) && defined(OG_GEN_HAS_PAR)
+#include "og_par.h"
+constexpr int PAR_THREADS = 256;
+
+__device__ __forceinline__ void exact_par_row(const ogk_args& a, double* dF) {
+    const int kp = (int)blockIdx.y, tid = (int)threadIdx.x;
+    double* drow = dF + (long)kp * OgGen::M;
+    for (int r = tid; r < OgGen::M; r += PAR_THREADS) drow[r] = 0.0;
+    __syncthreads();                            // (every thread of the workgroup: the zeros of the row before its entries)
+    const int entries = OgGen::PAR_ENTRIES(kp);
+    for (int e = tid; e < entries; e += PAR_THREADS) {
+        int row;
+        const double v = og_par_entry<OgGen>(kp, e, a.x0, a.y0, a.cvec, a.dfrag, &row);
+        drow[row] = v;
+    }
+}
+
+__global__ __launch_bounds__(PAR_THREADS) void ogk_exact_par(const ogk_args a) { exact_par_row(a, a.jt); }
+
+// the same on a lane's record (blockIdx.z: the lane; its own cvec gives every lane its own theta); the lane's dF is
+// where OGK_BATCH_BIND put the record's pvals
+__global__ __launch_bounds__(PAR_THREADS) void ogk_exact_par_batch(const ogk_args* __restrict__ lanes) {
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_par_row(a, a.pvals);
 }
 #endif
 
@@ -1976,6 +2015,17 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
         return (int)hipGetLastError();
     }
 #endif
+#ifdef OGK_HAS_PAR
+    if (mode == OGK_PAR_JAC) {
+#ifdef OG_GEN_HAS_PAR
+        if (!args->jt || !args->x0 || !args->y0) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ogk_exact_par, dim3(1, OgGen::N_PAR), dim3(PAR_THREADS), 0, stream, *args);
+        return (int)hipGetLastError();
+#else
+        return (int)hipErrorInvalidValue;           // a module without run-time parameters
+#endif
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2022,5 +2072,22 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
     hipLaunchKernelGGL(ogk_exact_struct_batch, dim3(grid, b->count), dim3(XB_THREADS), 0, stream,
                        (const ogk_args*)b->lanes);
     return (int)hipGetLastError();
+}
+#endif
+
+#ifdef OGK_HAS_PAR
+// the parameter part's batched mode: it exports the entry name of the batch parts and is looked up in its own shared
+// object
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || mode != OGK_BATCH_PAR_JAC) return (int)hipErrorInvalidValue;
+#ifdef OG_GEN_HAS_PAR
+    hipLaunchKernelGGL(ogk_exact_par_batch, dim3(1, OgGen::N_PAR, b->count), dim3(PAR_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes);
+    return (int)hipGetLastError();
+#else
+    (void)stream;
+    return (int)hipErrorInvalidValue;               // a module without run-time parameters
+#endif
 }
 #endif

@@ -202,6 +202,12 @@ struct og_problem_s {
     // the exact Jacobian of a batch (og_jacobian_exact_batch_load): a part of its own, loaded when first asked for
     void* batch_exact_module = nullptr;
     ogk_launch_batch_fn batch_exact_launch = nullptr;
+    // exact dF/dtheta for the run-time parameters (og_parameter_jacobian_load): a part of its own with a single-point and
+    // a batched launcher, loaded when first asked for; d_pj: [n_par][m] staging of the host-pointer call
+    void* par_module = nullptr;
+    ogk_launch_fn par_launch = nullptr;
+    ogk_launch_batch_fn par_launch_batch = nullptr;
+    double* d_pj = nullptr;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -848,11 +854,13 @@ void og_problem_destroy(og_handle p) {
     while (!p->batches.empty()) og_batch_destroy(p->batches.back());
     if (p->batch_module) dlclose(p->batch_module);
     if (p->batch_exact_module) dlclose(p->batch_exact_module);
+    if (p->par_module) dlclose(p->par_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
     hipFree(p->d_cvec);
     hipFree(p->d_theta);
+    hipFree(p->d_pj);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1382,6 +1390,7 @@ struct og_batch_s {
     // records' cvec point into it), and [capacity][n_par] staging of the host-pointer og_parameters_batch
     double* d_cvec = nullptr;
     double *d_th = nullptr, *h_th = nullptr;
+    double* d_pj = nullptr;                 // [capacity][n_par][m] staging of the host-pointer og_parameter_jacobian_batch
 };
 
 namespace {
@@ -1421,10 +1430,11 @@ ogk_batch_args batch_args(og_batch_s* b, int set, int count) {
 // launch: the records are device state that a replayed graph rewrites behind the host's back, so the host keeps no
 // memory of what they hold.  The same launch zeroes the non-finite counter of the lanes an evaluation is about to
 // run (clear_set: the record set of that evaluation, or -1).
+// (vals_stride: doubles per lane of `vals` when it is not an array of packed non-zeros)
 int batch_bind(og_batch_s* b, int count, const double* X, const double* H, double* F, double* vals, int clear_set,
-               hipStream_t s, const char* who) {
+               hipStream_t s, const char* who, int64_t vals_stride = -1) {
     ogk_batch_args ba = batch_args(b, 0, count);        // (the whole table)
-    ba.X = X, ba.H = H, ba.F0 = F, ba.vals = vals, ba.nnz = b->nnz;
+    ba.X = X, ba.H = H, ba.F0 = F, ba.vals = vals, ba.nnz = vals_stride >= 0 ? vals_stride : b->nnz;
     ba.clear_set = clear_set;
     const int rc = b->p->batch_launch(&ba, OGK_BATCH_BIND, s);
     if (rc) return launched(rc, who);
@@ -1557,6 +1567,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_vals);
     hipFree(b->d_cvec);
     hipFree(b->d_th);
+    hipFree(b->d_pj);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -1888,6 +1899,112 @@ int og_jacobian_exact_batch(og_batch b, int32_t count, const double* X, double* 
     if (!rc) rc = og_jacobian_exact_batch_dev(b, count, b->d_xh, d_f, d_vals, p->stream);
     if (rc) return rc;
     return batch_results(b, (size_t)count, in_place, F0, vals, nonfinite);
+}
+
+// ---- exact dF/dtheta for the run-time parameters (include/ogpsx.h) ----
+static int parameter_jacobian_check(const og_problem_s* p, const char* who) {
+    if (p->n_par == 0) return fail(1, std::string(who) + ": the module has no run-time parameters");
+    if (!p->par_launch)
+        return fail(4, std::string(who) + ": the module's parameter part is not loaded (og_parameter_jacobian_load)");
+    return 0;
+}
+
+int og_parameter_jacobian_load(og_handle p, const char* par_part_path) {
+    if (!p) return fail(1, "og_parameter_jacobian_load: null handle");
+    if (p->n_par == 0) return fail(1, "og_parameter_jacobian_load: the module has no run-time parameters");
+    if (p->par_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, par_part_path, "og_parameter_jacobian_load", "parameter part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the parameter part knows the mode)
+    if (!fn || fn(&probe, OGK_PAR_JAC, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_parameter_jacobian_load: the parameter part does not belong to the handle's module");
+    }
+    p->par_module = mod;
+    p->par_launch = fn;
+    p->par_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_parameter_jacobian_dev(og_handle p, const double* d_x, double* d_dF, double* d_F0, void* hip_stream) {
+    if (!p || !d_x || !d_dF) return fail(1, "og_parameter_jacobian_dev: null argument");
+    int rc = parameter_jacobian_check(p, "og_parameter_jacobian_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (no J_T among the arguments: the evaluation counts no launch into any buffer's words, and nothing here reads them)
+    fill_args(p, &a, d_x, nullptr, d_F0 ? d_F0 : p->d_f0, nullptr, 0, 0);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_dF;
+    if (!rc) rc = p->par_launch(&a, OGK_PAR_JAC, hip_stream);
+    return launched(rc, "og_parameter_jacobian_dev");
+}
+
+int og_parameter_jacobian(og_handle p, const double* x, double* dF, double* F0) {
+    if (!p || !x || !dF) return fail(1, "og_parameter_jacobian: null argument");
+    int rc = parameter_jacobian_check(p, "og_parameter_jacobian");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t count = (size_t)p->n_par * (size_t)p->m;
+    if (!p->d_pj) OG_HIP(hipMalloc(&p->d_pj, sizeof(double) * count));
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    rc = og_parameter_jacobian_dev(p, p->d_x, p->d_pj, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(dF, p->d_pj, sizeof(double) * count, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_parameter_jacobian_batch_dev(og_batch b, int32_t count, const double* d_X, double* d_F0, double* d_dF,
+                                    void* hip_stream) {
+    int rc = batch_check(b, count, "og_parameter_jacobian_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_dF) return fail(1, "og_parameter_jacobian_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = parameter_jacobian_check(p, "og_parameter_jacobian_batch_dev");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T; the lanes'
+    // pvals are bound to the slices of d_dF
+    rc = batch_bind(b, count, d_X, nullptr, d_F0 ? d_F0 : b->d_f, d_dF, 1, s, "og_parameter_jacobian_batch_dev",
+                    (int64_t)p->n_par * (int64_t)p->m);
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        const ogk_batch_args ba = batch_args(b, 1, count);
+        rc = p->par_launch_batch(&ba, OGK_BATCH_PAR_JAC, s);
+    }
+    return launched(rc, "og_parameter_jacobian_batch_dev");
+}
+
+int og_parameter_jacobian_batch(og_batch b, int32_t count, const double* X, double* F0, double* dF) {
+    int rc = batch_check(b, count, "og_parameter_jacobian_batch");
+    if (rc) return rc;
+    if (!X || !dF) return fail(1, "og_parameter_jacobian_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = parameter_jacobian_check(p, "og_parameter_jacobian_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t lane = (size_t)p->n_par * (size_t)p->m, c = (size_t)count;
+    if (!b->d_pj) OG_HIP(hipMalloc(&b->d_pj, sizeof(double) * (size_t)b->capacity * lane));
+    rc = batch_upload(b, c, X, nullptr);
+    if (!rc) rc = og_parameter_jacobian_batch_dev(b, count, b->d_xh, b->d_f, b->d_pj, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(dF, b->d_pj, sizeof(double) * c * lane, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
 }
 
 }  // extern "C"

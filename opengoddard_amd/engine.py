@@ -143,6 +143,37 @@ class HipEngine:
         _native.check(self._lib.og_get_parameters(self._handle, _native.dptr(theta), self.n_par), "og_get_parameters")
         return theta
 
+    # ------------------------------------------------------------------ exact dF/dtheta
+    def _load_parameter_part(self):
+        """The module's parameter part (``build.build_parameter_part``): compiled by the first exact-parameter call,
+        loaded once per handle (``og_parameter_jacobian_load``)."""
+        if self.n_par == 0:
+            raise ValueError("this problem declares no parameter")
+        if getattr(self, "parameter_part_path", None) is None:
+            path = build.build_parameter_part(self.header)
+            _native.check(self._lib.og_parameter_jacobian_load(self._handle, path.encode()), "og_parameter_jacobian_load")
+            self.parameter_part_path = path
+
+    def parameter_jacobian(self, x):
+        """``(dF, F0)``: ``dF[k, r] = dF_r/dtheta_k`` at ``x`` and the parameters on the device, ``[n_par, m]``, EXACT
+        (forward-mode differentiation with the seed on the parameter's table entry, ``og_parameter_jacobian``: an
+        evaluation and one small launch), and ``F0 = F(x)``.  With ``devices=[...]`` the first device's handle serves
+        it; the call is not split."""
+        self._load_parameter_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        assert x.shape == (self.n,)
+        dF, F0 = np.empty((self.n_par, self.m)), np.empty(self.m)
+        _native.check(self._lib.og_parameter_jacobian(self._handle, _native.dptr(x), _native.dptr(dF), _native.dptr(F0)),
+                      "og_parameter_jacobian")
+        return dF, F0
+
+    def parameter_jacobian_dev(self, d_x, d_dF, d_F0=None, stream=0):
+        """``og_parameter_jacobian_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_dF`` ``[n_par, m]``, ``d_F0``
+        ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_parameter_part()
+        _native.check(self._lib.og_parameter_jacobian_dev(self._handle, d_x, d_dF, d_F0, stream),
+                      "og_parameter_jacobian_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -429,6 +460,28 @@ class BatchSweep:
                                                         nonfinite.ctypes.data_as(C.POINTER(C.c_int32))),
                       "og_jacobian_exact_batch")
         return F0, vals, nonfinite
+
+    def parameter_jacobian(self, X, count=None):
+        """``(dF[B, n_par, m], F0[B, m])``: lane ``k``'s exact ``dF/dtheta`` at ``X[k]`` and at the lane's own parameters
+        (:meth:`set_parameters`) - bit for bit :meth:`HipEngine.parameter_jacobian` at that point and those values
+        (``og_parameter_jacobian_batch``; three launches whatever ``B`` is).  ``count``: only the first ``count`` rows
+        of ``X`` (default: all).  No lane's J_T is written."""
+        X = self._points(X, "X")
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_parameter_part()
+        dF, F0 = np.empty((B, self.engine.n_par, self.m)), np.empty((B, self.m))
+        _native.check(self._lib.og_parameter_jacobian_batch(self._handle, B, _native.dptr(X), _native.dptr(F0),
+                                                            _native.dptr(dF)), "og_parameter_jacobian_batch")
+        return dF, F0
+
+    def parameter_jacobian_dev(self, count, d_X, d_dF, d_F0=None, stream=0):
+        """``og_parameter_jacobian_batch_dev``: ``d_X`` ``[count, n]``, ``d_dF`` ``[count, n_par, m]``, ``d_F0``
+        ``[count, m]`` or None."""
+        self.engine._load_parameter_part()
+        _native.check(self._lib.og_parameter_jacobian_batch_dev(self._handle, int(count), d_X, d_F0, d_dF, stream),
+                      "og_parameter_jacobian_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

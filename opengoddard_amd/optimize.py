@@ -73,6 +73,7 @@ class BatchResult:
         self.gradient = self.steps = self.values = self.pattern = None
         self.jacobian = None
         self.parameters = None          # [B, n_par]: the parameter values every point was evaluated with
+        self.parameter_jacobian = None  # [B, n_par, m]: exact dF/dtheta (evaluate_batch(parameter_jacobian=True))
 
     def __len__(self):
         return self.cost.shape[0]
@@ -230,18 +231,39 @@ class Problem:
             raise ValueError("parameters holds no row")
         return np.ascontiguousarray(TH)
 
-    def parameter_sensitivity(self, obj, p=None):
+    def _batch_engine(self, obj):
+        """The engine of an earlier ``solve`` / ``evaluate_batch``, or a new one that the next ``solve`` closes."""
+        engine = getattr(self, "_engine", None)
+        if engine is None:
+            engine = ENGINE_FACTORY(self, obj) if ENGINE_FACTORY is not None else _default_engine(self, obj)
+            self._engine = engine
+            self._engine_of_batch = True         # (solve closes an engine that was only made for batches)
+        return engine
+
+    def parameter_sensitivity(self, obj, p=None, exact=False):
         """``dF/dtheta`` of ``F = [cost | c_eq | c_ineq]`` at the decision vector ``p`` (default ``prob.p``) and the
-        current parameter values, shape ``[n_par, m]``, by forward differences: ONE batched evaluation of ``n_par + 1``
+        current parameter values, shape ``[n_par, m]``.
+
+        ``exact=True``: forward-mode derivatives of the traced callbacks with the seed on the parameter's table entry -
+        as exact as ``jacobian="exact"`` is in ``p``, no step and no forward-difference noise.  ONE call to the engine
+        (``HipEngine.parameter_jacobian``: an evaluation and one small launch); no batch is made.  An engine without
+        that method is a ``ValueError``.
+
+        The default is forward differences: ONE batched evaluation of ``n_par + 1``
         lanes at the same point - lane 0 at ``theta``, lane ``k + 1`` at ``theta + h_k e_k`` with SciPy's step rule
         (``og_fd_step`` without bounds) - and row ``k`` is ``(F(theta + h_k e_k) - F(theta)) / h_k``, formed on the host.
         The lanes are not chunked: ``evaluate_batch`` re-creates the problem's batch with ``n_par + 1`` lanes when the one
-        it has is smaller (a lane owns a dense n x m matrix on the device).  Exact derivatives with respect to parameters
-        do not exist."""
+        it has is smaller (a lane owns a dense n x m matrix on the device)."""
         from . import _native
         n_par = len(self._par_names)
         if n_par == 0:
             raise ValueError("this problem declares no parameter")
+        if exact:
+            engine = self._batch_engine(obj)
+            if not hasattr(engine, "parameter_jacobian"):
+                raise ValueError("this engine has no exact parameter Jacobian (it has no parameter_jacobian)")
+            point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+            return np.array(engine.parameter_jacobian(point)[0], dtype=float, copy=True)
         theta = np.asarray(self._par_values, dtype=float)
         inf = np.full(n_par, np.inf)
         h = _native.fd_step(theta, -inf, inf)
@@ -652,7 +674,7 @@ class Problem:
             self.iterator += 1
 
     # ------------------------------------------------------------------ many points at once
-    def evaluate_batch(self, obj, points, jacobian=False, parameters=None):
+    def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -674,7 +696,14 @@ class Problem:
         ``[B]`` array (names not given keep their current value).  ``None``: every point is evaluated at the current
         values.  ``points`` with ONE row is repeated for every row of ``parameters`` - a scan at one trajectory.  A
         stand-in engine is served point by point through its ``set_parameters`` (without one: ``ValueError``).
-        ``BatchResult.parameters`` holds the values used."""
+        ``BatchResult.parameters`` holds the values used.
+
+        ``parameter_jacobian=True`` adds ``BatchResult.parameter_jacobian``, ``[B, n_par, m]``: the EXACT ``dF/dtheta`` of
+        every point at its own row of ``parameters`` (``BatchSweep.parameter_jacobian``; a stand-in engine is served
+        point by point through its ``parameter_jacobian``, without one: ``ValueError``).  It combines with any
+        ``jacobian=``; a problem without parameters is a ``ValueError``."""
+        if parameter_jacobian and not self._par_names:
+            raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
@@ -691,11 +720,7 @@ class Problem:
             jacobian = "fd" if jacobian else None
         TH = self._batch_parameters(parameters, points.shape[0])
 
-        engine = getattr(self, "_engine", None)
-        if engine is None:
-            engine = ENGINE_FACTORY(self, obj) if ENGINE_FACTORY is not None else _default_engine(self, obj)
-            self._engine = engine
-            self._engine_of_batch = True         # (solve closes an engine that was only made for batches)
+        engine = self._batch_engine(obj)
         if TH is not None and TH.shape[0] != points.shape[0]:
             points = np.repeat(points, TH.shape[0], axis=0)          # one trajectory, scanned
         points = np.ascontiguousarray(points)
@@ -709,6 +734,8 @@ class Problem:
         if not hasattr(engine, "batch"):
             if TH is not None and not hasattr(engine, "set_parameters"):
                 raise ValueError("this engine cannot change parameters (it has no set_parameters)")
+            if parameter_jacobian and not hasattr(engine, "parameter_jacobian"):
+                raise ValueError("this engine has no exact parameter Jacobian (it has no parameter_jacobian)")
 
             def lanes():
                 for k, p in enumerate(points):
@@ -716,13 +743,16 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
+            par_jac = None
             try:
+                if parameter_jacobian:
+                    par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
-                    res.parameters = used
+                    res.parameters, res.parameter_jacobian = used, par_jac
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -743,7 +773,7 @@ class Problem:
                 if TH is not None:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
-            res.parameters = used
+            res.parameters, res.parameter_jacobian = used, par_jac
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -761,9 +791,14 @@ class Problem:
         if getattr(engine, "n_par", 0):
             # (None binds the handle's values to every lane: per-lane values of an earlier call do not leak into this one)
             batch.set_parameters(TH)
+        par_jac = None
+        if parameter_jacobian:
+            if not hasattr(batch, "parameter_jacobian"):
+                raise ValueError("this engine has no exact parameter Jacobian (its batch has no parameter_jacobian)")
+            par_jac = batch.parameter_jacobian(points)[0]
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
-            res.parameters = used
+            res.parameters, res.parameter_jacobian = used, par_jac
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -771,7 +806,7 @@ class Problem:
         else:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
-        res.parameters = used
+        res.parameters, res.parameter_jacobian = used, par_jac
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost

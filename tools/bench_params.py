@@ -20,7 +20,14 @@ units, p10 / median / p90:
 ``--setup`` adds what set_parameter saves, host clock: the set-up of a second solve (trace + header + loading the cached
 module: ``HipEngine`` construction) against a cold build of the baked module's kernels (``build_module(force=True)``).
 On a tree without parameters the baked legs remain: that is leg (c), the parent commit's batch by the same tool;
-``--merge`` / ``--merge-parent`` put result files into one, the parent's under ``parent_commit``."""
+``--merge`` / ``--merge-parent`` put result files into one, the parent's under ``parent_commit``.
+
+``--exact`` (default output profiles/params_exact.json) measures exact dF/dtheta instead, same method, at the same three
+parameters per problem: og_parameter_jacobian_dev (an evaluation and one small launch) and og_parameter_jacobian_batch_dev
+at every B, the forms alternating with the device path of the forward-difference ``parameter_sensitivity`` - per-lane
+parameters and one batched evaluation of ``n_par + 1`` lanes.  On a tree without the exact calls only that path is timed:
+the parent commit's leg, merged under ``parent_commit`` as above.  Nothing is gated on these times: the feature is
+exactness."""
 import argparse
 import json
 import os
@@ -36,10 +43,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-SIZES = {"C2": "goddard", "C3": "polar_tsto"}
+SIZES = {"C2": "goddard", "C3": "polar_tsto", "C5": "launch4"}
 # name -> (where it is read, how to fetch it from / store it into obj)
 PARAMS = {"goddard": (("Hc", "dynamics"), ("Mf", "boundary row and bound"), ("T_max", "bound")),
-          "polar_tsto": (("g0", "dynamics and bound"), ("Vtarget", "boundary row"), ("MaxG", "bound"))}
+          "polar_tsto": (("g0", "dynamics and bound"), ("Vtarget", "boundary row"), ("MaxG", "bound")),
+          "launch4": (("c_q", "dynamics"), ("Vtarget", "boundary row"), ("MaxG", "bound"))}
 
 
 def commit_of_tree():
@@ -73,6 +81,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30, help="event intervals per round")
     ap.add_argument("--inner", type=int, default=10, help="repetitions of the unit inside one interval")
     ap.add_argument("--rounds", type=int, default=3, help="alternations of the forms")
+    ap.add_argument("--exact", action="store_true", help="measure exact dF/dtheta against the FD device path instead")
     ap.add_argument("--setup", action="store_true", help="also time a second solve's set-up against a cold module build")
     ap.add_argument("--commit", default=None)
     ap.add_argument("--out", default=None)
@@ -95,8 +104,10 @@ def main():
             result["commit"] = a.commit
         if a.merge_parent:
             result["parent_commit"] = merged(a.merge_parent)
-            result["parent_commit"]["note"] = ("the same tool on the parent commit's tree in the same lease: the baked "
-                                               "legs only, there are no parameters there")
+            result["parent_commit"]["note"] = (
+                "the same tool on the parent commit's tree in the same lease: the FD device path only, there is no exact "
+                "parameter Jacobian there" if result.get("mode") == "exact" else
+                "the same tool on the parent commit's tree in the same lease: the baked legs only, there are no parameters there")
         with open(a.out, "w") as fh:
             fh.write(json.dumps(result, indent=1, sort_keys=True) + "\n")
         return
@@ -136,6 +147,55 @@ def main():
     result = {"tool": "tools/bench_params.py", "host": socket.gethostname(), "commit": a.commit or commit_of_tree(),
               "device": torch.cuda.get_device_name(0), "reps": a.reps, "inner": a.inner, "rounds": a.rounds,
               "has_parameters": has_params, "sizes": {}}
+    if a.exact:
+        # exact dF/dtheta against the device path of the forward-difference parameter_sensitivity
+        has_exact = hasattr(HipEngine, "parameter_jacobian_dev")
+        result.update({"mode": "exact", "has_exact": has_exact})
+        for tag in a.sizes.split(","):
+            name = SIZES[tag]
+            prob, obj = make(name, True)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                eng = HipEngine(prob, obj)
+            n, m, n_par = eng.n, eng.m, eng.n_par
+            lb = np.array([-np.inf if b[0] is None else b[0] for b in prob.bounds], dtype=float)
+            ub = np.array([np.inf if b[1] is None else b[1] for b in prob.bounds], dtype=float)
+            x0 = np.clip(prob.p, lb, ub)
+            theta = eng.get_parameters()
+            h = _native.fd_step(theta, np.full(n_par, -np.inf), np.full(n_par, np.inf))
+            TH = np.tile(theta, (n_par + 1, 1))
+            TH[np.arange(1, n_par + 1), np.arange(n_par)] += h
+            Bs = [int(v) for v in a.batches.split(",")]
+            Bmax = max(Bs + [n_par + 1])
+            with torch.cuda.stream(stream_obj):
+                d_X = torch.from_numpy(np.tile(x0, (Bmax, 1))).to(dev)
+                d_TH = torch.from_numpy(TH).to(dev)
+                d_F = torch.empty((Bmax, m), dtype=torch.float64, device=dev)
+                d_dF = torch.empty((Bmax, n_par, m), dtype=torch.float64, device=dev)
+            fd_batch = eng.batch(n_par + 1)
+            units = {"fd_device_path": lambda: (fd_batch.set_parameters_dev(n_par + 1, d_TH.data_ptr(), stream),
+                                                fd_batch.values_dev(n_par + 1, d_X.data_ptr(), d_F.data_ptr(), stream))}
+            batches = []
+            if has_exact:
+                units["exact_single"] = lambda: eng.parameter_jacobian_dev(d_X.data_ptr(), d_dF.data_ptr(), d_F.data_ptr(), stream)
+                for B in Bs:
+                    batch = eng.batch(B)
+                    batches.append(batch)
+                    units["exact_batch_%d" % B] = (lambda batch=batch, B=B: batch.parameter_jacobian_dev(
+                        B, d_X.data_ptr(), d_dF.data_ptr(), d_F.data_ptr(), stream))
+            entry = {"problem": name, "n": n, "m": m, "n_par": n_par, "parameters": {k: w for k, w in PARAMS[name]},
+                     "fd_lanes": n_par + 1, "module": os.path.basename(eng.module_path)}
+            entry.update(alternate(units))
+            result["sizes"][tag] = entry
+            print("%s exact: " % tag + ", ".join("%s %.2f us (p10 %.2f p90 %.2f)" % (k, v["median_us"], v["p10_us"], v["p90_us"])
+                                                 for k, v in entry.items() if isinstance(v, dict) and "median_us" in v), flush=True)
+            eng.close()
+        out = a.out or os.path.join(ROOT, "profiles", "params_exact.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as fh:
+            fh.write(json.dumps(result, indent=1, sort_keys=True) + "\n")
+        print(json.dumps({"bench_params": "done", "mode": "exact", "host": result["host"], "out": out}))
+        return
     for tag in a.sizes.split(","):
         name = SIZES[tag]
         forms = {"baked": make(name, False)}
