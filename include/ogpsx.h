@@ -401,6 +401,42 @@ int og_parameter_jacobian_batch_dev(og_batch b, int32_t count, const double* d_X
                                     void* hip_stream);
 int og_parameter_jacobian_batch(og_batch b, int32_t count, const double* X, double* F0, double* dF);
 
+/* ---- exact directional derivatives F'(x) v ---------------------------------------------------------
+ * dF[d][r] = sum_j dF_r/dx_j V[d][j] of F = [cost | c_eq | c_ineq], [k][m] row-major and dense, for k directions V[k][n]
+ * in the decision vector, WITHOUT forming the Jacobian: one forward-mode pass of the traced callbacks with the seed
+ * V[d][i] on variable i (og_jacobian_exact has a unit seed on one variable at a time) - the work of one evaluation on
+ * dual numbers per direction, no pattern, no J_T, no n x m memory, no step.  Every call writes all k * m doubles.  A
+ * run-time parameter is a constant along v; a direction in parameter space is, by linearity, sum_k w_k dF/dtheta_k from
+ * og_parameter_jacobian.  At a switch of the callbacks the derivative is that of the branch F(x) takes, as everywhere in
+ * the exact mode.
+ * Load rule: the kernels live in a part of the callback module of its own (dir_part_path:
+ * opengoddard_amd.build.build_directional_part), for a module with or without parameters.  og_directional_load loads
+ * it once per handle - a later call is a no-op and may pass NULL - and og_problem_destroy closes it; error 4: the part
+ * is missing or cannot be loaded, 5: it belongs to another module.  The other four fail with error 4 while it is not
+ * loaded, and with error 1 (and a message in og_last_error) for null pointers, k < 1 or k > 65535, or a count outside
+ * 1 .. capacity.
+ * og_directional_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own array
+ * when d_F0 is NULL; og_nonfinite_rows counts its non-finite rows) and the derivative kernel, one thread per row and
+ * direction.  Asynchronous and capturable: a captured graph replays on new contents of d_x and d_V.  No J_T is written
+ * and no registered buffer's bookkeeping moves.  Direction d of a call with k directions is bit for bit the call with
+ * that direction alone.
+ * og_directional: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], along V[c] - ONE direction per lane; repeat a point for more - and at the
+ * lane's own parameters (og_parameters_batch*), and writes dF[c][m] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit
+ * the single-point call at that point, direction and those values.  Three launches whatever count is: bind, the batched
+ * evaluation, the derivative kernel.  Lanes count .. capacity-1, their slices of the output and every lane's J_T with
+ * its state words are not touched.
+ * A multi-device handle (og_multi_*) has no form of this call and does not split it: the handle of the first device
+ * serves it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_directional_load(og_handle h, const char* dir_part_path);
+int og_directional_dev(og_handle h, const double* d_x, int32_t k, const double* d_V, double* d_dF, double* d_F0,
+                       void* hip_stream);
+int og_directional(og_handle h, const double* x, int32_t k, const double* V, double* dF, double* F0);
+int og_directional_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_V, double* d_F0, double* d_dF,
+                             void* hip_stream);
+int og_directional_batch(og_batch b, int32_t count, const double* X, const double* V, double* F0, double* dF);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

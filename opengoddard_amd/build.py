@@ -70,7 +70,8 @@ def _core_sources():
 
 
 def _kernel_sources():
-    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h")]
+    return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
+                                               "og_dir.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -201,6 +202,21 @@ def build_parameter_part(header_source, force=False):
     ``BatchSweep.parameter_jacobian``): the module and the two batch parts are what they were, and a user who never asks
     builds and loads what they did before."""
     return _build_on_demand_part(header_source, PARAMETER_PART, parameter_part_path, force)
+
+
+DIRECTIONAL_PART = 7            # OGK_PART_DIR, <module>.dir.so: exact directional derivatives F'(x) v
+
+
+def directional_part_path(out):
+    return out[:-3] + ".dir.so"
+
+
+def build_directional_part(header_source, force=False):
+    """``ogk_exact_dir`` / ``ogk_exact_dir_batch`` (``OGK_PART=7``) -> path of ``<module>.dir.so``.  A part of its own,
+    built when a directional derivative is first asked for (``HipEngine.directional``, ``BatchSweep.directional``): the
+    module and the other on-demand parts are what they were, and a user who never asks builds and loads what they did
+    before."""
+    return _build_on_demand_part(header_source, DIRECTIONAL_PART, directional_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

@@ -54,7 +54,17 @@ enum ogk_mode {
 #define OGK_PAR_JAC 15
 #define OGK_BATCH_PAR_JAC 16
 
-// The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART).
+// The two modes of the directional part (OGK_PART_DIR; macros for the same reason): exact directional derivatives
+// F'(x) v.  OGK_DIR (ogk_launch): K = col_hi - col_lo directions of one point, direction d read at args->h + d * n (the
+// exact path never uses h as a step), its [m] doubles written to args->jt + d * m.  OGK_BATCH_DIR (ogk_launch_batch):
+// one direction per lane, the lane record's h, the result at its pvals (OGK_BATCH_BIND with V as H and the output array
+// as vals, nnz = m).  Both need an evaluation at the same point before them on the same stream (y0), write every one of
+// the m rows, and touch no jt_state / jt_launches word.
+#define OGK_DIR 17
+#define OGK_BATCH_DIR 18
+
+// The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
+// DIRECTIONAL_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -63,6 +73,7 @@ enum ogk_mode {
 #define OGK_PART_BATCH 4        /* <module>.batch.so, on demand: OGK_BATCH_FUSED, OGK_BATCH_EVAL, OGK_BATCH_BIND */
 #define OGK_PART_BATCH_EXACT 5  /* <module>.batchx.so, on demand: OGK_BATCH_EXACT */
 #define OGK_PART_PAR 6          /* <module>.par.so, on demand: OGK_PAR_JAC, OGK_BATCH_PAR_JAC */
+#define OGK_PART_DIR 7          /* <module>.dir.so, on demand: OGK_DIR, OGK_BATCH_DIR */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

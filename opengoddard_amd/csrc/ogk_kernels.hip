@@ -203,6 +203,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #if defined(OGK_PART) && OGK_PART == OGK_PART_PAR
 #define OGK_HAS_PAR 1        // OGK_PAR_JAC, OGK_BATCH_PAR_JAC: exact dF/dtheta for run-time parameters; built on demand
 #endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_DIR
+#define OGK_HAS_DIR 1        // OGK_DIR, OGK_BATCH_DIR: exact directional derivatives F'(x) v; built on demand
+#endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
 // ------------------------------------------------------------------------------------------
@@ -1581,7 +1584,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // through the constant address space (scalar loads, as it reads a launch's argument block) - a copy of a 500-byte
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
-#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR)
+#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -1734,6 +1737,99 @@ __global__ __launch_bounds__(PAR_THREADS) void ogk_exact_par(const ogk_args a) {
 __global__ __launch_bounds__(PAR_THREADS) void ogk_exact_par_batch(const ogk_args* __restrict__ lanes) {
     const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
     exact_par_row(a, a.pvals);
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Modes 17 and 18 (the directional part, OGK_PART_DIR): exact directional derivatives F'(x) v, [m] doubles per
+// direction, every entry by the functions of og_dir.h that a host probe shares (og_dir_entry there is these pieces in
+// one thread): an entry is computed by ONE thread from x0, v, y0, cvec and the D image, no reduction across threads, so
+// the mapping cannot change a bit of it.  Every row of F belongs to exactly one entry: there is no fill, and no entry
+// is written twice.  y0 is the evaluation's (OGK_EVAL / OGK_BATCH_EVAL before this launch on the same stream).
+// Mapping along blockIdx.x, 256 threads per workgroup:
+//   - first the row groups, one WAVEFRONT per (group, 64 elements): a wavefront runs one group's code, not one after
+//     the other of every group its 64 entries happen to span (the head of F is dozens of groups of one row each, and
+//     each is a chain of dependent loads);
+//   - then one workgroup per (defect group, collocation slot): its threads first put the N operand derivatives
+//     d(operand_l)/dv into LDS, one each, and after the barrier thread k runs the row's fma chain over them - the same
+//     doubles in the same order as the probe's chain, which evaluates them in place.  Measured without the staging (every
+//     thread evaluating the N operands inside its chain, a load behind a switch per step): 18 / 60 / 188 us for the
+//     kernel at N = 50 / 80 / 128 (C2 / C3 / C5).
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_DIR
+#include "og_dir.h"
+constexpr int DIR_THREADS = 256;
+constexpr int DIR_WAVES = DIR_THREADS / 64;
+
+// workgroups of the row groups (DIR_WAVES wavefront units each), and (defect group, slot) units
+inline int dir_row_blocks() {
+    int waves = 0;
+    for (int g = 0; g < OgGen::N_GROUPS; ++g)
+        if (OgGen::G_KIND(g) == 0) waves += (OgGen::G_LEN(g) + 63) >> 6;
+    return (waves + DIR_WAVES - 1) / DIR_WAVES;
+}
+inline int dir_defect_units() {
+    int units = 0;
+    for (int g = 0; g < OgGen::N_GROUPS; ++g)
+        if (OgGen::G_KIND(g) == 1) units += OgGen::G_NMV(g);
+    return units;
+}
+
+__device__ __forceinline__ void exact_dir_block(const ogk_args& a, const double* v, double* dF, const int row_blocks) {
+    __shared__ double opd[OgGen::MAX_NODES];
+    const int bx = (int)blockIdx.x, tid = (int)threadIdx.x;
+    const OgDirX xd{a.x0, v};
+    if (bx < row_blocks) {
+        // (the same in all 64 lanes of a wavefront - said to the compiler, so that the group's tables stay scalar loads)
+        int w = __builtin_amdgcn_readfirstlane(bx * DIR_WAVES + (tid >> 6));
+        for (int g = 0; g < OgGen::N_GROUPS; ++g) {
+            if (OgGen::G_KIND(g) != 0) continue;
+            const int len = OgGen::G_LEN(g), nw = (len + 63) >> 6;
+            if (w >= nw) {
+                w -= nw;
+                continue;
+            }
+            const int k = w * 64 + (tid & 63);
+            if (k < len) {
+                int row;
+                const double d = OgGen::item_value(g, 0, k, xd, a.y0, a.cvec, &row).d;
+                dF[row] = d;
+            }
+            return;
+        }
+        return;                                     // (a wavefront past the last group)
+    }
+    int u = bx - row_blocks;                        // the same for the whole workgroup: every thread reaches the barrier
+    for (int g = 0; g < OgGen::N_GROUPS; ++g) {
+        if (OgGen::G_KIND(g) != 1) continue;
+        const int nmv = OgGen::G_NMV(g);
+        if (u >= nmv) {
+            u -= nmv;
+            continue;
+        }
+        const int N = OgGen::G_LEN(g), slot = OgGen::G_MV0(g) + u;
+        for (int l = tid; l < N; l += DIR_THREADS) opd[l] = og_dir_operand<OgGen>(slot, l, xd, a.cvec);
+        __syncthreads();
+        for (int k = tid; k < N; k += DIR_THREADS) {
+            int row;
+            const double d = og_dir_defect<OgGen>(g, u, k, [&](const int l) { return opd[l]; }, xd, a.cvec, a.dfrag, &row);
+            dF[row] = d;
+        }
+        return;
+    }
+}
+
+// blockIdx.y: the direction, read at h + d * n, written to jt + d * m
+__global__ __launch_bounds__(DIR_THREADS) void ogk_exact_dir(const ogk_args a, const int row_blocks) {
+    const long d = (long)blockIdx.y;
+    exact_dir_block(a, a.h + d * OgGen::N_VAR, a.jt + d * OgGen::M, row_blocks);
+}
+
+// the same on a lane's record (blockIdx.z: the lane, as in ogk_exact_par_batch): one direction per lane - the record's
+// h - and the result where OGK_BATCH_BIND put the record's pvals
+__global__ __launch_bounds__(DIR_THREADS) void ogk_exact_dir_batch(const ogk_args* __restrict__ lanes, const int row_blocks) {
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_dir_block(a, a.h, a.pvals, row_blocks);
 }
 #endif
 
@@ -2026,6 +2122,16 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
 #endif
     }
 #endif
+#ifdef OGK_HAS_DIR
+    if (mode == OGK_DIR) {
+        // ncols directions (gridDim.y: at most 65535)
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || ncols < 1 || ncols > 65535) return (int)hipErrorInvalidValue;
+        const int row_blocks = dir_row_blocks(), grid = row_blocks + dir_defect_units();
+        if (grid > 0)
+            hipLaunchKernelGGL(ogk_exact_dir, dim3(grid, ncols), dim3(DIR_THREADS), 0, stream, *args, row_blocks);
+        return (int)hipGetLastError();
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2089,5 +2195,20 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
     (void)stream;
     return (int)hipErrorInvalidValue;               // a module without run-time parameters
 #endif
+}
+#endif
+
+#ifdef OGK_HAS_DIR
+// the directional part's batched mode: it exports the entry name of the batch parts and is looked up in its own shared
+// object
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || mode != OGK_BATCH_DIR)
+        return (int)hipErrorInvalidValue;
+    const int row_blocks = dir_row_blocks(), grid = row_blocks + dir_defect_units();
+    if (grid > 0)
+        hipLaunchKernelGGL(ogk_exact_dir_batch, dim3(grid, 1, b->count), dim3(DIR_THREADS), 0, stream,
+                           (const ogk_args*)b->lanes, row_blocks);
+    return (int)hipGetLastError();
 }
 #endif

@@ -208,6 +208,14 @@ struct og_problem_s {
     ogk_launch_fn par_launch = nullptr;
     ogk_launch_batch_fn par_launch_batch = nullptr;
     double* d_pj = nullptr;
+    // exact directional derivatives (og_directional_load): a part of its own with a single-point and a batched
+    // launcher, loaded when first asked for; d_dir: [V[k][n] | dF[k][m]] staging of the host-pointer call, dir_capacity
+    // directions large
+    void* dir_module = nullptr;
+    ogk_launch_fn dir_launch = nullptr;
+    ogk_launch_batch_fn dir_launch_batch = nullptr;
+    double* d_dir = nullptr;
+    size_t dir_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -855,12 +863,14 @@ void og_problem_destroy(og_handle p) {
     if (p->batch_module) dlclose(p->batch_module);
     if (p->batch_exact_module) dlclose(p->batch_exact_module);
     if (p->par_module) dlclose(p->par_module);
+    if (p->dir_module) dlclose(p->dir_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
     hipFree(p->d_cvec);
     hipFree(p->d_theta);
     hipFree(p->d_pj);
+    hipFree(p->d_dir);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1391,6 +1401,7 @@ struct og_batch_s {
     double* d_cvec = nullptr;
     double *d_th = nullptr, *h_th = nullptr;
     double* d_pj = nullptr;                 // [capacity][n_par][m] staging of the host-pointer og_parameter_jacobian_batch
+    double* d_dj = nullptr;                 // [capacity][m] staging of the host-pointer og_directional_batch
 };
 
 namespace {
@@ -1568,6 +1579,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_cvec);
     hipFree(b->d_th);
     hipFree(b->d_pj);
+    hipFree(b->d_dj);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -2003,6 +2015,133 @@ int og_parameter_jacobian_batch(og_batch b, int32_t count, const double* X, doub
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(dF, b->d_pj, sizeof(double) * c * lane, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * (size_t)p->m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- exact directional derivatives F'(x) v (include/ogpsx.h) ----
+static const int OG_MAX_DIRECTIONS = 65535;         // (one launch: the direction is a grid dimension)
+
+static int directional_check(const og_problem_s* p, const char* who) {
+    if (!p->dir_launch)
+        return fail(4, std::string(who) + ": the module's directional part is not loaded (og_directional_load)");
+    return 0;
+}
+
+static int directional_count_check(int32_t k, const char* who) {
+    if (k < 1) return fail(1, std::string(who) + ": k must be at least 1");
+    if (k > OG_MAX_DIRECTIONS)
+        return fail(1, std::string(who) + ": k " + std::to_string(k) + " exceeds " + std::to_string(OG_MAX_DIRECTIONS) +
+                           " directions of one call");
+    return 0;
+}
+
+int og_directional_load(og_handle p, const char* dir_part_path) {
+    if (!p) return fail(1, "og_directional_load: null handle");
+    if (p->dir_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, dir_part_path, "og_directional_load", "directional part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the directional part knows the mode)
+    if (!fn || fn(&probe, OGK_DIR, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_directional_load: the directional part does not belong to the handle's module");
+    }
+    p->dir_module = mod;
+    p->dir_launch = fn;
+    p->dir_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_directional_dev(og_handle p, const double* d_x, int32_t k, const double* d_V, double* d_dF, double* d_F0,
+                       void* hip_stream) {
+    if (!p || !d_x || !d_V || !d_dF) return fail(1, "og_directional_dev: null argument");
+    int rc = directional_check(p, "og_directional_dev");
+    if (!rc) rc = directional_count_check(k, "og_directional_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (no J_T among the arguments: the evaluation counts no launch into any buffer's words, and nothing here reads them;
+    // the directions travel in the step pointer, which the evaluation does not read, and their number as a column range)
+    fill_args(p, &a, d_x, d_V, d_F0 ? d_F0 : p->d_f0, nullptr, 0, k);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_dF;
+    if (!rc) rc = p->dir_launch(&a, OGK_DIR, hip_stream);
+    return launched(rc, "og_directional_dev");
+}
+
+int og_directional(og_handle p, const double* x, int32_t k, const double* V, double* dF, double* F0) {
+    if (!p || !x || !V || !dF) return fail(1, "og_directional: null argument");
+    int rc = directional_check(p, "og_directional");
+    if (!rc) rc = directional_count_check(k, "og_directional");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, kk = (size_t)k;
+    if (kk > p->dir_capacity) {
+        if (p->d_dir) OG_HIP(hipFree(p->d_dir));
+        p->d_dir = nullptr;
+        p->dir_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_dir, sizeof(double) * kk * (n + m)));
+        p->dir_capacity = kk;
+    }
+    double *d_V = p->d_dir, *d_dF = p->d_dir + kk * n;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_V, V, sizeof(double) * kk * n, hipMemcpyHostToDevice, p->stream));
+    rc = og_directional_dev(p, p->d_x, k, d_V, d_dF, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(dF, d_dF, sizeof(double) * kk * m, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_directional_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_V, double* d_F0, double* d_dF,
+                             void* hip_stream) {
+    int rc = batch_check(b, count, "og_directional_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_V || !d_dF) return fail(1, "og_directional_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = directional_check(p, "og_directional_batch_dev");
+    if (!rc) rc = directional_count_check(count, "og_directional_batch_dev");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T; the lanes' h
+    // is bound to the rows of d_V and their pvals to the rows of d_dF
+    rc = batch_bind(b, count, d_X, d_V, d_F0 ? d_F0 : b->d_f, d_dF, 1, s, "og_directional_batch_dev", (int64_t)p->m);
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        const ogk_batch_args ba = batch_args(b, 1, count);
+        rc = p->dir_launch_batch(&ba, OGK_BATCH_DIR, s);
+    }
+    return launched(rc, "og_directional_batch_dev");
+}
+
+int og_directional_batch(og_batch b, int32_t count, const double* X, const double* V, double* F0, double* dF) {
+    int rc = batch_check(b, count, "og_directional_batch");
+    if (rc) return rc;
+    if (!X || !V || !dF) return fail(1, "og_directional_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = directional_check(p, "og_directional_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t m = (size_t)p->m, c = (size_t)count;
+    if (!b->d_dj) OG_HIP(hipMalloc(&b->d_dj, sizeof(double) * (size_t)b->capacity * m));
+    rc = batch_upload(b, c, X, V);                  // (V where a sweep's steps go: [capacity][n] behind X)
+    if (!rc) rc = og_directional_batch_dev(b, count, b->d_xh, b->d_xh + (size_t)b->capacity * (size_t)p->n, b->d_f, b->d_dj,
+                                           p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(dF, b->d_dj, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
     return 0;
 }

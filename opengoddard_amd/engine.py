@@ -174,6 +174,39 @@ class HipEngine:
         _native.check(self._lib.og_parameter_jacobian_dev(self._handle, d_x, d_dF, d_F0, stream),
                       "og_parameter_jacobian_dev")
 
+    # ------------------------------------------------------------------ exact F'(x) v
+    def _load_directional_part(self):
+        """The module's directional part (``build.build_directional_part``): compiled by the first directional call,
+        loaded once per handle (``og_directional_load``)."""
+        if getattr(self, "directional_part_path", None) is None:
+            path = build.build_directional_part(self.header)
+            _native.check(self._lib.og_directional_load(self._handle, path.encode()), "og_directional_load")
+            self.directional_part_path = path
+
+    def directional(self, x, V):
+        """``(dF, F0)``: ``dF[d] = F'(x) V[d]``, ``[K, m]``, the EXACT derivative of ``F`` at ``x`` along each of the
+        ``K`` directions ``V[K, n]`` without forming the Jacobian (one forward-mode pass with the seed ``V[d, i]`` on
+        variable ``i``, ``og_directional``: an evaluation and one small launch), and ``F0 = F(x)``.  Run-time parameters
+        are constants along a direction.  With ``devices=[...]`` the first device's handle serves it; the call is not
+        split."""
+        self._load_directional_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if V.ndim != 2 or V.shape[1] != self.n or V.shape[0] < 1:
+            raise ValueError("directions must have shape [K, %d] with K >= 1, got %s" % (self.n, V.shape))
+        dF, F0 = np.empty((V.shape[0], self.m)), np.empty(self.m)
+        _native.check(self._lib.og_directional(self._handle, _native.dptr(x), V.shape[0], _native.dptr(V), _native.dptr(dF),
+                                               _native.dptr(F0)), "og_directional")
+        return dF, F0
+
+    def directional_dev(self, d_x, k, d_V, d_dF, d_F0=None, stream=0):
+        """``og_directional_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_V`` ``[k, n]``, ``d_dF`` ``[k, m]``,
+        ``d_F0`` ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_directional_part()
+        _native.check(self._lib.og_directional_dev(self._handle, d_x, int(k), d_V, d_dF, d_F0, stream),
+                      "og_directional_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -482,6 +515,30 @@ class BatchSweep:
         self.engine._load_parameter_part()
         _native.check(self._lib.og_parameter_jacobian_batch_dev(self._handle, int(count), d_X, d_F0, d_dF, stream),
                       "og_parameter_jacobian_batch_dev")
+
+    def directional(self, X, V, count=None):
+        """``(dF[B, m], F0[B, m])``: lane ``k``'s exact ``F'(X[k]) V[k]`` - one direction per lane, at the lane's own
+        parameters (:meth:`set_parameters`) - bit for bit :meth:`HipEngine.directional` at that point, direction and those
+        values (``og_directional_batch``; three launches whatever ``B`` is).  ``count``: only the first ``count`` rows
+        (default: all).  No lane's J_T is written."""
+        X, V = self._points(X, "X"), self._points(V, "V")
+        if V.shape != X.shape:
+            raise ValueError("BatchSweep: %d directions for %d points" % (V.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_directional_part()
+        dF, F0 = np.empty((B, self.m)), np.empty((B, self.m))
+        _native.check(self._lib.og_directional_batch(self._handle, B, _native.dptr(X), _native.dptr(V), _native.dptr(F0),
+                                                     _native.dptr(dF)), "og_directional_batch")
+        return dF, F0
+
+    def directional_dev(self, count, d_X, d_V, d_dF, d_F0=None, stream=0):
+        """``og_directional_batch_dev``: ``d_X`` and ``d_V`` ``[count, n]``, ``d_dF`` ``[count, m]``, ``d_F0``
+        ``[count, m]`` or None."""
+        self.engine._load_directional_part()
+        _native.check(self._lib.og_directional_batch_dev(self._handle, int(count), d_X, d_V, d_F0, d_dF, stream),
+                      "og_directional_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

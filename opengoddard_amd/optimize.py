@@ -74,6 +74,7 @@ class BatchResult:
         self.jacobian = None
         self.parameters = None          # [B, n_par]: the parameter values every point was evaluated with
         self.parameter_jacobian = None  # [B, n_par, m]: exact dF/dtheta (evaluate_batch(parameter_jacobian=True))
+        self.directional = None         # [B, m]: exact F'(x_k) v_k (evaluate_batch(directions=V))
 
     def __len__(self):
         return self.cost.shape[0]
@@ -673,8 +674,32 @@ class Problem:
                 break
             self.iterator += 1
 
+    def directional_derivative(self, obj, directions, p=None):
+        """``F'(p) v`` of ``F = [cost | c_eq | c_ineq]`` at the decision vector ``p`` (default ``prob.p``) and the current
+        parameter values, EXACT and without forming the Jacobian: one forward-mode pass of the traced callbacks per
+        direction, the seed ``v_i`` on variable ``i`` (``HipEngine.directional``: an evaluation and one small launch for
+        all ``K`` directions).  ``directions``: ``[K, number_of_variables]`` -> ``[K, m]``, or one vector -> ``[m]``.
+        What it serves: checking a problem's derivatives (compare with ``J v``), the exact slope of a merit function
+        along a search direction, the first-order effect of ``K`` dispersion directions on the constraints, the term
+        ``F'(x) dx/dtheta`` of a continuation's tangent residual, any matrix-free method.  A direction in PARAMETER space
+        needs no call of its own: by linearity it is ``sum_k w_k dF/dtheta_k`` of :meth:`parameter_sensitivity`.  An
+        engine without ``directional`` and a direction of the wrong length are ``ValueError``s."""
+        V = np.asarray(directions, dtype=float)
+        single = V.ndim == 1
+        if single:
+            V = V[None, :]
+        if V.ndim != 2 or V.shape[1] != self.number_of_variables or V.shape[0] < 1:
+            raise ValueError("directions must have %d entries (number_of_variables) each, got shape %s" % (
+                self.number_of_variables, np.shape(directions)))
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "directional"):
+            raise ValueError("this engine has no exact directional derivative (it has no directional)")
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+        dF = np.array(engine.directional(point, np.ascontiguousarray(V))[0], dtype=float, copy=True)
+        return dF[0] if single else dF
+
     # ------------------------------------------------------------------ many points at once
-    def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False):
+    def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -701,10 +726,24 @@ class Problem:
         ``parameter_jacobian=True`` adds ``BatchResult.parameter_jacobian``, ``[B, n_par, m]``: the EXACT ``dF/dtheta`` of
         every point at its own row of ``parameters`` (``BatchSweep.parameter_jacobian``; a stand-in engine is served
         point by point through its ``parameter_jacobian``, without one: ``ValueError``).  It combines with any
-        ``jacobian=``; a problem without parameters is a ``ValueError``."""
+        ``jacobian=``; a problem without parameters is a ``ValueError``.
+
+        ``directions=V`` (``[B, number_of_variables]``, one row per row of ``points``) adds ``BatchResult.directional``,
+        ``[B, m]``: the EXACT derivative ``F'(x_k) v_k`` of every point along its own direction, without a Jacobian
+        (``BatchSweep.directional``; a stand-in engine is served point by point through its ``directional``, without one:
+        ``ValueError``).  A point with its own row of ``parameters`` is differentiated at those values.  It combines with
+        any ``jacobian=``; more directions at one point: repeat the point.  ``None``: nothing is computed and the call
+        makes exactly the launches it makes without the keyword."""
         if parameter_jacobian and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
+        if directions is not None:
+            directions = np.asarray(directions, dtype=float)
+            if directions.ndim != 2 or directions.shape[1] != self.number_of_variables:
+                raise ValueError("directions must have shape [B, %d] (number_of_variables), got %s" % (
+                    self.number_of_variables, directions.shape))
+            if points.ndim == 2 and directions.shape[0] != points.shape[0]:
+                raise ValueError("directions holds %d rows for %d points" % (directions.shape[0], points.shape[0]))
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
             "points must have %d columns (number_of_variables), got %d" % (self.number_of_variables, points.shape[1])
@@ -723,7 +762,11 @@ class Problem:
         engine = self._batch_engine(obj)
         if TH is not None and TH.shape[0] != points.shape[0]:
             points = np.repeat(points, TH.shape[0], axis=0)          # one trajectory, scanned
+            if directions is not None:
+                directions = np.repeat(directions, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
+        if directions is not None:
+            directions = np.ascontiguousarray(directions)
         B, n = points.shape
         used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
@@ -736,6 +779,8 @@ class Problem:
                 raise ValueError("this engine cannot change parameters (it has no set_parameters)")
             if parameter_jacobian and not hasattr(engine, "parameter_jacobian"):
                 raise ValueError("this engine has no exact parameter Jacobian (it has no parameter_jacobian)")
+            if directions is not None and not hasattr(engine, "directional"):
+                raise ValueError("this engine has no exact directional derivative (it has no directional)")
 
             def lanes():
                 for k, p in enumerate(points):
@@ -743,16 +788,19 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = None
+            par_jac = along = None
             try:
                 if parameter_jacobian:
                     par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
+                if directions is not None:
+                    along = np.stack([np.array(engine.directional(p, directions[k:k + 1])[0], dtype=float).reshape(-1)
+                                      for k, p in enumerate(lanes())])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
-                    res.parameters, res.parameter_jacobian = used, par_jac
+                    res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -773,7 +821,7 @@ class Problem:
                 if TH is not None:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
-            res.parameters, res.parameter_jacobian = used, par_jac
+            res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -796,9 +844,14 @@ class Problem:
             if not hasattr(batch, "parameter_jacobian"):
                 raise ValueError("this engine has no exact parameter Jacobian (its batch has no parameter_jacobian)")
             par_jac = batch.parameter_jacobian(points)[0]
+        along = None
+        if directions is not None:
+            if not hasattr(batch, "directional"):
+                raise ValueError("this engine has no exact directional derivative (its batch has no directional)")
+            along = batch.directional(points, directions)[0]
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
-            res.parameters, res.parameter_jacobian = used, par_jac
+            res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -806,7 +859,7 @@ class Problem:
         else:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
-        res.parameters, res.parameter_jacobian = used, par_jac
+        res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost
