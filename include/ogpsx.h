@@ -437,6 +437,44 @@ int og_directional_batch_dev(og_batch b, int32_t count, const double* d_X, const
                              void* hip_stream);
 int og_directional_batch(og_batch b, int32_t count, const double* X, const double* V, double* F0, double* dF);
 
+/* ---- exact adjoint products F'(x)^T w --------------------------------------------------------------
+ * G[d][j] = sum_r W[d][r] dF_r/dx_j of F = [cost | c_eq | c_ineq], [k][n] row-major and dense, for k weight vectors
+ * W[k][m] over the rows of F, WITHOUT forming the Jacobian: the transposed half of the matrix-free pair whose other half
+ * is og_directional.  W = e_0 gives the gradient of the cost, W = [1, lambda] the gradient of the Lagrangian, W = [0, W c]
+ * that of a merit 1/2 c' W c.  One workgroup per variable computes the entries of that variable's column of the exact
+ * Jacobian (what og_jacobian_exact writes) once, multiplies each by the weight of its row for every vector and sums them
+ * where they are: no pattern, no J_T, no n x m memory, no step.  The ORDER of a sum is fixed (csrc/og_adj.h: 256 strided
+ * fma chains in ascending term order, then a fixed pairwise tree - no atomics, nothing that depends on scheduling), so
+ * the result is reproducible to the bit and vector d of a call with k vectors is bit for bit the call with that vector
+ * alone.  A row whose weight is zero is not skipped (0 * inf is NaN, as the product would give); a variable that no row
+ * reads gets +0.0; every call writes all k * n doubles.  A run-time parameter is a constant.  At a switch of the
+ * callbacks the derivative is that of the branch F(x) takes, as everywhere in the exact mode.
+ * Load rule: the kernels live in a part of the callback module of its own (adj_part_path:
+ * opengoddard_amd.build.build_adjoint_part), for a module with or without parameters.  og_adjoint_load loads it once per
+ * handle - a later call is a no-op and may pass NULL - and og_problem_destroy closes it; error 4: the part is missing or
+ * cannot be loaded, 5: it belongs to another module.  The other four fail with error 4 while it is not loaded, and with
+ * error 1 (and a message in og_last_error) for null pointers, k < 1 or k > 65535, or a count outside 1 .. capacity.
+ * og_adjoint_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own array when
+ * d_F0 is NULL; og_nonfinite_rows counts its non-finite rows) and the adjoint kernel.  Asynchronous and capturable: a
+ * captured graph replays on new contents of d_x and d_W.  No J_T is written and no registered buffer's bookkeeping
+ * moves.
+ * og_adjoint: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], with W[c] - ONE weight vector per lane; repeat a point for more - and at the
+ * lane's own parameters (og_parameters_batch*), and writes G[c][n] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit the
+ * single-point call at that point, vector and those values.  Three launches whatever count is: bind, the batched
+ * evaluation, the adjoint kernel.  Lanes count .. capacity-1, their slices of the output and every lane's J_T with its
+ * state words are not touched.
+ * A multi-device handle (og_multi_*) has no form of this call and does not split it: the handle of the first device
+ * serves it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_adjoint_load(og_handle h, const char* adj_part_path);
+int og_adjoint_dev(og_handle h, const double* d_x, int32_t k, const double* d_W, double* d_G, double* d_F0,
+                   void* hip_stream);
+int og_adjoint(og_handle h, const double* x, int32_t k, const double* W, double* G, double* F0);
+int og_adjoint_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0, double* d_G,
+                         void* hip_stream);
+int og_adjoint_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* G);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

@@ -116,6 +116,12 @@ SIGNATURES = {
     "og_directional_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p]),
     "og_directional_batch": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "og_adjoint_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "og_adjoint_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "og_adjoint": (C.c_int, [C.c_void_p, _c_double_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
+    "og_adjoint_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    "og_adjoint_batch": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "og_device_read": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "og_trace_read": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
     "og_last_error": (C.c_char_p, []),

@@ -71,7 +71,7 @@ def _core_sources():
 
 def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
-                                               "og_dir.h")]
+                                               "og_dir.h", "og_adj.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -217,6 +217,20 @@ def build_directional_part(header_source, force=False):
     module and the other on-demand parts are what they were, and a user who never asks builds and loads what they did
     before."""
     return _build_on_demand_part(header_source, DIRECTIONAL_PART, directional_part_path, force)
+
+
+ADJOINT_PART = 8                # OGK_PART_ADJ, <module>.adj.so: exact adjoint products F'(x)^T w
+
+
+def adjoint_part_path(out):
+    return out[:-3] + ".adj.so"
+
+
+def build_adjoint_part(header_source, force=False):
+    """``ogk_exact_adj`` / ``ogk_exact_adj_batch`` (``OGK_PART=8``) -> path of ``<module>.adj.so``.  A part of its own,
+    built when an adjoint product is first asked for (``HipEngine.adjoint``, ``BatchSweep.adjoint``): the module and the
+    other on-demand parts are what they were, and a user who never asks builds and loads what they did before."""
+    return _build_on_demand_part(header_source, ADJOINT_PART, adjoint_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

@@ -63,8 +63,18 @@ enum ogk_mode {
 #define OGK_DIR 17
 #define OGK_BATCH_DIR 18
 
+// The two modes of the adjoint part (OGK_PART_ADJ; macros for the same reason): exact adjoint products F'(x)^T w.
+// OGK_ADJ (ogk_launch): K = col_hi - col_lo weight vectors of one point, vector d read at args->h + d * m (the exact path
+// never uses h as a step), its [n] doubles written to args->jt + d * n.  OGK_BATCH_ADJ (ogk_launch_batch): one weight
+// vector per lane, lane c reads H + c * m and writes vals + c * n of the launch's own ogk_batch_args (OGK_BATCH_BIND
+// before it binds X and F0 only: a record's h has the stride of a decision vector).  Both need an evaluation at the same
+// point before them on the same stream (y0), write every one of the n entries in the order of sums that og_adj.h fixes,
+// and touch no jt_state / jt_launches word.
+#define OGK_ADJ 19
+#define OGK_BATCH_ADJ 20
+
 // The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
-// DIRECTIONAL_PART).
+// DIRECTIONAL_PART, ADJOINT_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -74,6 +84,7 @@ enum ogk_mode {
 #define OGK_PART_BATCH_EXACT 5  /* <module>.batchx.so, on demand: OGK_BATCH_EXACT */
 #define OGK_PART_PAR 6          /* <module>.par.so, on demand: OGK_PAR_JAC, OGK_BATCH_PAR_JAC */
 #define OGK_PART_DIR 7          /* <module>.dir.so, on demand: OGK_DIR, OGK_BATCH_DIR */
+#define OGK_PART_ADJ 8          /* <module>.adj.so, on demand: OGK_ADJ, OGK_BATCH_ADJ */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

@@ -206,6 +206,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #if defined(OGK_PART) && OGK_PART == OGK_PART_DIR
 #define OGK_HAS_DIR 1        // OGK_DIR, OGK_BATCH_DIR: exact directional derivatives F'(x) v; built on demand
 #endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_ADJ
+#define OGK_HAS_ADJ 1        // OGK_ADJ, OGK_BATCH_ADJ: exact adjoint products F'(x)^T w; built on demand
+#endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
 // ------------------------------------------------------------------------------------------
@@ -1584,7 +1587,8 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // through the constant address space (scalar loads, as it reads a launch's argument block) - a copy of a 500-byte
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
-#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR)
+#if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR) || \
+    defined(OGK_HAS_ADJ)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -1830,6 +1834,127 @@ __global__ __launch_bounds__(DIR_THREADS) void ogk_exact_dir(const ogk_args a, c
 __global__ __launch_bounds__(DIR_THREADS) void ogk_exact_dir_batch(const ogk_args* __restrict__ lanes, const int row_blocks) {
     const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
     exact_dir_block(a, a.h, a.pvals, row_blocks);
+}
+#endif
+
+// ------------------------------------------------------------------------------------------
+// Modes 19 and 20 (the adjoint part, OGK_PART_ADJ): exact adjoint products g = F'(x)^T w, [n] doubles per weight vector.
+// g_j is the sum that og_adj.h defines: the entries ogk_exact_struct writes for column j (og_adj_term), each times the
+// weight of its row, in 256 strided fma chains and the tree of og_adj_tree.  A thread computes a dual-number entry ONCE
+// and applies it to every weight vector of its chunk (ADJ_CHUNK of them: their partial sums are its registers), so K
+// vectors do not repeat the forward-mode work.  The 64 chains [64 q, 64 q + 64) are the 64 lanes of a wavefront: the
+// tree's levels s = 32 .. 1 are a shuffle-down reduction (adj_block_sums), and what is left is (p0 + p1) + (p2 + p3) of
+// the four blocks.  WHO runs block q does not enter the result, so the mapping follows ogk_exact_struct_batch:
+//   - a column the tracer marked heavy (HEAVY_FLAG, OGT_HEAVY: longest first; a final time has a thousand terms) gets a
+//     workgroup, wavefront q runs block q, the four sums meet in LDS; these workgroups lead the grid;
+//   - every other column has a few dozen terms (at most a state's own N defect rows and its row items) and gets ONE
+//     wavefront, four columns per workgroup, which runs the four blocks one after the other - a block past the last term
+//     is +0.0 without any work; no LDS, no barrier.  Measured with a workgroup per column for all of them (three of four
+//     wavefronts idle on almost every column, the grid four times as long): 9.0 / 23.9 / 347 us per call at C2 / C3 / C5
+//     and 33 / 255 / 6270 us for 32 lanes, twice the batched exact Jacobian.
+// The result is the host probe's (og_adj_entry) bit for bit whatever the scheduling, and vector d of K is the call with
+// that vector alone.  Every g_j of every vector is written, +0.0 for a column without terms; nothing else is: no J_T,
+// no fill, no jt_state / jt_launches word.  y0 is the evaluation's (OGK_EVAL / OGK_BATCH_EVAL before this launch on the
+// same stream).  The column is the workgroup's or the wavefront's, so its records and the slot table stay scalar loads.
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_ADJ
+#include "og_adj.h"
+constexpr int ADJ_THREADS = OG_ADJ_CHAINS;
+constexpr int ADJ_WAVES = ADJ_THREADS / 64;
+constexpr int ADJ_CHUNK = 8;            // weight vectors per chunk: 16 VGPRs of partial sums per thread
+static_assert(ADJ_WAVES == 4 && ADJ_CHUNK <= 64, "og_adj_tree combines four blocks of 64 chains");
+
+struct AdjTables {
+    __device__ __forceinline__ int4 col(const int j) const { return OGT_COL[j]; }
+    __device__ __forceinline__ int4 elem(const int e) const { return OGT_ELEM[e]; }
+    __device__ __forceinline__ const ogt_int8& slot(const int s) const { return OGT_SLOT[s]; }
+};
+
+inline int adj_grid() { return OgGen::N_HEAVY + (OgGen::N_VAR + ADJ_WAVES - 1) / ADJ_WAVES; }
+
+// Block q = chain >> 6 of column j for the kc vectors of a chunk, by the 64 lanes of one wavefront (chain: this lane's):
+// the chains (og_adj_chain, every entry applied to all vectors), then the levels s = 32 .. 1 of og_adj_tree -> r[d],
+// valid in lane 0 (lane i of level s needs lane i + s < 2 s <= 64 only; what the lanes above compute is never used).
+// kc and q are the same in all lanes.
+__device__ __forceinline__ void adj_block_sums(const ogk_args& a, const AdjTables& tab, const OgAdjCol& c, const int j,
+                                               const double* w, const int kc, const int chain, double* r) {
+#pragma unroll
+    for (int d = 0; d < ADJ_CHUNK; ++d) r[d] = 0.0;
+    if ((chain & ~63) >= c.terms) return;           // (no chain of the block has a term: +0.0 all the way up the tree)
+    for (int t = chain; t < c.terms; t += OG_ADJ_CHAINS) {
+        int row;
+        const double e = og_adj_term<OgGen>(tab, c, j, t, a.x0, a.y0, a.cvec, a.dfrag, &row);
+#pragma unroll
+        for (int d = 0; d < ADJ_CHUNK; ++d)
+            if (d < kc) r[d] = __builtin_fma(w[(long)d * OgGen::M + row], e, r[d]);
+    }
+#pragma unroll
+    for (int d = 0; d < ADJ_CHUNK; ++d)
+        if (d < kc) {
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) r[d] = r[d] + __shfl_down(r[d], s, 64);
+        }
+}
+
+// w: the chunk's first weight vector (the next at w + M), g: row 0 of its part of the result (the next at g + N_VAR),
+// kc: the chunk's vectors, 1 .. ADJ_CHUNK.  blockIdx.x: heavy columns first, then four light columns per workgroup.
+__device__ __forceinline__ void exact_adj_block(const ogk_args& a, const double* w, double* g, const int kc) {
+    __shared__ double part[ADJ_CHUNK][ADJ_WAVES];
+    const int id = (int)blockIdx.x, tid = (int)threadIdx.x;
+    // (the same in all 64 lanes of a wavefront - said to the compiler, so that the column's tables stay scalar loads)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const AdjTables tab;
+    double r[ADJ_CHUNK];
+    if (id < OgGen::N_HEAVY) {                      // the whole workgroup: every thread reaches the barrier
+        const int j = OGT_HEAVY[id];
+        const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+        adj_block_sums(a, tab, c, j, w, kc, tid, r);
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int d = 0; d < ADJ_CHUNK; ++d) part[d][wave] = r[d];
+        }
+        __syncthreads();
+        if (tid < kc) g[(long)tid * OgGen::N_VAR + j] = (part[tid][0] + part[tid][1]) + (part[tid][2] + part[tid][3]);
+        return;
+    }
+    const int j = (id - OgGen::N_HEAVY) * ADJ_WAVES + wave;
+    if (j >= OgGen::N_VAR || (OGT_COL[j].w & HEAVY_FLAG)) return;   // (the whole wavefront; a heavy column has its own)
+    const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+    const int lane = tid & 63;
+    double s[ADJ_CHUNK], u[ADJ_CHUNK];
+    // (p0 + p1) + (p2 + p3): s = p0, s += p1, u = p2, s += u + p3
+#pragma unroll 1
+    for (int q = 0; q < ADJ_WAVES; ++q) {
+        adj_block_sums(a, tab, c, j, w, kc, q * 64 + lane, r);
+#pragma unroll
+        for (int d = 0; d < ADJ_CHUNK; ++d) {
+            if (q == 0) s[d] = r[d];
+            else if (q == 1) s[d] = s[d] + r[d];
+            else if (q == 2) u[d] = r[d];
+            else s[d] = s[d] + (u[d] + r[d]);
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int d = 0; d < ADJ_CHUNK; ++d)
+            if (d < kc) g[(long)d * OgGen::N_VAR + j] = s[d];
+    }
+}
+
+// blockIdx.y: the chunk of the K = nw weight vectors, read at h + d * m, written to jt + d * n
+__global__ __launch_bounds__(ADJ_THREADS) void ogk_exact_adj(const ogk_args a, const int nw) {
+    const int d0 = (int)blockIdx.y * ADJ_CHUNK;
+    const int kc = nw - d0 < ADJ_CHUNK ? nw - d0 : ADJ_CHUNK;
+    exact_adj_block(a, a.h + (long)d0 * OgGen::M, a.jt + (long)d0 * OgGen::N_VAR, kc);
+}
+
+// the same on a lane's record (blockIdx.z: the lane): one weight vector per lane, row `lane` of W[count][m], the result
+// in row `lane` of G[count][n] (the launch's own arguments: a lane record's h has the stride of a decision vector)
+__global__ __launch_bounds__(ADJ_THREADS) void ogk_exact_adj_batch(const ogk_args* __restrict__ lanes, const double* W,
+                                                                   double* G) {
+    const long lane = (long)blockIdx.z;
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_adj_block(a, W + lane * OgGen::M, G + lane * OgGen::N_VAR, 1);
 }
 #endif
 
@@ -2132,6 +2257,15 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
         return (int)hipGetLastError();
     }
 #endif
+#ifdef OGK_HAS_ADJ
+    if (mode == OGK_ADJ) {
+        // ncols weight vectors (gridDim.y: their chunks)
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || ncols < 1 || ncols > 65535) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ogk_exact_adj, dim3(adj_grid(), (ncols + ADJ_CHUNK - 1) / ADJ_CHUNK), dim3(ADJ_THREADS), 0, stream,
+                           *args, ncols);
+        return (int)hipGetLastError();
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2209,6 +2343,20 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
     if (grid > 0)
         hipLaunchKernelGGL(ogk_exact_dir_batch, dim3(grid, 1, b->count), dim3(DIR_THREADS), 0, stream,
                            (const ogk_args*)b->lanes, row_blocks);
+    return (int)hipGetLastError();
+}
+#endif
+
+#ifdef OGK_HAS_ADJ
+// the adjoint part's batched mode: it exports the entry name of the batch parts and is looked up in its own shared
+// object.  H: the weight vectors W[count][m], vals: the result G[count][n] (the lane records hold neither)
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || mode != OGK_BATCH_ADJ || !b->H ||
+        !b->vals)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(ogk_exact_adj_batch, dim3(adj_grid(), 1, b->count), dim3(ADJ_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes, b->H, b->vals);
     return (int)hipGetLastError();
 }
 #endif

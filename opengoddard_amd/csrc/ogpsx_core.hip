@@ -216,6 +216,13 @@ struct og_problem_s {
     ogk_launch_batch_fn dir_launch_batch = nullptr;
     double* d_dir = nullptr;
     size_t dir_capacity = 0;
+    // exact adjoint products (og_adjoint_load): the same arrangement; d_adj: [W[k][m] | G[k][n]] staging of the
+    // host-pointer call, adj_capacity weight vectors large
+    void* adj_module = nullptr;
+    ogk_launch_fn adj_launch = nullptr;
+    ogk_launch_batch_fn adj_launch_batch = nullptr;
+    double* d_adj = nullptr;
+    size_t adj_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -864,6 +871,7 @@ void og_problem_destroy(og_handle p) {
     if (p->batch_exact_module) dlclose(p->batch_exact_module);
     if (p->par_module) dlclose(p->par_module);
     if (p->dir_module) dlclose(p->dir_module);
+    if (p->adj_module) dlclose(p->adj_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -871,6 +879,7 @@ void og_problem_destroy(og_handle p) {
     hipFree(p->d_theta);
     hipFree(p->d_pj);
     hipFree(p->d_dir);
+    hipFree(p->d_adj);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1402,6 +1411,7 @@ struct og_batch_s {
     double *d_th = nullptr, *h_th = nullptr;
     double* d_pj = nullptr;                 // [capacity][n_par][m] staging of the host-pointer og_parameter_jacobian_batch
     double* d_dj = nullptr;                 // [capacity][m] staging of the host-pointer og_directional_batch
+    double* d_aj = nullptr;                 // [W[capacity][m] | G[capacity][n]] staging of the host-pointer og_adjoint_batch
 };
 
 namespace {
@@ -1580,6 +1590,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_th);
     hipFree(b->d_pj);
     hipFree(b->d_dj);
+    hipFree(b->d_aj);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -2141,6 +2152,137 @@ int og_directional_batch(og_batch b, int32_t count, const double* X, const doubl
                                            p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(dF, b->d_dj, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- exact adjoint products F'(x)^T w (include/ogpsx.h) ----
+static const int OG_MAX_WEIGHT_VECTORS = 65535;     // (one launch; the lanes of a batch are a grid dimension)
+
+static int adjoint_check(const og_problem_s* p, const char* who) {
+    if (!p->adj_launch) return fail(4, std::string(who) + ": the module's adjoint part is not loaded (og_adjoint_load)");
+    return 0;
+}
+
+static int adjoint_count_check(int32_t k, const char* who) {
+    if (k < 1) return fail(1, std::string(who) + ": k must be at least 1");
+    if (k > OG_MAX_WEIGHT_VECTORS)
+        return fail(1, std::string(who) + ": k " + std::to_string(k) + " exceeds " + std::to_string(OG_MAX_WEIGHT_VECTORS) +
+                           " weight vectors of one call");
+    return 0;
+}
+
+int og_adjoint_load(og_handle p, const char* adj_part_path) {
+    if (!p) return fail(1, "og_adjoint_load: null handle");
+    if (p->adj_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, adj_part_path, "og_adjoint_load", "adjoint part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the adjoint part knows the mode)
+    if (!fn || fn(&probe, OGK_ADJ, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_adjoint_load: the adjoint part does not belong to the handle's module");
+    }
+    p->adj_module = mod;
+    p->adj_launch = fn;
+    p->adj_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_adjoint_dev(og_handle p, const double* d_x, int32_t k, const double* d_W, double* d_G, double* d_F0,
+                   void* hip_stream) {
+    if (!p || !d_x || !d_W || !d_G) return fail(1, "og_adjoint_dev: null argument");
+    int rc = adjoint_check(p, "og_adjoint_dev");
+    if (!rc) rc = adjoint_count_check(k, "og_adjoint_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (no J_T among the arguments: the evaluation counts no launch into any buffer's words, and nothing here reads them;
+    // the weight vectors travel in the step pointer, which the evaluation does not read, and their number as a column
+    // range)
+    fill_args(p, &a, d_x, d_W, d_F0 ? d_F0 : p->d_f0, nullptr, 0, k);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_G;
+    if (!rc) rc = p->adj_launch(&a, OGK_ADJ, hip_stream);
+    return launched(rc, "og_adjoint_dev");
+}
+
+int og_adjoint(og_handle p, const double* x, int32_t k, const double* W, double* G, double* F0) {
+    if (!p || !x || !W || !G) return fail(1, "og_adjoint: null argument");
+    int rc = adjoint_check(p, "og_adjoint");
+    if (!rc) rc = adjoint_count_check(k, "og_adjoint");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, kk = (size_t)k;
+    if (kk > p->adj_capacity) {
+        if (p->d_adj) OG_HIP(hipFree(p->d_adj));
+        p->d_adj = nullptr;
+        p->adj_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_adj, sizeof(double) * kk * (n + m)));
+        p->adj_capacity = kk;
+    }
+    double *d_W = p->d_adj, *d_G = p->d_adj + kk * m;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * kk * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_adjoint_dev(p, p->d_x, k, d_W, d_G, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(G, d_G, sizeof(double) * kk * n, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_adjoint_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0, double* d_G,
+                         void* hip_stream) {
+    int rc = batch_check(b, count, "og_adjoint_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_W || !d_G) return fail(1, "og_adjoint_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = adjoint_check(p, "og_adjoint_batch_dev");
+    if (!rc) rc = adjoint_count_check(count, "og_adjoint_batch_dev");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T.  The records
+    // learn X and F0 only: a record's h has the stride of a decision vector, so the weight vectors [count][m] and the
+    // result [count][n] are arguments of the adjoint launch itself
+    rc = batch_bind(b, count, d_X, nullptr, d_F0 ? d_F0 : b->d_f, nullptr, 1, s, "og_adjoint_batch_dev");
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        ogk_batch_args ba = batch_args(b, 1, count);
+        ba.H = d_W, ba.vals = d_G, ba.nnz = (int64_t)p->n;
+        rc = p->adj_launch_batch(&ba, OGK_BATCH_ADJ, s);
+    }
+    return launched(rc, "og_adjoint_batch_dev");
+}
+
+int og_adjoint_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* G) {
+    int rc = batch_check(b, count, "og_adjoint_batch");
+    if (rc) return rc;
+    if (!X || !W || !G) return fail(1, "og_adjoint_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = adjoint_check(p, "og_adjoint_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    if (!b->d_aj) OG_HIP(hipMalloc(&b->d_aj, sizeof(double) * cap * (m + n)));
+    double *d_W = b->d_aj, *d_G = b->d_aj + cap * m;
+    rc = batch_upload(b, c, X, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_adjoint_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_G, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(G, d_G, sizeof(double) * c * n, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
     return 0;

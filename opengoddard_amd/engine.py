@@ -207,6 +207,38 @@ class HipEngine:
         _native.check(self._lib.og_directional_dev(self._handle, d_x, int(k), d_V, d_dF, d_F0, stream),
                       "og_directional_dev")
 
+    # ------------------------------------------------------------------ exact F'(x)^T w
+    def _load_adjoint_part(self):
+        """The module's adjoint part (``build.build_adjoint_part``): compiled by the first adjoint call, loaded once per
+        handle (``og_adjoint_load``)."""
+        if getattr(self, "adjoint_part_path", None) is None:
+            path = build.build_adjoint_part(self.header)
+            _native.check(self._lib.og_adjoint_load(self._handle, path.encode()), "og_adjoint_load")
+            self.adjoint_part_path = path
+
+    def adjoint(self, x, W):
+        """``(G, F0)``: ``G[d] = F'(x)^T W[d]``, ``[K, n]``, the EXACT adjoint product at ``x`` for each of the ``K``
+        weight vectors ``W[K, m]`` over the rows of ``F`` without forming the Jacobian (``og_adjoint``: an evaluation and
+        one launch, a workgroup per variable; the order of every sum is fixed, csrc/og_adj.h), and ``F0 = F(x)``.
+        Run-time parameters are constants.  With ``devices=[...]`` the first device's handle serves it; the call is not
+        split."""
+        self._load_adjoint_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if W.ndim != 2 or W.shape[1] != self.m or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, %d] with K >= 1, got %s" % (self.m, W.shape))
+        G, F0 = np.empty((W.shape[0], self.n)), np.empty(self.m)
+        _native.check(self._lib.og_adjoint(self._handle, _native.dptr(x), W.shape[0], _native.dptr(W), _native.dptr(G),
+                                           _native.dptr(F0)), "og_adjoint")
+        return G, F0
+
+    def adjoint_dev(self, d_x, k, d_W, d_G, d_F0=None, stream=0):
+        """``og_adjoint_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_W`` ``[k, m]``, ``d_G`` ``[k, n]``, ``d_F0``
+        ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_adjoint_part()
+        _native.check(self._lib.og_adjoint_dev(self._handle, d_x, int(k), d_W, d_G, d_F0, stream), "og_adjoint_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -539,6 +571,33 @@ class BatchSweep:
         self.engine._load_directional_part()
         _native.check(self._lib.og_directional_batch_dev(self._handle, int(count), d_X, d_V, d_F0, d_dF, stream),
                       "og_directional_batch_dev")
+
+    def adjoint(self, X, W, count=None):
+        """``(G[B, n], F0[B, m])``: lane ``k``'s exact ``F'(X[k])^T W[k]`` - one weight vector ``W[k]`` of ``m`` entries
+        per lane, at the lane's own parameters (:meth:`set_parameters`) - bit for bit :meth:`HipEngine.adjoint` at that
+        point, vector and those values (``og_adjoint_batch``; three launches whatever ``B`` is).  ``count``: only the
+        first ``count`` rows (default: all).  No lane's J_T is written."""
+        X = self._points(X, "X")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.m:
+            raise ValueError("BatchSweep: W must have shape [B, %d], got %s" % (self.m, W.shape))
+        if W.shape[0] != X.shape[0]:
+            raise ValueError("BatchSweep: %d weight vectors for %d points" % (W.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_adjoint_part()
+        G, F0 = np.empty((B, self.n)), np.empty((B, self.m))
+        _native.check(self._lib.og_adjoint_batch(self._handle, B, _native.dptr(X), _native.dptr(W), _native.dptr(F0),
+                                                 _native.dptr(G)), "og_adjoint_batch")
+        return G, F0
+
+    def adjoint_dev(self, count, d_X, d_W, d_G, d_F0=None, stream=0):
+        """``og_adjoint_batch_dev``: ``d_X`` ``[count, n]``, ``d_W`` ``[count, m]``, ``d_G`` ``[count, n]``, ``d_F0``
+        ``[count, m]`` or None."""
+        self.engine._load_adjoint_part()
+        _native.check(self._lib.og_adjoint_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_G, stream),
+                      "og_adjoint_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

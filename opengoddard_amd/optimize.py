@@ -75,6 +75,7 @@ class BatchResult:
         self.parameters = None          # [B, n_par]: the parameter values every point was evaluated with
         self.parameter_jacobian = None  # [B, n_par, m]: exact dF/dtheta (evaluate_batch(parameter_jacobian=True))
         self.directional = None         # [B, m]: exact F'(x_k) v_k (evaluate_batch(directions=V))
+        self.adjoint = None             # [B, n]: exact F'(x_k)^T w_k (evaluate_batch(adjoints=W))
 
     def __len__(self):
         return self.cost.shape[0]
@@ -698,8 +699,44 @@ class Problem:
         dF = np.array(engine.directional(point, np.ascontiguousarray(V))[0], dtype=float, copy=True)
         return dF[0] if single else dF
 
+    @staticmethod
+    def _rows_of(engine, point):
+        """m, the rows of ``F``: the engine's ``m``, or the length of its values at ``point``."""
+        m = getattr(engine, "m", None)
+        if m is None:
+            m = sum(np.atleast_1d(np.asarray(v)).size for v in engine.values(point))
+        return int(m)
+
+    def adjoint_product(self, obj, weights, p=None):
+        """``F'(p)^T w``, ``g_j = sum_r w_r dF_r/dx_j``, of ``F = [cost | c_eq | c_ineq]`` at the decision vector ``p``
+        (default ``prob.p``) and the current parameter values, EXACT and without forming the Jacobian
+        (``HipEngine.adjoint``: an evaluation and one launch for all ``K`` weight vectors; the column entries are computed
+        once and shared by the vectors).  ``weights``: ``[K, m]`` over the rows of ``F`` -> ``[K, number_of_variables]``,
+        or one vector -> ``[number_of_variables]``.  What it serves: ``w = e_0`` is the gradient of the cost,
+        ``w = [1, lambda]`` the gradient of the Lagrangian (a KKT residual), ``w = [0, W c]`` the gradient of a penalty or
+        feasibility merit ``1/2 c' W c``; with :meth:`directional_derivative` it is the pair ``J v`` / ``J^T w`` that LSQR
+        or CG need, a least-squares multiplier estimate for instance.  The order of every sum is fixed, so the result is
+        reproducible to the bit; run-time parameters are constants.  An engine without ``adjoint`` and a weight vector
+        of the wrong length are ``ValueError``s."""
+        W = np.asarray(weights, dtype=float)
+        single = W.ndim == 1
+        if single:
+            W = W[None, :]
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, m] or [m], got shape %s" % (np.shape(weights),))
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "adjoint"):
+            raise ValueError("this engine has no exact adjoint product (it has no adjoint)")
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+        m = self._rows_of(engine, point)
+        if W.shape[1] != m:
+            raise ValueError("weights must have %d entries (the rows of F) each, got shape %s" % (m, np.shape(weights)))
+        G = np.array(engine.adjoint(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
+        return G[0] if single else G
+
     # ------------------------------------------------------------------ many points at once
-    def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None):
+    def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None,
+                       adjoints=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -733,7 +770,15 @@ class Problem:
         (``BatchSweep.directional``; a stand-in engine is served point by point through its ``directional``, without one:
         ``ValueError``).  A point with its own row of ``parameters`` is differentiated at those values.  It combines with
         any ``jacobian=``; more directions at one point: repeat the point.  ``None``: nothing is computed and the call
-        makes exactly the launches it makes without the keyword."""
+        makes exactly the launches it makes without the keyword.
+
+        ``adjoints=W`` (``[B, m]``, one weight vector over the rows of ``F`` per row of ``points``) adds
+        ``BatchResult.adjoint``, ``[B, number_of_variables]``: the EXACT adjoint product ``F'(x_k)^T w_k`` of every point
+        with its own vector, without a Jacobian (``BatchSweep.adjoint``; a stand-in engine is served point by point
+        through its ``adjoint``, without one: ``ValueError``).  A point with its own row of ``parameters`` is
+        differentiated at those values; one point scanned over ``parameters`` takes its one vector along.  It combines
+        with every other keyword.  ``None``: nothing is computed and the call makes exactly the launches it makes
+        without the keyword."""
         if parameter_jacobian and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
@@ -744,6 +789,12 @@ class Problem:
                     self.number_of_variables, directions.shape))
             if points.ndim == 2 and directions.shape[0] != points.shape[0]:
                 raise ValueError("directions holds %d rows for %d points" % (directions.shape[0], points.shape[0]))
+        if adjoints is not None:
+            adjoints = np.asarray(adjoints, dtype=float)
+            if adjoints.ndim != 2:
+                raise ValueError("adjoints must have shape [B, m] (the rows of F), got %s" % (adjoints.shape,))
+            if points.ndim == 2 and adjoints.shape[0] != points.shape[0]:
+                raise ValueError("adjoints holds %d rows for %d points" % (adjoints.shape[0], points.shape[0]))
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
             "points must have %d columns (number_of_variables), got %d" % (self.number_of_variables, points.shape[1])
@@ -764,10 +815,19 @@ class Problem:
             points = np.repeat(points, TH.shape[0], axis=0)          # one trajectory, scanned
             if directions is not None:
                 directions = np.repeat(directions, TH.shape[0], axis=0)
+            if adjoints is not None:
+                adjoints = np.repeat(adjoints, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
         if directions is not None:
             directions = np.ascontiguousarray(directions)
         B, n = points.shape
+        if adjoints is not None:
+            if not hasattr(engine, "adjoint"):
+                raise ValueError("this engine has no exact adjoint product (it has no adjoint)")
+            adjoints = np.ascontiguousarray(adjoints)
+            m_rows = self._rows_of(engine, points[0])
+            if adjoints.shape[1] != m_rows:
+                raise ValueError("adjoints must have shape [B, %d] (the rows of F), got %s" % (m_rows, adjoints.shape))
         used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
@@ -788,19 +848,22 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = along = None
+            par_jac = along = back = None
             try:
                 if parameter_jacobian:
                     par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
                 if directions is not None:
                     along = np.stack([np.array(engine.directional(p, directions[k:k + 1])[0], dtype=float).reshape(-1)
                                       for k, p in enumerate(lanes())])
+                if adjoints is not None:
+                    back = np.stack([np.array(engine.adjoint(p, adjoints[k:k + 1])[0], dtype=float).reshape(-1)
+                                     for k, p in enumerate(lanes())])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
-                    res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
+                    res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -821,7 +884,7 @@ class Problem:
                 if TH is not None:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
-            res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
+            res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -849,9 +912,14 @@ class Problem:
             if not hasattr(batch, "directional"):
                 raise ValueError("this engine has no exact directional derivative (its batch has no directional)")
             along = batch.directional(points, directions)[0]
+        back = None
+        if adjoints is not None:
+            if not hasattr(batch, "adjoint"):
+                raise ValueError("this engine has no exact adjoint product (its batch has no adjoint)")
+            back = batch.adjoint(points, adjoints)[0]
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
-            res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
+            res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -859,7 +927,7 @@ class Problem:
         else:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
-        res.parameters, res.parameter_jacobian, res.directional = used, par_jac, along
+        res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost
