@@ -475,6 +475,40 @@ int og_adjoint_batch_dev(og_batch b, int32_t count, const double* d_X, const dou
                          void* hip_stream);
 int og_adjoint_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* G);
 
+/* ---- exact Hessian-vector products of w . F ---------------------------------------------------------
+ * Q[d][j] = sum_r W[d][r] d2F_r/dx_j dV[d] of F = [cost | c_eq | c_ineq], that is Q[d] = grad^2 (W[d] . F)(x) V[d],
+ * [k][n] row-major and dense, for k pairs of a weight vector W[d][m] over the rows of F and a direction V[d][n] in the
+ * decision vector, WITHOUT forming a Hessian: with W = [1, lambda] the Hessian of the Lagrangian times a vector - the
+ * curvature v' H v along a step, the product a Newton-CG or Lanczos iteration asks for.  The terms of an entry are the
+ * terms og_adjoint sums for that variable, each evaluated on second-order dual numbers (csrc/og_dual2.h) with the unit
+ * seed on x_j and V[d] as the second seed (csrc/og_hvp.h); the ORDER of the sum is og_adjoint's (csrc/og_adj.h), so the
+ * result is reproducible to the bit and pair d of a call with k pairs is bit for bit the call with that pair alone.  A row
+ * whose weight is zero is not skipped; a variable that no row reads gets +0.0; every call writes all k * n doubles.  A
+ * run-time parameter is a constant (no mixed d2/dx dtheta).  At a switch of the callbacks the derivative is that of the
+ * branch F(x) takes; fabs, max / min, the remainders and the linear interpolation have no curvature of their own.
+ * Load rule: the kernels live in a part of the callback module of its own (hvp_part_path:
+ * opengoddard_amd.build.build_hessian_part).  og_hessian_vector_load loads it once per handle - a later call is a no-op
+ * and may pass NULL - and og_problem_destroy closes it; error 4: the part is missing or cannot be loaded, 5: it belongs
+ * to another module.  The other four fail with error 4 while it is not loaded, and with error 1 (and a message in
+ * og_last_error) for null pointers, k < 1 or k > 65535, or a count outside 1 .. capacity.
+ * og_hessian_vector_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own array
+ * when d_F0 is NULL) and the Hessian kernel, one grid slice per pair.  Asynchronous and capturable: a captured graph
+ * replays on new contents of d_x, d_W and d_V.  No J_T is written and no registered buffer's bookkeeping moves.
+ * og_hessian_vector: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], with the ONE pair W[c], V[c] and at the lane's own parameters
+ * (og_parameters_batch*), and writes Q[c][n] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit the single-point call at
+ * that point, pair and those values.  Three launches whatever count is: bind, the batched evaluation, the Hessian kernel.
+ * A multi-device handle (og_multi_*) has no form of this call and does not split it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_hessian_vector_load(og_handle h, const char* hvp_part_path);
+int og_hessian_vector_dev(og_handle h, const double* d_x, int32_t k, const double* d_W, const double* d_V, double* d_Q,
+                          double* d_F0, void* hip_stream);
+int og_hessian_vector(og_handle h, const double* x, int32_t k, const double* W, const double* V, double* Q, double* F0);
+int og_hessian_vector_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, const double* d_V,
+                                double* d_F0, double* d_Q, void* hip_stream);
+int og_hessian_vector_batch(og_batch b, int32_t count, const double* X, const double* W, const double* V, double* F0,
+                            double* Q);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

@@ -71,7 +71,7 @@ def _core_sources():
 
 def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
-                                               "og_dir.h", "og_adj.h")]
+                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -231,6 +231,21 @@ def build_adjoint_part(header_source, force=False):
     built when an adjoint product is first asked for (``HipEngine.adjoint``, ``BatchSweep.adjoint``): the module and the
     other on-demand parts are what they were, and a user who never asks builds and loads what they did before."""
     return _build_on_demand_part(header_source, ADJOINT_PART, adjoint_part_path, force)
+
+
+HESSIAN_PART = 9                # OGK_PART_HVP, <module>.hvp.so: exact Hessian-vector products of w . F
+
+
+def hessian_part_path(out):
+    return out[:-3] + ".hvp.so"
+
+
+def build_hessian_part(header_source, force=False):
+    """``ogk_exact_hvp`` / ``ogk_exact_hvp_batch`` (``OGK_PART=9``) -> path of ``<module>.hvp.so``.  A part of its own,
+    built when a Hessian-vector product is first asked for (``HipEngine.hessian_vector``,
+    ``BatchSweep.hessian_vector``): the module and the other on-demand parts are what they were, and a user who never
+    asks builds and loads what they did before."""
+    return _build_on_demand_part(header_source, HESSIAN_PART, hessian_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

@@ -73,8 +73,19 @@ enum ogk_mode {
 #define OGK_ADJ 19
 #define OGK_BATCH_ADJ 20
 
+// The two modes of the Hessian part (OGK_PART_HVP; macros for the same reason): exact Hessian-vector products
+// grad^2 (w . F)(x) v.  OGK_HVP (ogk_launch): K = col_hi - col_lo pairs of one point, weight vector d read at
+// args->h + d * m as in OGK_ADJ, direction d at args->pvals + d * n (read only; no packed values travel in this mode),
+// its [n] doubles written to args->jt + d * n.  OGK_BATCH_HVP (ogk_launch_batch): one pair per lane, the direction is
+// the lane record's h (OGK_BATCH_BIND before it binds X, V as H, and F0), lane c reads its weights at H + c * m and
+// writes vals + c * n of the launch's own ogk_batch_args.  Both need an evaluation at the same point before them on the
+// same stream (y0), write every one of the n entries in the order of sums that og_adj.h fixes, and touch no
+// jt_state / jt_launches word.
+#define OGK_HVP 21
+#define OGK_BATCH_HVP 22
+
 // The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
-// DIRECTIONAL_PART, ADJOINT_PART).
+// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -85,6 +96,7 @@ enum ogk_mode {
 #define OGK_PART_PAR 6          /* <module>.par.so, on demand: OGK_PAR_JAC, OGK_BATCH_PAR_JAC */
 #define OGK_PART_DIR 7          /* <module>.dir.so, on demand: OGK_DIR, OGK_BATCH_DIR */
 #define OGK_PART_ADJ 8          /* <module>.adj.so, on demand: OGK_ADJ, OGK_BATCH_ADJ */
+#define OGK_PART_HVP 9          /* <module>.hvp.so, on demand: OGK_HVP, OGK_BATCH_HVP */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

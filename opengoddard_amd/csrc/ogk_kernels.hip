@@ -46,6 +46,9 @@
 #include <hip/hip_runtime.h>
 #include "ogk.h"
 #include "og_dual.h"
+#if defined(OGK_PART) && OGK_PART == OGK_PART_HVP
+#include "og_dual2.h"       // (ahead of the generated header, whose functions name ogm:: at their definition)
+#endif
 #include OG_GEN_HEADER
 
 typedef double v4f64 __attribute__((ext_vector_type(4)));
@@ -208,6 +211,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #endif
 #if defined(OGK_PART) && OGK_PART == OGK_PART_ADJ
 #define OGK_HAS_ADJ 1        // OGK_ADJ, OGK_BATCH_ADJ: exact adjoint products F'(x)^T w; built on demand
+#endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_HVP
+#define OGK_HAS_HVP 1        // OGK_HVP, OGK_BATCH_HVP: exact Hessian-vector products of w . F; built on demand
 #endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
@@ -1588,7 +1594,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
 #if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR) || \
-    defined(OGK_HAS_ADJ)
+    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -1958,6 +1964,94 @@ __global__ __launch_bounds__(ADJ_THREADS) void ogk_exact_adj_batch(const ogk_arg
 }
 #endif
 
+// ------------------------------------------------------------------------------------------
+// Modes 21 and 22 (the Hessian part, OGK_PART_HVP): exact Hessian-vector products q = grad^2 (w . F)(x) v, [n] doubles
+// per pair (w, v).  q_j is the sum that og_hvp.h defines: the terms of column j that og_adj.h enumerates, each the mixed
+// part of the item on second-order dual numbers (unit seed on x_j, v in the other slot), times the weight of its row, in
+// the chains and the tree of og_adj.h.  The forward-mode work depends on v, so - unlike ogk_exact_adj, where a chunk of
+// weight vectors shares an entry - there is nothing to share across pairs but the column lookup: one pair per grid slice
+// (blockIdx.y for the K pairs of one point, blockIdx.z for the lanes of a batch).  The column mapping is
+// ogk_exact_adj's: a heavy column (OGT_HEAVY) gets a workgroup, wavefront q runs block q of 64 chains and the four sums
+// meet in LDS; every other column gets one wavefront, four columns per workgroup, which runs the four blocks one after
+// the other.  A wavefront's 64 lanes are 64 chains and __shfl_down is the tree's levels s = 32 .. 1.  The column is the
+// workgroup's or the wavefront's, so its records stay scalar loads.  Every q_j of every pair is written, +0.0 for a
+// column without terms; no J_T, no jt_state / jt_launches word.  y0 is the evaluation's.
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_HVP
+#include "og_hvp.h"
+constexpr int HVP_THREADS = OG_ADJ_CHAINS;
+constexpr int HVP_WAVES = HVP_THREADS / 64;
+static_assert(HVP_WAVES == 4, "og_adj_tree combines four blocks of 64 chains");
+
+struct HvpTables {
+    __device__ __forceinline__ int4 col(const int j) const { return OGT_COL[j]; }
+    __device__ __forceinline__ int4 elem(const int e) const { return OGT_ELEM[e]; }
+    __device__ __forceinline__ const ogt_int8& slot(const int s) const { return OGT_SLOT[s]; }
+};
+
+inline int hvp_grid() { return OgGen::N_HEAVY + (OgGen::N_VAR + HVP_WAVES - 1) / HVP_WAVES; }
+
+// Block chain >> 6 of column j by the 64 lanes of one wavefront (chain: this lane's): the chain (og_hvp_chain), then the
+// levels s = 32 .. 1 of og_adj_tree -> valid in lane 0 (lane i of level s needs lane i + s < 2 s <= 64 only).  A block
+// past the last term is +0.0 in every lane without any work.
+__device__ __forceinline__ double hvp_block_sum(const ogk_args& a, const HvpTables& tab, const OgAdjCol& c, const int j,
+                                                const double* w, const double* v, const int chain) {
+    double r = og_hvp_chain<OgGen>(tab, c, j, chain, w, v, a.x0, a.y0, a.cvec, a.dfrag);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) r = r + __shfl_down(r, s, 64);
+    return r;
+}
+
+// w[M], v[N_VAR]: the pair, q[N_VAR]: its result.  blockIdx.x: heavy columns first, then four light columns per
+// workgroup.
+__device__ __forceinline__ void exact_hvp_block(const ogk_args& a, const double* w, const double* v, double* q) {
+    __shared__ double part[HVP_WAVES];
+    const int id = (int)blockIdx.x, tid = (int)threadIdx.x;
+    // (the same in all 64 lanes of a wavefront - said to the compiler, so that the column's tables stay scalar loads)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const HvpTables tab;
+    if (id < OgGen::N_HEAVY) {                      // the whole workgroup: every thread reaches the barrier
+        const int j = OGT_HEAVY[id];
+        const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+        const double r = hvp_block_sum(a, tab, c, j, w, v, tid);
+        if ((tid & 63) == 0) part[wave] = r;
+        __syncthreads();
+        if (tid == 0) q[j] = (part[0] + part[1]) + (part[2] + part[3]);
+        return;
+    }
+    const int j = (id - OgGen::N_HEAVY) * HVP_WAVES + wave;
+    if (j >= OgGen::N_VAR || (OGT_COL[j].w & HEAVY_FLAG)) return;   // (the whole wavefront; a heavy column has its own)
+    const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+    const int lane = tid & 63;
+    double s = 0.0, u = 0.0;
+    // (p0 + p1) + (p2 + p3): s = p0, s += p1, u = p2, s += u + p3
+#pragma unroll 1
+    for (int b = 0; b < HVP_WAVES; ++b) {
+        const double r = hvp_block_sum(a, tab, c, j, w, v, b * 64 + lane);
+        if (b == 0) s = r;
+        else if (b == 1) s = s + r;
+        else if (b == 2) u = r;
+        else s = s + (u + r);
+    }
+    if (lane == 0) q[j] = s;
+}
+
+// blockIdx.y: the pair of the K of this point - weights at h + d * m, direction at pvals + d * n, result at jt + d * n
+__global__ __launch_bounds__(HVP_THREADS) void ogk_exact_hvp(const ogk_args a) {
+    const long d = (long)blockIdx.y;
+    exact_hvp_block(a, a.h + d * OgGen::M, a.pvals + d * OgGen::N_VAR, a.jt + d * OgGen::N_VAR);
+}
+
+// the same on a lane's record (blockIdx.z: the lane): the direction is the record's h (bound to row `lane` of
+// V[count][n]), the weights row `lane` of W[count][m], the result row `lane` of Q[count][n] (the launch's own arguments)
+__global__ __launch_bounds__(HVP_THREADS) void ogk_exact_hvp_batch(const ogk_args* __restrict__ lanes, const double* W,
+                                                                   double* Q) {
+    const long lane = (long)blockIdx.z;
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_hvp_block(a, W + lane * OgGen::M, a.h, Q + lane * OgGen::N_VAR);
+}
+#endif
+
 #ifdef OGK_HAS_SWEEP
 __global__ __launch_bounds__(SWEEP_THREADS) void ogk_sweep(const ogk_args a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2266,6 +2360,15 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
         return (int)hipGetLastError();
     }
 #endif
+#ifdef OGK_HAS_HVP
+    if (mode == OGK_HVP) {
+        // ncols pairs (gridDim.y)
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || !args->pvals || ncols < 1 || ncols > 65535)
+            return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ogk_exact_hvp, dim3(hvp_grid(), ncols), dim3(HVP_THREADS), 0, stream, *args);
+        return (int)hipGetLastError();
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2356,6 +2459,20 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
         !b->vals)
         return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(ogk_exact_adj_batch, dim3(adj_grid(), 1, b->count), dim3(ADJ_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes, b->H, b->vals);
+    return (int)hipGetLastError();
+}
+#endif
+
+#ifdef OGK_HAS_HVP
+// the Hessian part's batched mode, under the entry name of the batch parts as the adjoint part's is.  H: the weight
+// vectors W[count][m], vals: the result Q[count][n]; the directions are the lane records' h (OGK_BATCH_BIND)
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || mode != OGK_BATCH_HVP || !b->H ||
+        !b->vals)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(ogk_exact_hvp_batch, dim3(hvp_grid(), 1, b->count), dim3(HVP_THREADS), 0, stream,
                        (const ogk_args*)b->lanes, b->H, b->vals);
     return (int)hipGetLastError();
 }

@@ -223,6 +223,13 @@ struct og_problem_s {
     ogk_launch_batch_fn adj_launch_batch = nullptr;
     double* d_adj = nullptr;
     size_t adj_capacity = 0;
+    // exact Hessian-vector products (og_hessian_vector_load): the same arrangement; d_hvp: [W[k][m] | V[k][n] | Q[k][n]]
+    // staging of the host-pointer call, hvp_capacity pairs large
+    void* hvp_module = nullptr;
+    ogk_launch_fn hvp_launch = nullptr;
+    ogk_launch_batch_fn hvp_launch_batch = nullptr;
+    double* d_hvp = nullptr;
+    size_t hvp_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -872,6 +879,7 @@ void og_problem_destroy(og_handle p) {
     if (p->par_module) dlclose(p->par_module);
     if (p->dir_module) dlclose(p->dir_module);
     if (p->adj_module) dlclose(p->adj_module);
+    if (p->hvp_module) dlclose(p->hvp_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -880,6 +888,7 @@ void og_problem_destroy(og_handle p) {
     hipFree(p->d_pj);
     hipFree(p->d_dir);
     hipFree(p->d_adj);
+    hipFree(p->d_hvp);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1412,6 +1421,7 @@ struct og_batch_s {
     double* d_pj = nullptr;                 // [capacity][n_par][m] staging of the host-pointer og_parameter_jacobian_batch
     double* d_dj = nullptr;                 // [capacity][m] staging of the host-pointer og_directional_batch
     double* d_aj = nullptr;                 // [W[capacity][m] | G[capacity][n]] staging of the host-pointer og_adjoint_batch
+    double* d_hj = nullptr;                 // [W[capacity][m] | Q[capacity][n]] staging of the host-pointer og_hessian_vector_batch
 };
 
 namespace {
@@ -1591,6 +1601,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_pj);
     hipFree(b->d_dj);
     hipFree(b->d_aj);
+    hipFree(b->d_hj);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -2283,6 +2294,138 @@ int og_adjoint_batch(og_batch b, int32_t count, const double* X, const double* W
     rc = og_adjoint_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_G, p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(G, d_G, sizeof(double) * c * n, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- exact Hessian-vector products grad^2 (w . F)(x) v (include/ogpsx.h) ----
+static int hessian_check(const og_problem_s* p, const char* who) {
+    if (!p->hvp_launch)
+        return fail(4, std::string(who) + ": the module's Hessian part is not loaded (og_hessian_vector_load)");
+    return 0;
+}
+
+static int hessian_count_check(int32_t k, const char* who) {
+    if (k < 1) return fail(1, std::string(who) + ": k must be at least 1");
+    if (k > OG_MAX_WEIGHT_VECTORS)
+        return fail(1, std::string(who) + ": k " + std::to_string(k) + " exceeds " + std::to_string(OG_MAX_WEIGHT_VECTORS) +
+                           " pairs of one call");
+    return 0;
+}
+
+int og_hessian_vector_load(og_handle p, const char* hvp_part_path) {
+    if (!p) return fail(1, "og_hessian_vector_load: null handle");
+    if (p->hvp_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, hvp_part_path, "og_hessian_vector_load", "Hessian part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the Hessian part knows the mode)
+    if (!fn || fn(&probe, OGK_HVP, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_hessian_vector_load: the Hessian part does not belong to the handle's module");
+    }
+    p->hvp_module = mod;
+    p->hvp_launch = fn;
+    p->hvp_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_hessian_vector_dev(og_handle p, const double* d_x, int32_t k, const double* d_W, const double* d_V, double* d_Q,
+                          double* d_F0, void* hip_stream) {
+    if (!p || !d_x || !d_W || !d_V || !d_Q) return fail(1, "og_hessian_vector_dev: null argument");
+    int rc = hessian_check(p, "og_hessian_vector_dev");
+    if (!rc) rc = hessian_count_check(k, "og_hessian_vector_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (as og_adjoint_dev: no J_T among the arguments, the weight vectors in the step pointer and the number of pairs as a
+    // column range; the directions in the packed-values pointer, which neither launch writes)
+    fill_args(p, &a, d_x, d_W, d_F0 ? d_F0 : p->d_f0, nullptr, 0, k);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_Q;
+    a.pvals = const_cast<double*>(d_V);
+    if (!rc) rc = p->hvp_launch(&a, OGK_HVP, hip_stream);
+    return launched(rc, "og_hessian_vector_dev");
+}
+
+int og_hessian_vector(og_handle p, const double* x, int32_t k, const double* W, const double* V, double* Q, double* F0) {
+    if (!p || !x || !W || !V || !Q) return fail(1, "og_hessian_vector: null argument");
+    int rc = hessian_check(p, "og_hessian_vector");
+    if (!rc) rc = hessian_count_check(k, "og_hessian_vector");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, kk = (size_t)k;
+    if (kk > p->hvp_capacity) {
+        if (p->d_hvp) OG_HIP(hipFree(p->d_hvp));
+        p->d_hvp = nullptr;
+        p->hvp_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_hvp, sizeof(double) * kk * (m + 2 * n)));
+        p->hvp_capacity = kk;
+    }
+    double *d_W = p->d_hvp, *d_V = d_W + kk * m, *d_Q = d_V + kk * n;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * kk * m, hipMemcpyHostToDevice, p->stream));
+    OG_HIP(hipMemcpyAsync(d_V, V, sizeof(double) * kk * n, hipMemcpyHostToDevice, p->stream));
+    rc = og_hessian_vector_dev(p, p->d_x, k, d_W, d_V, d_Q, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(Q, d_Q, sizeof(double) * kk * n, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_hessian_vector_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, const double* d_V,
+                                double* d_F0, double* d_Q, void* hip_stream) {
+    int rc = batch_check(b, count, "og_hessian_vector_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_W || !d_V || !d_Q) return fail(1, "og_hessian_vector_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = hessian_check(p, "og_hessian_vector_batch_dev");
+    if (!rc) rc = hessian_count_check(count, "og_hessian_vector_batch_dev");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T.  The records
+    // learn X, F0 and - as h, which has the stride of a decision vector - the rows of d_V; the weight vectors
+    // [count][m] and the result [count][n] are arguments of the Hessian launch itself
+    rc = batch_bind(b, count, d_X, d_V, d_F0 ? d_F0 : b->d_f, nullptr, 1, s, "og_hessian_vector_batch_dev");
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        ogk_batch_args ba = batch_args(b, 1, count);
+        ba.H = d_W, ba.vals = d_Q, ba.nnz = (int64_t)p->n;
+        rc = p->hvp_launch_batch(&ba, OGK_BATCH_HVP, s);
+    }
+    return launched(rc, "og_hessian_vector_batch_dev");
+}
+
+int og_hessian_vector_batch(og_batch b, int32_t count, const double* X, const double* W, const double* V, double* F0,
+                            double* Q) {
+    int rc = batch_check(b, count, "og_hessian_vector_batch");
+    if (rc) return rc;
+    if (!X || !W || !V || !Q) return fail(1, "og_hessian_vector_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = hessian_check(p, "og_hessian_vector_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    if (!b->d_hj) OG_HIP(hipMalloc(&b->d_hj, sizeof(double) * cap * (m + n)));
+    double *d_W = b->d_hj, *d_Q = b->d_hj + cap * m;
+    rc = batch_upload(b, c, X, V);                  // (V where a sweep's steps go: [capacity][n] behind X)
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_hessian_vector_batch_dev(b, count, b->d_xh, d_W, b->d_xh + cap * n, b->d_f, d_Q, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(Q, d_Q, sizeof(double) * c * n, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
     return 0;

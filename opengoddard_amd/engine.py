@@ -239,6 +239,43 @@ class HipEngine:
         self._load_adjoint_part()
         _native.check(self._lib.og_adjoint_dev(self._handle, d_x, int(k), d_W, d_G, d_F0, stream), "og_adjoint_dev")
 
+    # ------------------------------------------------------------------ exact grad^2 (w . F)(x) v
+    def _load_hessian_part(self):
+        """The module's Hessian part (``build.build_hessian_part``): compiled by the first Hessian-vector call, loaded
+        once per handle (``og_hessian_vector_load``)."""
+        if getattr(self, "hessian_part_path", None) is None:
+            path = build.build_hessian_part(self.header)
+            _native.check(self._lib.og_hessian_vector_load(self._handle, path.encode()), "og_hessian_vector_load")
+            self.hessian_part_path = path
+
+    def hessian_vector(self, x, W, V):
+        """``(Q, F0)``: ``Q[d] = grad^2 (W[d] . F)(x) V[d]``, ``[K, n]``, the EXACT Hessian-vector product at ``x`` for
+        each of the ``K`` pairs of a weight vector ``W[d]`` (``[K, m]``, over the rows of ``F``) and a direction ``V[d]``
+        (``[K, n]``) without forming a Hessian (``og_hessian_vector``: an evaluation and one launch, a grid slice per
+        pair; second-order dual numbers, the order of every sum fixed - csrc/og_hvp.h), and ``F0 = F(x)``.  Run-time
+        parameters are constants.  With ``devices=[...]`` the first device's handle serves it; the call is not
+        split."""
+        self._load_hessian_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if W.ndim != 2 or W.shape[1] != self.m or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, %d] with K >= 1, got %s" % (self.m, W.shape))
+        if V.shape != (W.shape[0], self.n):
+            raise ValueError("directions must have shape [%d, %d], got %s" % (W.shape[0], self.n, V.shape))
+        Q, F0 = np.empty((W.shape[0], self.n)), np.empty(self.m)
+        _native.check(self._lib.og_hessian_vector(self._handle, _native.dptr(x), W.shape[0], _native.dptr(W),
+                                                  _native.dptr(V), _native.dptr(Q), _native.dptr(F0)), "og_hessian_vector")
+        return Q, F0
+
+    def hessian_vector_dev(self, d_x, k, d_W, d_V, d_Q, d_F0=None, stream=0):
+        """``og_hessian_vector_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_W`` ``[k, m]``, ``d_V`` and ``d_Q``
+        ``[k, n]``, ``d_F0`` ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_hessian_part()
+        _native.check(self._lib.og_hessian_vector_dev(self._handle, d_x, int(k), d_W, d_V, d_Q, d_F0, stream),
+                      "og_hessian_vector_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -598,6 +635,37 @@ class BatchSweep:
         self.engine._load_adjoint_part()
         _native.check(self._lib.og_adjoint_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_G, stream),
                       "og_adjoint_batch_dev")
+
+    def hessian_vector(self, X, W, V, count=None):
+        """``(Q[B, n], F0[B, m])``: lane ``k``'s exact ``grad^2 (W[k] . F)(X[k]) V[k]`` - one pair of a weight vector
+        (``m`` entries) and a direction (``n`` entries) per lane, at the lane's own parameters (:meth:`set_parameters`) -
+        bit for bit :meth:`HipEngine.hessian_vector` at that point, pair and those values (``og_hessian_vector_batch``;
+        three launches whatever ``B`` is).  ``count``: only the first ``count`` rows (default: all).  No lane's J_T is
+        written."""
+        X = self._points(X, "X")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.m:
+            raise ValueError("BatchSweep: W must have shape [B, %d], got %s" % (self.m, W.shape))
+        if V.shape != X.shape:
+            raise ValueError("BatchSweep: V must have shape %s, got %s" % (X.shape, V.shape))
+        if W.shape[0] != X.shape[0]:
+            raise ValueError("BatchSweep: %d weight vectors for %d points" % (W.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_hessian_part()
+        Q, F0 = np.empty((B, self.n)), np.empty((B, self.m))
+        _native.check(self._lib.og_hessian_vector_batch(self._handle, B, _native.dptr(X), _native.dptr(W), _native.dptr(V),
+                                                        _native.dptr(F0), _native.dptr(Q)), "og_hessian_vector_batch")
+        return Q, F0
+
+    def hessian_vector_dev(self, count, d_X, d_W, d_V, d_Q, d_F0=None, stream=0):
+        """``og_hessian_vector_batch_dev``: ``d_X``, ``d_V`` and ``d_Q`` ``[count, n]``, ``d_W`` ``[count, m]``, ``d_F0``
+        ``[count, m]`` or None."""
+        self.engine._load_hessian_part()
+        _native.check(self._lib.og_hessian_vector_batch_dev(self._handle, int(count), d_X, d_W, d_V, d_F0, d_Q, stream),
+                      "og_hessian_vector_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

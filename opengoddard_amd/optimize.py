@@ -76,6 +76,7 @@ class BatchResult:
         self.parameter_jacobian = None  # [B, n_par, m]: exact dF/dtheta (evaluate_batch(parameter_jacobian=True))
         self.directional = None         # [B, m]: exact F'(x_k) v_k (evaluate_batch(directions=V))
         self.adjoint = None             # [B, n]: exact F'(x_k)^T w_k (evaluate_batch(adjoints=W))
+        self.hessian_product = None     # [B, n]: exact grad^2 (w_k . F)(x_k) v_k (evaluate_batch(hessian_products=(W, V)))
 
     def __len__(self):
         return self.cost.shape[0]
@@ -734,9 +735,44 @@ class Problem:
         G = np.array(engine.adjoint(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
         return G[0] if single else G
 
+    def hessian_vector_product(self, obj, weights, directions, p=None):
+        """``grad^2 (w . F)(p) v``, ``q_j = sum_r w_r d2F_r/dx_j dv``, of ``F = [cost | c_eq | c_ineq]`` at the decision
+        vector ``p`` (default ``prob.p``) and the current parameter values, EXACT and without forming a Hessian
+        (``HipEngine.hessian_vector``: an evaluation and one launch for all ``K`` pairs; second-order dual numbers, no
+        step).  ``directions``: ``[K, number_of_variables]`` -> ``[K, number_of_variables]``, or one vector ->
+        ``[number_of_variables]``.  ``weights``: ``[K, m]`` over the rows of ``F``, one vector per direction, or ONE
+        ``[m]`` used for every direction - one ``lambda``, many ``v`` is the common call.  With ``w = [1, lambda]`` it is
+        the Hessian of the Lagrangian times ``v``: the curvature ``v' H v`` along a step or a null-space direction, the
+        product Newton-CG or Lanczos ask for, a check on what a quasi-Newton factor has learnt.  The order of every sum
+        is fixed, so the result is reproducible to the bit; run-time parameters are constants.  An engine without
+        ``hessian_vector`` and vectors of the wrong length are ``ValueError``s."""
+        V = np.asarray(directions, dtype=float)
+        single = V.ndim == 1
+        if single:
+            V = V[None, :]
+        if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] != self.number_of_variables:
+            raise ValueError("directions must have shape [K, %d] or [%d] (number_of_variables), got shape %s" % (
+                self.number_of_variables, self.number_of_variables, np.shape(directions)))
+        W = np.asarray(weights, dtype=float)
+        if W.ndim == 1:
+            W = np.repeat(W[None, :], V.shape[0], axis=0)
+        if W.ndim != 2 or W.shape[0] != V.shape[0]:
+            raise ValueError("weights must have shape [%d, m] (one vector per direction) or [m], got shape %s" % (
+                V.shape[0], np.shape(weights)))
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "hessian_vector"):
+            raise ValueError("this engine has no exact Hessian-vector product (it has no hessian_vector)")
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+        m = self._rows_of(engine, point)
+        if W.shape[1] != m:
+            raise ValueError("weights must have %d entries (the rows of F) each, got shape %s" % (m, np.shape(weights)))
+        Q = np.array(engine.hessian_vector(point, np.ascontiguousarray(W), np.ascontiguousarray(V))[0], dtype=float,
+                     copy=True)
+        return Q[0] if single else Q
+
     # ------------------------------------------------------------------ many points at once
     def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None,
-                       adjoints=None):
+                       adjoints=None, hessian_products=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -778,7 +814,15 @@ class Problem:
         through its ``adjoint``, without one: ``ValueError``).  A point with its own row of ``parameters`` is
         differentiated at those values; one point scanned over ``parameters`` takes its one vector along.  It combines
         with every other keyword.  ``None``: nothing is computed and the call makes exactly the launches it makes
-        without the keyword."""
+        without the keyword.
+
+        ``hessian_products=(W, V)`` (``W`` ``[B, m]``, ``V`` ``[B, number_of_variables]``: one pair per row of ``points``)
+        adds ``BatchResult.hessian_product``, ``[B, number_of_variables]``: the EXACT ``grad^2 (w_k . F)(x_k) v_k`` of
+        every point with its own pair, without a Hessian (``BatchSweep.hessian_vector``; a stand-in engine is served
+        point by point through its ``hessian_vector``, without one: ``ValueError``).  A point with its own row of
+        ``parameters`` is differentiated at those values; one point scanned over ``parameters`` takes its one pair
+        along.  It combines with every other keyword.  ``None``: nothing is computed and the call builds, loads and
+        launches exactly what it does without the keyword."""
         if parameter_jacobian and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
@@ -795,6 +839,17 @@ class Problem:
                 raise ValueError("adjoints must have shape [B, m] (the rows of F), got %s" % (adjoints.shape,))
             if points.ndim == 2 and adjoints.shape[0] != points.shape[0]:
                 raise ValueError("adjoints holds %d rows for %d points" % (adjoints.shape[0], points.shape[0]))
+        hess_w = hess_v = None
+        if hessian_products is not None:
+            if not isinstance(hessian_products, (tuple, list)) or len(hessian_products) != 2:
+                raise ValueError("hessian_products must be a pair (W [B, m], V [B, number_of_variables])")
+            hess_w, hess_v = (np.asarray(a, dtype=float) for a in hessian_products)
+            if hess_w.ndim != 2 or hess_v.ndim != 2 or hess_v.shape[1] != self.number_of_variables:
+                raise ValueError("hessian_products must have shapes [B, m] and [B, %d], got %s and %s" % (
+                    self.number_of_variables, hess_w.shape, hess_v.shape))
+            if hess_w.shape[0] != hess_v.shape[0] or (points.ndim == 2 and hess_v.shape[0] != points.shape[0]):
+                raise ValueError("hessian_products holds %d and %d rows for %d points" % (
+                    hess_w.shape[0], hess_v.shape[0], points.shape[0] if points.ndim == 2 else 1))
         assert points.ndim == 2, "points must have shape [B, number_of_variables], got %s" % (points.shape,)
         assert points.shape[1] == self.number_of_variables, \
             "points must have %d columns (number_of_variables), got %d" % (self.number_of_variables, points.shape[1])
@@ -817,6 +872,8 @@ class Problem:
                 directions = np.repeat(directions, TH.shape[0], axis=0)
             if adjoints is not None:
                 adjoints = np.repeat(adjoints, TH.shape[0], axis=0)
+            if hess_w is not None:
+                hess_w, hess_v = np.repeat(hess_w, TH.shape[0], axis=0), np.repeat(hess_v, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
         if directions is not None:
             directions = np.ascontiguousarray(directions)
@@ -828,6 +885,14 @@ class Problem:
             m_rows = self._rows_of(engine, points[0])
             if adjoints.shape[1] != m_rows:
                 raise ValueError("adjoints must have shape [B, %d] (the rows of F), got %s" % (m_rows, adjoints.shape))
+        if hess_w is not None:
+            if not hasattr(engine, "hessian_vector"):
+                raise ValueError("this engine has no exact Hessian-vector product (it has no hessian_vector)")
+            hess_w, hess_v = np.ascontiguousarray(hess_w), np.ascontiguousarray(hess_v)
+            m_rows = self._rows_of(engine, points[0])
+            if hess_w.shape[1] != m_rows:
+                raise ValueError("hessian_products must have shapes [B, %d] and [B, %d], got %s and %s" % (
+                    m_rows, n, hess_w.shape, hess_v.shape))
         used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
@@ -848,7 +913,7 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = along = back = None
+            par_jac = along = back = curv = None
             try:
                 if parameter_jacobian:
                     par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
@@ -858,12 +923,16 @@ class Problem:
                 if adjoints is not None:
                     back = np.stack([np.array(engine.adjoint(p, adjoints[k:k + 1])[0], dtype=float).reshape(-1)
                                      for k, p in enumerate(lanes())])
+                if hess_w is not None:
+                    curv = np.stack([np.array(engine.hessian_vector(p, hess_w[k:k + 1], hess_v[k:k + 1])[0],
+                                              dtype=float).reshape(-1) for k, p in enumerate(lanes())])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
                     res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
+                    res.hessian_product = curv
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -885,6 +954,7 @@ class Problem:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
+            res.hessian_product = curv
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -917,9 +987,15 @@ class Problem:
             if not hasattr(batch, "adjoint"):
                 raise ValueError("this engine has no exact adjoint product (its batch has no adjoint)")
             back = batch.adjoint(points, adjoints)[0]
+        curv = None
+        if hess_w is not None:
+            if not hasattr(batch, "hessian_vector"):
+                raise ValueError("this engine has no exact Hessian-vector product (its batch has no hessian_vector)")
+            curv = batch.hessian_vector(points, hess_w, hess_v)[0]
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
+            res.hessian_product = curv
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -928,6 +1004,7 @@ class Problem:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
         res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
+        res.hessian_product = curv
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost

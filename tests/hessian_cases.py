@@ -1,0 +1,255 @@
+"""The cases of tests/test_hessian.py and tests/test_hessian_gpu.py (and of ``__graft_entry__.build``, which compiles the
+GPU cases' modules, batch parts and Hessian parts ahead of the GPU run): the rules of ``csrc/og_dual2.h`` against mpmath,
+the pairs ``(w, v)``, the host probe of ``csrc/og_hvp.h`` and its independent reference.
+
+Shapes, points and parameter sets are those of ``adjoint_cases.GPU_KEYS`` (``B5``, ``G17``, ``layout_8``, ``P2U``,
+``B90``), the weights ``adjoint_cases.weights`` and the directions ``directional_cases``' (``Case.directions``).  What the
+five contain (checked by tests/test_hessian.py from the probe's structure report): a column of more than 256 terms and a
+column the tracer marks heavy (the final time of ``B90``, both), columns with no term (``layout_8``), light columns (all).
+"""
+import os
+import subprocess
+
+import numpy as np
+
+import adjoint_cases as ac
+import parameter_exact_cases as ec
+import test_exact_surface as surface
+from oracle import exact_jac
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PROBE_SOURCE = os.path.join(ROOT, "tests", "hvp_probe.cpp")
+RULES_SOURCE = os.path.join(ROOT, "tests", "dual2_probe.cpp")
+BOUND = surface.BOUND           # 1e-12: the project's bound for exact modes (the symmetry test)
+
+GPU_KEYS = ac.GPU_KEYS
+case = ac.case
+
+
+def pairs(C):
+    """``(W[8, m], V[8, n])``: the eight weight vectors of ``adjoint_cases.weights`` (e_0, the last row, ones, three
+    seeded, zero, one without the defect rows) with the directions of ``directional_cases`` - three seeded random ones,
+    e_0, the final time, the last variable, the zero direction, a seeded one again: pair 6 is (0, 0) and pair 7 has
+    neither a defect weight nor a unit direction."""
+    W, D = ac.weights(C), C.directions()
+    V = np.stack([D[3], D[4], D[5], D[0], D[2], D[1], D[6], D[4]])
+    return W, V
+
+
+# ------------------------------------------------------------------------------------------------ the host probes
+def _compile(source, exe, compiler, sanitize, defines=()):
+    base = [compiler] + ec.PROBE_FLAGS + list(defines) + [source, "-o", exe, "-lstdc++", "-lm"]
+    if sanitize:
+        base = base[:1] + ["-O1", "-fsanitize=address,undefined"] + base[1:]
+        proc = subprocess.run(base + ["-static-libasan", "-static-libubsan"], stdout=subprocess.PIPE,
+                              stderr=subprocess.STDOUT, text=True)
+        if proc.returncode == 0:
+            return exe
+    proc = subprocess.run(base, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert proc.returncode == 0, proc.stdout[-3000:]
+    return exe
+
+
+def _exe(folder, stem, compiler, sanitize):
+    return os.path.join(folder, "%s_%s%s" % (stem, os.path.basename(compiler).replace("+", "x"), "_san" if sanitize else ""))
+
+
+def build_probe(C, folder, compiler="g++", sanitize=False):
+    """tests/hvp_probe.cpp against this case's header: a program of its own."""
+    header = os.path.join(folder, "og_gen_%s.h" % C.key)
+    if not os.path.exists(header):
+        with open(header, "w") as fh:
+            fh.write(C.header)
+    exe = _exe(folder, "hvp_probe_" + C.key, compiler, sanitize)
+    if os.path.exists(exe):
+        return exe
+    return _compile(PROBE_SOURCE, exe, compiler, sanitize, ["-DOG_GEN_HEADER=\"%s\"" % header])
+
+
+def _run(cmd):
+    env = dict(os.environ, UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, timeout=300)
+    assert proc.returncode == 0 and "runtime error" not in proc.stdout, proc.stdout[-3000:]
+    return proc.stdout
+
+
+class Probed:
+    """What one run of the probe returns: ``Q[K, n]`` (the products), ``G[K, n]`` (the first-order parts of the same
+    terms in the same order of sums), ``S[K, n]`` (``sum_r |w_r d2F_r/dx_j dv|``), ``F0[m]``, and per variable ``terms``,
+    ``reads`` (-1: no node of a collocated state) and ``heavy``."""
+
+
+def run_probe(C, exe, folder, x, W, V, theta=None, tag="run"):
+    """The probe at ``x`` for the pairs ``(W[d], V[d])``.  The probe itself fails (exit status 1) unless every one of the
+    ``n`` entries of every pair, pre-filled with NaN, is written exactly once and no column has two terms in one row."""
+    W, V = np.atleast_2d(np.asarray(W, dtype=np.float64)), np.atleast_2d(np.asarray(V, dtype=np.float64))
+    K, n, m = W.shape[0], C.n, C.m
+    assert W.shape == (K, m) and V.shape == (K, n)
+    data, out = os.path.join(folder, "%s_%s.in" % (C.key, tag)), os.path.join(folder, "%s_%s.out" % (C.key, tag))
+    cv = C.cvec(theta)
+    np.concatenate([np.asarray(x, dtype=np.float64), cv if cv.size else np.zeros(1)] +
+                   [np.ascontiguousarray(D, dtype=np.float64).reshape(-1) for D in C.prob.D] +
+                   [W.reshape(-1), V.reshape(-1)]).tofile(data)
+    text = _run([exe, data, out])
+    assert "pairs=%d variables=%d " % (K, n) in text and " bad=0" in text, text[-3000:]
+    got = np.fromfile(out)
+    assert got.size == 3 * K * n + m + 3 * n
+    r = Probed()
+    r.Q, r.G, r.S = (got[i * K * n:(i + 1) * K * n].reshape(K, n) for i in range(3))
+    rest = got[3 * K * n:]
+    r.F0 = rest[:m]
+    r.terms, r.reads, r.heavy = (rest[m + i * n:m + (i + 1) * n].astype(int) for i in range(3))
+    return r
+
+
+# ------------------------------------------------------------------------------------------------ the reference
+H_STEP = 2.0 ** -9
+
+
+def oracle_products(C, x, W, v, theta=None, h=H_STEP):
+    """``(ref[K, n], err[K, n])`` for ONE direction ``v`` and the rows of ``W``: central differences of the oracle's
+    complex-step ``J^T w`` (``oracle.exact_jac.jacobian`` at ``x +- h v``, the product in ``np.longdouble``),
+    Richardson-extrapolated from ``h`` and ``h / 2``; ``err`` is the reference's own error estimate, the difference
+    between the extrapolations from ``(h, h / 2)`` and ``(h / 2, h / 4)``.  It shares no generated code and no
+    derivative rule with the kernels."""
+    WL = np.atleast_2d(np.asarray(W, dtype=float)).astype(np.longdouble)
+    program = C.at(theta)
+
+    def central(step):
+        up = exact_jac.jacobian(program, C.prob, x + step * v).astype(np.longdouble)       # J_T [n, m]
+        dn = exact_jac.jacobian(program, C.prob, x - step * v).astype(np.longdouble)
+        return ((up - dn) @ WL.T).T / np.longdouble(2.0 * step)
+
+    d0, d1, d2 = central(h), central(h / 2), central(h / 4)
+    r0, r1 = (4 * d1 - d0) / 3, (4 * d2 - d1) / 3
+    return r1, np.abs(r1 - r0).astype(float)
+
+
+# ------------------------------------------------------------------------------------------------ the rules of og_dual2.h
+OPS = ["add", "sub", "mul", "div", "neg", "sqrt", "exp", "log", "sin", "cos", "tan", "fabs", "atan", "asin", "acos",
+       "atan2", "tanh", "sinh", "cosh", "expm1", "log1p", "log2", "log10", "cbrt", "hypot", "mod", "fmod", "pow",
+       "interp0", "interp1", "max", "min"]
+BINARY = ("add", "sub", "mul", "div", "atan2", "hypot", "mod", "fmod", "pow", "max", "min")
+XG, YG, FILLS = (0.0, 1.0, 2.5, 4.0), (1.0, 3.0, -2.0, 0.5), (-7.25, 11.5)
+SEEDS_A, SEEDS_B = (0.75, -1.25, 0.4375), (-0.625, 1.5, -0.3125)          # d1, d2, dd: all non-zero
+
+# the values the rules are evaluated at: interior points, and both sides of every branch of a rule
+UNARY_POINTS = {
+    "neg": (0.7, -2.5), "sqrt": (0.3, 2.0, 9.5), "exp": (-1.5, 0.3, 2.0), "log": (0.3, 1.7, 40.0),
+    "sin": (-2.0, 0.4, 3.0), "cos": (-2.0, 0.4, 3.0), "tan": (-1.2, 0.4, 1.3), "fabs": (-0.7, -1e-9, 1e-9, 0.7),
+    "atan": (-3.0, 0.2, 1.5), "asin": (-0.9, 0.1, 0.8), "acos": (-0.9, 0.1, 0.8), "tanh": (-1.5, 0.2, 2.0),
+    "sinh": (-1.5, 0.2, 2.0), "cosh": (-1.5, 0.2, 2.0), "expm1": (-1.5, 1e-3, 2.0), "log1p": (-0.6, 1e-3, 3.0),
+    "log2": (0.3, 1.7, 40.0), "log10": (0.3, 1.7, 40.0), "cbrt": (-2.0, 0.3, 9.5),
+    # inside the segments, at the knots (the right-hand segment), on the fills / the extrapolated ends
+    "interp0": (-0.5, 0.0, 0.4, 1.0, 1.7, 2.5, 3.0, 4.0, 4.5), "interp1": (-0.5, 0.0, 0.4, 1.0, 1.7, 2.5, 3.0, 4.0, 4.5),
+}
+BINARY_POINTS = {
+    "add": ((0.7, -2.5),), "sub": ((0.7, -2.5),), "mul": ((0.7, -2.5), (-3.0, 0.25)), "div": ((0.7, -2.5), (-3.0, 0.25)),
+    "atan2": ((0.7, -2.5), (-3.0, 0.25), (1.0, 2.0), (-0.5, -0.8)), "hypot": ((0.7, -2.5), (-3.0, 0.25)),
+    # across a jump of the quotient, both signs
+    "mod": ((7.4, 2.5), (7.6, 2.5), (-7.4, 2.5), (7.4, -2.5), (2.49, 2.5)),
+    "fmod": ((7.4, 2.5), (7.6, 2.5), (-7.4, 2.5), (7.4, -2.5), (2.49, 2.5)),
+    "pow": ((0.7, 2.5), (3.0, -0.5), (1.7, 2.0), (2.0, 3.0)),
+    "max": ((0.7, -2.5), (-2.5, 0.7)), "min": ((0.7, -2.5), (-2.5, 0.7)),
+}
+
+
+def rule_records():
+    """``[R, 10]`` records for tests/dual2_probe.cpp: every op at its points, a binary one in its three forms (pow with a
+    constant exponent, a constant base and both seeded)."""
+    rec = []
+    for code, name in enumerate(OPS):
+        if name in BINARY:
+            for a, b in BINARY_POINTS[name]:
+                for form in (0, 1, 2):
+                    rec.append([code, form, a, *SEEDS_A, b, *SEEDS_B])
+        else:
+            for a in UNARY_POINTS[name]:
+                rec.append([code, 0, a, *SEEDS_A, 0.0, 0.0, 0.0, 0.0])
+    return np.array(rec, dtype=np.float64)
+
+
+# the guarded singular points: an argument with zero seeds must give zeros, never NaN
+SINGULAR = [("sqrt", 0.0, 0.0), ("log", 0.0, 0.0), ("asin", 1.0, 0.0), ("acos", 1.0, 0.0), ("acos", -1.0, 0.0),
+            ("log1p", -1.0, 0.0), ("log2", 0.0, 0.0), ("log10", 0.0, 0.0), ("cbrt", 0.0, 0.0), ("div", 0.0, 0.0),
+            ("div", 1.0, 0.0), ("atan2", 0.0, 0.0), ("hypot", 0.0, 0.0), ("pow", 0.0, 2.0), ("pow", 0.0, 0.5),
+            ("pow", 0.0, 0.0), ("mul", np.inf, 0.0), ("exp", 800.0, 0.0), ("mod", 1.0, 0.0), ("fmod", 1.0, 0.0)]
+
+
+def singular_records():
+    return np.array([[OPS.index(name), 0, a, 0.0, 0.0, 0.0, b, 0.0, 0.0, 0.0] for name, a, b in SINGULAR])
+
+
+def build_rules_probe(folder, compiler="g++", sanitize=False):
+    exe = _exe(folder, "dual2_probe", compiler, sanitize)
+    return exe if os.path.exists(exe) else _compile(RULES_SOURCE, exe, compiler, sanitize)
+
+
+def run_rules_probe(exe, folder, records, tag="rules"):
+    """-> ``[R, 8]``: the result's v, d1, d2, dd, then og_dual.h's (v, d) along seed 1 and along seed 2."""
+    data, out = os.path.join(folder, tag + ".in"), os.path.join(folder, tag + ".out")
+    np.ascontiguousarray(records, dtype=np.float64).tofile(data)
+    text = _run([exe, data, out])
+    assert "records=%d" % len(records) in text, text
+    return np.fromfile(out).reshape(len(records), 8)
+
+
+def _partials(name, a, b):
+    """mpmath: ``(f, fx, fy, fxx, fxy, fyy)`` of the op at ``(a, b)`` (a unary op: the y parts are 0).  The
+    piecewise-linear ops are written out - they have no curvature, and a numerical derivative across a jump is none."""
+    import mpmath as mp
+    zero = mp.mpf(0)
+    if name in ("add", "sub"):
+        return (a + b if name == "add" else a - b), mp.mpf(1), mp.mpf(1 if name == "add" else -1), zero, zero, zero
+    if name == "neg":
+        return -a, mp.mpf(-1), zero, zero, zero, zero
+    if name == "fabs":
+        return abs(a), mp.sign(a), zero, zero, zero, zero
+    if name in ("max", "min"):
+        first = (a > b) if name == "max" else (a < b)
+        return (a if first else b), mp.mpf(1 if first else 0), mp.mpf(0 if first else 1), zero, zero, zero
+    if name in ("mod", "fmod"):
+        q = mp.floor(a / b) if name == "mod" else (mp.floor(a / b) if a / b >= 0 else mp.ceil(a / b))
+        return a - q * b, mp.mpf(1), -q, zero, zero, zero
+    if name in ("interp0", "interp1"):
+        xg, yg = [mp.mpf(v) for v in XG], [mp.mpf(v) for v in YG]
+        i = min(max(sum(1 for g in xg if g <= a), 1), len(xg) - 1)       # the right-hand segment at a knot
+        slope = (yg[i] - yg[i - 1]) / (xg[i] - xg[i - 1])
+        y = slope * (a - xg[i - 1]) + yg[i - 1]
+        if name == "interp0" and (a < xg[0] or a > xg[-1]):
+            y, slope = mp.mpf(FILLS[0] if a < xg[0] else FILLS[1]), zero
+        return y, slope, zero, zero, zero, zero
+    one = {"sqrt": mp.sqrt, "exp": mp.exp, "log": mp.log, "sin": mp.sin, "cos": mp.cos, "tan": mp.tan, "atan": mp.atan,
+           "asin": mp.asin, "acos": mp.acos, "tanh": mp.tanh, "sinh": mp.sinh, "cosh": mp.cosh, "expm1": mp.expm1,
+           "log1p": mp.log1p, "log2": lambda t: mp.log(t, 2), "log10": mp.log10, "cbrt": lambda t: mp.sign(t) * mp.cbrt(abs(t))}     # (the real root)
+    if name in one:
+        f = one[name]
+        return f(a), mp.diff(f, a, 1), zero, mp.diff(f, a, 2), zero, zero
+    two = {"mul": lambda x, y: x * y, "div": lambda x, y: x / y, "atan2": lambda x, y: mp.atan2(x, y),
+           "hypot": mp.hypot, "pow": mp.power}[name]
+    d = lambda i, j: mp.diff(two, (a, b), (i, j))
+    return two(a, b), d(1, 0), d(0, 1), d(2, 0), d(1, 1), d(0, 2)
+
+
+def rule_truth(record):
+    """-> ``(truth[4], unit[4])`` as floats' worth of mpmath numbers at 50 digits: the four parts of the op on the
+    record's second-order duals, and per part the sum of the absolute values of the rule's terms - the unit of error."""
+    import mpmath as mp
+    mp.mp.dps = 50
+    name, form = OPS[int(record[0])], int(record[1])
+    a, a1, a2, a12, b, b1, b2, b12 = (mp.mpf(float(v)) for v in record[2:])
+    if name not in BINARY or form == 1:
+        b1 = b2 = b12 = mp.mpf(0)
+    if name in BINARY and form == 2:
+        a1 = a2 = a12 = mp.mpf(0)
+    f, fx, fy, fxx, fxy, fyy = _partials(name, a, b)
+    first = lambda s, t: ([fx * s, fy * t])
+    mixed = [fxx * a1 * a2, fxy * a1 * b2, fxy * a2 * b1, fyy * b1 * b2, fx * a12, fy * b12]
+    parts = [[f], first(a1, b1), first(a2, b2), mixed]
+    return [mp.fsum(p) for p in parts], [mp.fsum(abs(t) for t in p) for p in parts]
+
+
+# what __graft_entry__.build compiles for tests/test_hessian_gpu.py: (label, header), each with its Hessian part and its
+# batch part
+def modules():
+    return [("hessian " + key, case(key).header) for key in GPU_KEYS]
