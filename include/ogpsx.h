@@ -484,7 +484,7 @@ int og_adjoint_batch(og_batch b, int32_t count, const double* X, const double* W
  * seed on x_j and V[d] as the second seed (csrc/og_hvp.h); the ORDER of the sum is og_adjoint's (csrc/og_adj.h), so the
  * result is reproducible to the bit and pair d of a call with k pairs is bit for bit the call with that pair alone.  A row
  * whose weight is zero is not skipped; a variable that no row reads gets +0.0; every call writes all k * n doubles.  A
- * run-time parameter is a constant (no mixed d2/dx dtheta).  At a switch of the callbacks the derivative is that of the
+ * run-time parameter is a constant (the mixed d2/dx dtheta: og_adjoint_parameter).  At a switch of the callbacks the derivative is that of the
  * branch F(x) takes; fabs, max / min, the remainders and the linear interpolation have no curvature of their own.
  * Load rule: the kernels live in a part of the callback module of its own (hvp_part_path:
  * opengoddard_amd.build.build_hessian_part).  og_hessian_vector_load loads it once per handle - a later call is a no-op
@@ -508,6 +508,40 @@ int og_hessian_vector_batch_dev(og_batch b, int32_t count, const double* d_X, co
                                 double* d_F0, double* d_Q, void* hip_stream);
 int og_hessian_vector_batch(og_batch b, int32_t count, const double* X, const double* W, const double* V, double* F0,
                             double* Q);
+
+/* ---- exact mixed derivatives d(F'(x)^T w)/dtheta for the run-time parameters ---------------------------
+ * S[d][k][j] = sum_r W[d][r] d2F_r/dx_j dtheta_k of F = [cost | c_eq | c_ineq], that is S[d][k] = d(F'(x)^T W[d])/dtheta_k,
+ * [kw][n_par][n] row-major and dense, for kw weight vectors W[d][m] over the rows of F and EVERY declared run-time
+ * parameter, at the handle's current parameter values: with W = [1, lambda] the block d(grad_x L)/dtheta of the
+ * linearised KKT system, the right-hand side of a continuation tangent.  The terms of an entry are the terms og_adjoint
+ * sums for that variable, each evaluated on second-order dual numbers (csrc/og_dual2.h) with the unit seed on x_j and the
+ * unit seed on the parameter's table entry (csrc/og_mix.h); the ORDER of the sum is og_adjoint's (csrc/og_adj.h), so the
+ * result is reproducible to the bit and vector d of a call with kw vectors is bit for bit the call with that vector
+ * alone.  A row whose weight is zero is not skipped; a variable that no row reads gets +0.0, and so does the whole row
+ * of a parameter that nothing reads; every call writes all kw * n_par * n doubles.  No step in theta, no
+ * og_set_parameters launch.  At a switch of the callbacks the derivative is that of the branch F(x) takes.
+ * Load rule: the kernels live in a part of the callback module of its own (mix_part_path:
+ * opengoddard_amd.build.build_mix_part).  og_adjoint_parameter_load loads it once per handle - a later call is a no-op
+ * and may pass NULL - and og_problem_destroy closes it; error 4: the part is missing or cannot be loaded, 5: it belongs
+ * to another module.  The other four fail with error 4 while it is not loaded.  All five fail with error 1 (and a
+ * message in og_last_error) for a module that declares no run-time parameter, for null pointers, kw < 1 or
+ * kw * n_par > 65535, or a count outside 1 .. capacity.
+ * og_adjoint_parameter_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own
+ * array when d_F0 is NULL) and the mixed kernel, one grid slice per pair (weight vector, parameter).  Asynchronous and
+ * capturable: a captured graph replays on new contents of d_x and d_W and on new parameter values.  No J_T is written
+ * and no registered buffer's bookkeeping moves.  og_adjoint_parameter: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], with the ONE weight vector W[c] and at the lane's own parameters
+ * (og_parameters_batch*), and writes S[c][n_par][n] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit the single-point
+ * call at that point, vector and those values.  Three launches whatever count is: bind, the batched evaluation, the
+ * mixed kernel.  A multi-device handle (og_multi_*) has no form of this call and does not split it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_adjoint_parameter_load(og_handle h, const char* mix_part_path);
+int og_adjoint_parameter_dev(og_handle h, const double* d_x, int32_t kw, const double* d_W, double* d_S, double* d_F0,
+                             void* hip_stream);
+int og_adjoint_parameter(og_handle h, const double* x, int32_t kw, const double* W, double* S, double* F0);
+int og_adjoint_parameter_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                   double* d_S, void* hip_stream);
+int og_adjoint_parameter_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* S);
 
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);

@@ -71,7 +71,7 @@ def _core_sources():
 
 def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
-                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h")]
+                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h", "og_mix.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -246,6 +246,21 @@ def build_hessian_part(header_source, force=False):
     ``BatchSweep.hessian_vector``): the module and the other on-demand parts are what they were, and a user who never
     asks builds and loads what they did before."""
     return _build_on_demand_part(header_source, HESSIAN_PART, hessian_part_path, force)
+
+
+MIX_PART = 10                   # OGK_PART_MIX, <module>.mix.so: exact mixed derivatives d(F'(x)^T w)/dtheta
+
+
+def mix_part_path(out):
+    return out[:-3] + ".mix.so"
+
+
+def build_mix_part(header_source, force=False):
+    """``ogk_exact_mix`` / ``ogk_exact_mix_batch`` (``OGK_PART=10``) -> path of ``<module>.mix.so``.  A part of its own,
+    built when a mixed derivative is first asked for (``HipEngine.adjoint_parameter``,
+    ``BatchSweep.adjoint_parameter``): the module and the other on-demand parts are what they were, and a user who never
+    asks builds and loads what they did before."""
+    return _build_on_demand_part(header_source, MIX_PART, mix_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

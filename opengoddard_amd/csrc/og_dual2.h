@@ -29,6 +29,8 @@ struct ogdual2 {
     double v, d1, d2, dd;
     OG_HDI ogdual2() : v(0.0), d1(0.0), d2(0.0), dd(0.0) {}
     OG_HDI ogdual2(const double value) : v(value), d1(0.0), d2(0.0), dd(0.0) {}
+    // value and slot-2 seed: what OgGen::par_leaf constructs for an accessor with a member par_seed (csrc/og_mix.h)
+    OG_HDI ogdual2(const double value, const double seed2) : v(value), d1(0.0), d2(seed2), dd(0.0) {}
     OG_HDI ogdual2(const double value, const double a, const double b, const double mixed)
         : v(value), d1(a), d2(b), dd(mixed) {}
 };

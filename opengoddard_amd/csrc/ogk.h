@@ -84,8 +84,19 @@ enum ogk_mode {
 #define OGK_HVP 21
 #define OGK_BATCH_HVP 22
 
+// The two modes of the mixed part (OGK_PART_MIX; macros for the same reason): exact mixed derivatives
+// d(F'(x)^T w)/dtheta_k for every run-time parameter.  OGK_MIX (ogk_launch): K = col_hi - col_lo weight vectors of one
+// point, vector d read at args->h + d * m as in OGK_ADJ, its [n_par][n] doubles written to args->jt + d * n_par * n.
+// OGK_BATCH_MIX (ogk_launch_batch): one weight vector per lane, lane c reads H + c * m and writes vals + c * n_par * n
+// of the launch's own ogk_batch_args (OGK_BATCH_BIND before it binds X and F0 only); every lane at its own parameters,
+// its record's cvec.  Both need an evaluation at the same point before them on the same stream (y0), write every one
+// of the n_par * n entries in the order of sums that og_adj.h fixes, and touch no jt_state / jt_launches word.  A
+// module without parameters answers hipErrorInvalidValue.
+#define OGK_MIX 23
+#define OGK_BATCH_MIX 24
+
 // The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
-// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART).
+// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART, MIX_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -97,6 +108,7 @@ enum ogk_mode {
 #define OGK_PART_DIR 7          /* <module>.dir.so, on demand: OGK_DIR, OGK_BATCH_DIR */
 #define OGK_PART_ADJ 8          /* <module>.adj.so, on demand: OGK_ADJ, OGK_BATCH_ADJ */
 #define OGK_PART_HVP 9          /* <module>.hvp.so, on demand: OGK_HVP, OGK_BATCH_HVP */
+#define OGK_PART_MIX 10         /* <module>.mix.so, on demand: OGK_MIX, OGK_BATCH_MIX */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

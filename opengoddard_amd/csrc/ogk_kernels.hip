@@ -46,7 +46,7 @@
 #include <hip/hip_runtime.h>
 #include "ogk.h"
 #include "og_dual.h"
-#if defined(OGK_PART) && OGK_PART == OGK_PART_HVP
+#if defined(OGK_PART) && (OGK_PART == OGK_PART_HVP || OGK_PART == OGK_PART_MIX)
 #include "og_dual2.h"       // (ahead of the generated header, whose functions name ogm:: at their definition)
 #endif
 #include OG_GEN_HEADER
@@ -214,6 +214,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #endif
 #if defined(OGK_PART) && OGK_PART == OGK_PART_HVP
 #define OGK_HAS_HVP 1        // OGK_HVP, OGK_BATCH_HVP: exact Hessian-vector products of w . F; built on demand
+#endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_MIX
+#define OGK_HAS_MIX 1        // OGK_MIX, OGK_BATCH_MIX: exact mixed derivatives d(F'(x)^T w)/dtheta; built on demand
 #endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
@@ -1594,7 +1597,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
 #if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR) || \
-    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP)
+    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP) || defined(OGK_HAS_MIX)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -2052,6 +2055,99 @@ __global__ __launch_bounds__(HVP_THREADS) void ogk_exact_hvp_batch(const ogk_arg
 }
 #endif
 
+// ------------------------------------------------------------------------------------------
+// Modes 23 and 24 (the mixed part, OGK_PART_MIX): exact mixed derivatives s_k = d(F'(x)^T w)/dtheta_k, [n_par][n]
+// doubles per weight vector w.  s_{k,j} is the sum that og_mix.h defines: the terms of column j that og_adj.h enumerates,
+// each the mixed part of the item on second-order dual numbers (unit seed on x_j, unit seed on the parameter's table
+// entry), times the weight of its row, in the chains and the tree of og_adj.h.  It is ogk_exact_hvp with the second slot
+// seeded on theta_k instead of on v: the forward-mode work depends on the parameter, so one pair (weight vector d,
+// parameter k) per grid slice - blockIdx.y = d * N_PAR + k for the K vectors of one point; blockIdx.y = k, blockIdx.z the
+// lane for a batch - and nothing shared across pairs but the column lookup.  The column mapping is ogk_exact_hvp's: a
+// heavy column (OGT_HEAVY) gets a workgroup, wavefront q runs block q of 64 chains and the four sums meet in LDS; every
+// other column gets one wavefront, four columns per workgroup, which runs the four blocks one after the other.  The
+// column and the parameter are the workgroup's or the wavefront's, so the column's records stay scalar loads.  Every
+// s_{k,j} of every pair is written, +0.0 for a column without terms and for a parameter nothing reads; no J_T, no
+// jt_state / jt_launches word.  y0 is the evaluation's.
+// ------------------------------------------------------------------------------------------
+#if defined(OGK_HAS_MIX) && defined(OG_GEN_HAS_PAR)
+#include "og_mix.h"
+constexpr int MIX_THREADS = OG_ADJ_CHAINS;
+constexpr int MIX_WAVES = MIX_THREADS / 64;
+static_assert(MIX_WAVES == 4, "og_adj_tree combines four blocks of 64 chains");
+
+struct MixTables {
+    __device__ __forceinline__ int4 col(const int j) const { return OGT_COL[j]; }
+    __device__ __forceinline__ int4 elem(const int e) const { return OGT_ELEM[e]; }
+    __device__ __forceinline__ const ogt_int8& slot(const int s) const { return OGT_SLOT[s]; }
+};
+
+inline int mix_grid() { return OgGen::N_HEAVY + (OgGen::N_VAR + MIX_WAVES - 1) / MIX_WAVES; }
+
+// Block chain >> 6 of column j by the 64 lanes of one wavefront (chain: this lane's): the chain (og_mix_chain), then the
+// levels s = 32 .. 1 of og_adj_tree -> valid in lane 0 (lane i of level s needs lane i + s < 2 s <= 64 only).  A block
+// past the last term is +0.0 in every lane without any work.
+__device__ __forceinline__ double mix_block_sum(const ogk_args& a, const MixTables& tab, const OgAdjCol& c, const int j,
+                                                const int seed, const double* w, const int chain) {
+    double r = og_mix_chain<OgGen>(tab, c, j, seed, chain, w, a.x0, a.y0, a.cvec, a.dfrag);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) r = r + __shfl_down(r, s, 64);
+    return r;
+}
+
+// w[M]: the weight vector, kp: the parameter, s[N_VAR]: the row of the result.  blockIdx.x: heavy columns first, then
+// four light columns per workgroup.
+__device__ __forceinline__ void exact_mix_block(const ogk_args& a, const double* w, const int kp, double* s) {
+    __shared__ double part[MIX_WAVES];
+    const int id = (int)blockIdx.x, tid = (int)threadIdx.x;
+    // (the same in all 64 lanes of a wavefront - said to the compiler, so that the column's tables stay scalar loads)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int seed = OgGen::PAR_OFF + kp;
+    const MixTables tab;
+    if (id < OgGen::N_HEAVY) {                      // the whole workgroup: every thread reaches the barrier
+        const int j = OGT_HEAVY[id];
+        const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+        const double r = mix_block_sum(a, tab, c, j, seed, w, tid);
+        if ((tid & 63) == 0) part[wave] = r;
+        __syncthreads();
+        if (tid == 0) s[j] = (part[0] + part[1]) + (part[2] + part[3]);
+        return;
+    }
+    const int j = (id - OgGen::N_HEAVY) * MIX_WAVES + wave;
+    if (j >= OgGen::N_VAR || (OGT_COL[j].w & HEAVY_FLAG)) return;   // (the whole wavefront; a heavy column has its own)
+    const OgAdjCol c = og_adj_col<OgGen>(tab, j, a.x0, a.cvec);
+    const int lane = tid & 63;
+    double acc = 0.0, u = 0.0;
+    // (p0 + p1) + (p2 + p3): acc = p0, acc += p1, u = p2, acc += u + p3
+#pragma unroll 1
+    for (int b = 0; b < MIX_WAVES; ++b) {
+        const double r = mix_block_sum(a, tab, c, j, seed, w, b * 64 + lane);
+        if (b == 0) acc = r;
+        else if (b == 1) acc = acc + r;
+        else if (b == 2) u = r;
+        else acc = acc + (u + r);
+    }
+    if (lane == 0) s[j] = acc;
+}
+
+// blockIdx.y = d * N_PAR + k: weight vector d of the K of this point at h + d * m, parameter k, its row of the result at
+// jt + blockIdx.y * n
+__global__ __launch_bounds__(MIX_THREADS) void ogk_exact_mix(const ogk_args a) {
+    const int pair = (int)blockIdx.y, d = pair / OgGen::N_PAR, kp = pair - d * OgGen::N_PAR;
+    exact_mix_block(a, a.h + (long)d * OgGen::M, kp, a.jt + (long)pair * OgGen::N_VAR);
+}
+
+// the same on a lane's record (blockIdx.z: the lane, blockIdx.y: the parameter; the record's own cvec gives every lane
+// its own theta): the weights are row `lane` of W[count][m], the result slice `lane` of S[count][n_par][n] (the launch's
+// own arguments)
+__global__ __launch_bounds__(MIX_THREADS) void ogk_exact_mix_batch(const ogk_args* __restrict__ lanes, const double* W,
+                                                                   double* S) {
+    const long lane = (long)blockIdx.z;
+    const int kp = (int)blockIdx.y;
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_mix_block(a, W + lane * OgGen::M, kp, S + (lane * OgGen::N_PAR + kp) * OgGen::N_VAR);
+}
+#endif
+
 #ifdef OGK_HAS_SWEEP
 __global__ __launch_bounds__(SWEEP_THREADS) void ogk_sweep(const ogk_args a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2369,6 +2465,19 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
         return (int)hipGetLastError();
     }
 #endif
+#ifdef OGK_HAS_MIX
+    if (mode == OGK_MIX) {
+#ifdef OG_GEN_HAS_PAR
+        // ncols weight vectors, ncols * N_PAR pairs (gridDim.y)
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || ncols < 1 || (long)ncols * OgGen::N_PAR > 65535)
+            return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ogk_exact_mix, dim3(mix_grid(), ncols * OgGen::N_PAR), dim3(MIX_THREADS), 0, stream, *args);
+        return (int)hipGetLastError();
+#else
+        return (int)hipErrorInvalidValue;           // a module without run-time parameters
+#endif
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2475,5 +2584,24 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
     hipLaunchKernelGGL(ogk_exact_hvp_batch, dim3(hvp_grid(), 1, b->count), dim3(HVP_THREADS), 0, stream,
                        (const ogk_args*)b->lanes, b->H, b->vals);
     return (int)hipGetLastError();
+}
+#endif
+
+#ifdef OGK_HAS_MIX
+// the mixed part's batched mode, under the entry name of the batch parts as the adjoint part's is; any other mode is
+// another part's.  H: the weight vectors W[count][m], vals: the result S[count][n_par][n] (the lane records hold neither)
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mode != OGK_BATCH_MIX) return OGK_OTHER_PART;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || !b->H || !b->vals)
+        return (int)hipErrorInvalidValue;
+#ifdef OG_GEN_HAS_PAR
+    hipLaunchKernelGGL(ogk_exact_mix_batch, dim3(mix_grid(), OgGen::N_PAR, b->count), dim3(MIX_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes, b->H, b->vals);
+    return (int)hipGetLastError();
+#else
+    (void)stream;
+    return (int)hipErrorInvalidValue;               // a module without run-time parameters
+#endif
 }
 #endif

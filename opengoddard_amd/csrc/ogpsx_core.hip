@@ -230,6 +230,13 @@ struct og_problem_s {
     ogk_launch_batch_fn hvp_launch_batch = nullptr;
     double* d_hvp = nullptr;
     size_t hvp_capacity = 0;
+    // exact mixed derivatives d(F'(x)^T w)/dtheta (og_adjoint_parameter_load): the same arrangement;
+    // d_mix: [W[k][m] | S[k][n_par][n]] staging of the host-pointer call, mix_capacity weight vectors large
+    void* mix_module = nullptr;
+    ogk_launch_fn mix_launch = nullptr;
+    ogk_launch_batch_fn mix_launch_batch = nullptr;
+    double* d_mix = nullptr;
+    size_t mix_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -880,6 +887,7 @@ void og_problem_destroy(og_handle p) {
     if (p->dir_module) dlclose(p->dir_module);
     if (p->adj_module) dlclose(p->adj_module);
     if (p->hvp_module) dlclose(p->hvp_module);
+    if (p->mix_module) dlclose(p->mix_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -889,6 +897,7 @@ void og_problem_destroy(og_handle p) {
     hipFree(p->d_dir);
     hipFree(p->d_adj);
     hipFree(p->d_hvp);
+    hipFree(p->d_mix);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1422,6 +1431,7 @@ struct og_batch_s {
     double* d_dj = nullptr;                 // [capacity][m] staging of the host-pointer og_directional_batch
     double* d_aj = nullptr;                 // [W[capacity][m] | G[capacity][n]] staging of the host-pointer og_adjoint_batch
     double* d_hj = nullptr;                 // [W[capacity][m] | Q[capacity][n]] staging of the host-pointer og_hessian_vector_batch
+    double* d_mj = nullptr;                 // [W[capacity][m] | S[capacity][n_par][n]] staging of the host-pointer og_adjoint_parameter_batch
 };
 
 namespace {
@@ -1602,6 +1612,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_dj);
     hipFree(b->d_aj);
     hipFree(b->d_hj);
+    hipFree(b->d_mj);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -2426,6 +2437,141 @@ int og_hessian_vector_batch(og_batch b, int32_t count, const double* X, const do
     rc = og_hessian_vector_batch_dev(b, count, b->d_xh, d_W, b->d_xh + cap * n, b->d_f, d_Q, p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(Q, d_Q, sizeof(double) * c * n, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- exact mixed derivatives d(F'(x)^T w)/dtheta_k for the run-time parameters (include/ogpsx.h) ----
+static int adjoint_parameter_check(const og_problem_s* p, const char* who) {
+    if (p->n_par == 0) return fail(1, std::string(who) + ": the module has no run-time parameters");
+    if (!p->mix_launch)
+        return fail(4, std::string(who) + ": the module's mixed part is not loaded (og_adjoint_parameter_load)");
+    return 0;
+}
+
+// (one launch: the pairs of a weight vector and a parameter are a grid dimension, the lanes of a batch another)
+static int adjoint_parameter_count_check(const og_problem_s* p, int32_t k, const char* who) {
+    if (k < 1) return fail(1, std::string(who) + ": k must be at least 1");
+    if ((int64_t)k * (int64_t)p->n_par > OG_MAX_WEIGHT_VECTORS)
+        return fail(1, std::string(who) + ": k " + std::to_string(k) + " times " + std::to_string(p->n_par) +
+                           " parameters exceeds " + std::to_string(OG_MAX_WEIGHT_VECTORS) + " pairs of one call");
+    return 0;
+}
+
+int og_adjoint_parameter_load(og_handle p, const char* mix_part_path) {
+    if (!p) return fail(1, "og_adjoint_parameter_load: null handle");
+    if (p->n_par == 0) return fail(1, "og_adjoint_parameter_load: the module has no run-time parameters");
+    if (p->mix_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, mix_part_path, "og_adjoint_parameter_load", "mixed part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the mixed part knows the mode)
+    if (!fn || fn(&probe, OGK_MIX, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_adjoint_parameter_load: the mixed part does not belong to the handle's module");
+    }
+    p->mix_module = mod;
+    p->mix_launch = fn;
+    p->mix_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_adjoint_parameter_dev(og_handle p, const double* d_x, int32_t k, const double* d_W, double* d_S, double* d_F0,
+                             void* hip_stream) {
+    if (!p || !d_x || !d_W || !d_S) return fail(1, "og_adjoint_parameter_dev: null argument");
+    int rc = adjoint_parameter_check(p, "og_adjoint_parameter_dev");
+    if (!rc) rc = adjoint_parameter_count_check(p, k, "og_adjoint_parameter_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (as og_adjoint_dev: no J_T among the arguments, the weight vectors in the step pointer and their number as a column
+    // range)
+    fill_args(p, &a, d_x, d_W, d_F0 ? d_F0 : p->d_f0, nullptr, 0, k);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_S;
+    if (!rc) rc = p->mix_launch(&a, OGK_MIX, hip_stream);
+    return launched(rc, "og_adjoint_parameter_dev");
+}
+
+int og_adjoint_parameter(og_handle p, const double* x, int32_t k, const double* W, double* S, double* F0) {
+    if (!p || !x || !W || !S) return fail(1, "og_adjoint_parameter: null argument");
+    int rc = adjoint_parameter_check(p, "og_adjoint_parameter");
+    if (!rc) rc = adjoint_parameter_count_check(p, k, "og_adjoint_parameter");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, kk = (size_t)k, out = (size_t)p->n_par * n;
+    if (kk > p->mix_capacity) {
+        if (p->d_mix) OG_HIP(hipFree(p->d_mix));
+        p->d_mix = nullptr;
+        p->mix_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_mix, sizeof(double) * kk * (m + out)));
+        p->mix_capacity = kk;
+    }
+    double *d_W = p->d_mix, *d_S = d_W + kk * m;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * kk * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_adjoint_parameter_dev(p, p->d_x, k, d_W, d_S, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(S, d_S, sizeof(double) * kk * out, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_adjoint_parameter_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                   double* d_S, void* hip_stream) {
+    int rc = batch_check(b, count, "og_adjoint_parameter_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_W || !d_S) return fail(1, "og_adjoint_parameter_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = adjoint_parameter_check(p, "og_adjoint_parameter_batch_dev");
+    if (!rc && count > OG_MAX_WEIGHT_VECTORS)
+        rc = fail(1, "og_adjoint_parameter_batch_dev: count " + std::to_string(count) + " exceeds " +
+                         std::to_string(OG_MAX_WEIGHT_VECTORS) + " lanes of one call");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T.  The records
+    // learn X and F0 only, as in og_adjoint_batch_dev: the weight vectors [count][m] and the result [count][n_par][n]
+    // are arguments of the mixed launch itself
+    rc = batch_bind(b, count, d_X, nullptr, d_F0 ? d_F0 : b->d_f, nullptr, 1, s, "og_adjoint_parameter_batch_dev");
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        ogk_batch_args ba = batch_args(b, 1, count);
+        ba.H = d_W, ba.vals = d_S, ba.nnz = (int64_t)p->n_par * (int64_t)p->n;
+        rc = p->mix_launch_batch(&ba, OGK_BATCH_MIX, s);
+    }
+    return launched(rc, "og_adjoint_parameter_batch_dev");
+}
+
+int og_adjoint_parameter_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* S) {
+    int rc = batch_check(b, count, "og_adjoint_parameter_batch");
+    if (rc) return rc;
+    if (!X || !W || !S) return fail(1, "og_adjoint_parameter_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = adjoint_parameter_check(p, "og_adjoint_parameter_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t n = (size_t)p->n, m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    const size_t out = (size_t)p->n_par * n;
+    if (!b->d_mj) OG_HIP(hipMalloc(&b->d_mj, sizeof(double) * cap * (m + out)));
+    double *d_W = b->d_mj, *d_S = b->d_mj + cap * m;
+    rc = batch_upload(b, c, X, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_adjoint_parameter_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_S, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(S, d_S, sizeof(double) * c * out, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
     return 0;

@@ -276,6 +276,43 @@ class HipEngine:
         _native.check(self._lib.og_hessian_vector_dev(self._handle, d_x, int(k), d_W, d_V, d_Q, d_F0, stream),
                       "og_hessian_vector_dev")
 
+    # ------------------------------------------------------------------ exact d(F'(x)^T w)/dtheta
+    def _load_mix_part(self):
+        """The module's mixed part (``build.build_mix_part``): compiled by the first mixed-derivative call, loaded once
+        per handle (``og_adjoint_parameter_load``)."""
+        if self.n_par == 0:
+            raise ValueError("this problem declares no parameter")
+        if getattr(self, "mix_part_path", None) is None:
+            path = build.build_mix_part(self.header)
+            _native.check(self._lib.og_adjoint_parameter_load(self._handle, path.encode()), "og_adjoint_parameter_load")
+            self.mix_part_path = path
+
+    def adjoint_parameter(self, x, W):
+        """``(S, F0)``: ``S[d, k, j] = sum_r W[d, r] d2F_r/dx_j dtheta_k``, ``[K, n_par, n]``, the EXACT derivative of the
+        adjoint product ``F'(x)^T W[d]`` with respect to every run-time parameter at ``x`` and the parameters on the
+        device, for each of the ``K`` weight vectors ``W[d]`` (``[K, m]``, over the rows of ``F``)
+        (``og_adjoint_parameter``: an evaluation and one launch, a grid slice per pair of a vector and a parameter;
+        second-order dual numbers with the second seed on the parameter's table entry, the order of every sum fixed -
+        csrc/og_mix.h), and ``F0 = F(x)``.  With ``devices=[...]`` the first device's handle serves it; the call is not
+        split."""
+        self._load_mix_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if W.ndim != 2 or W.shape[1] != self.m or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, %d] with K >= 1, got %s" % (self.m, W.shape))
+        S, F0 = np.empty((W.shape[0], self.n_par, self.n)), np.empty(self.m)
+        _native.check(self._lib.og_adjoint_parameter(self._handle, _native.dptr(x), W.shape[0], _native.dptr(W),
+                                                     _native.dptr(S), _native.dptr(F0)), "og_adjoint_parameter")
+        return S, F0
+
+    def adjoint_parameter_dev(self, d_x, k, d_W, d_S, d_F0=None, stream=0):
+        """``og_adjoint_parameter_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_W`` ``[k, m]``, ``d_S``
+        ``[k, n_par, n]``, ``d_F0`` ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_mix_part()
+        _native.check(self._lib.og_adjoint_parameter_dev(self._handle, d_x, int(k), d_W, d_S, d_F0, stream),
+                      "og_adjoint_parameter_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -666,6 +703,34 @@ class BatchSweep:
         self.engine._load_hessian_part()
         _native.check(self._lib.og_hessian_vector_batch_dev(self._handle, int(count), d_X, d_W, d_V, d_F0, d_Q, stream),
                       "og_hessian_vector_batch_dev")
+
+    def adjoint_parameter(self, X, W, count=None):
+        """``(S[B, n_par, n], F0[B, m])``: lane ``k``'s exact ``d(F'(X[k])^T W[k])/dtheta`` - one weight vector (``m``
+        entries) per lane, every parameter, at the lane's own parameters (:meth:`set_parameters`) - bit for bit
+        :meth:`HipEngine.adjoint_parameter` at that point, vector and those values (``og_adjoint_parameter_batch``;
+        three launches whatever ``B`` is).  ``count``: only the first ``count`` rows (default: all).  No lane's J_T is
+        written."""
+        X = self._points(X, "X")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.m:
+            raise ValueError("BatchSweep: W must have shape [B, %d], got %s" % (self.m, W.shape))
+        if W.shape[0] != X.shape[0]:
+            raise ValueError("BatchSweep: %d weight vectors for %d points" % (W.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_mix_part()
+        S, F0 = np.empty((B, self.engine.n_par, self.n)), np.empty((B, self.m))
+        _native.check(self._lib.og_adjoint_parameter_batch(self._handle, B, _native.dptr(X), _native.dptr(W),
+                                                           _native.dptr(F0), _native.dptr(S)), "og_adjoint_parameter_batch")
+        return S, F0
+
+    def adjoint_parameter_dev(self, count, d_X, d_W, d_S, d_F0=None, stream=0):
+        """``og_adjoint_parameter_batch_dev``: ``d_X`` ``[count, n]``, ``d_W`` ``[count, m]``, ``d_S``
+        ``[count, n_par, n]``, ``d_F0`` ``[count, m]`` or None."""
+        self.engine._load_mix_part()
+        _native.check(self._lib.og_adjoint_parameter_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_S, stream),
+                      "og_adjoint_parameter_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

@@ -77,6 +77,7 @@ class BatchResult:
         self.directional = None         # [B, m]: exact F'(x_k) v_k (evaluate_batch(directions=V))
         self.adjoint = None             # [B, n]: exact F'(x_k)^T w_k (evaluate_batch(adjoints=W))
         self.hessian_product = None     # [B, n]: exact grad^2 (w_k . F)(x_k) v_k (evaluate_batch(hessian_products=(W, V)))
+        self.adjoint_parameter = None   # [B, n_par, n]: exact d(F'(x_k)^T w_k)/dtheta (evaluate_batch(adjoint_parameter=W))
 
     def __len__(self):
         return self.cost.shape[0]
@@ -770,9 +771,39 @@ class Problem:
                      copy=True)
         return Q[0] if single else Q
 
+    def adjoint_parameter_sensitivity(self, obj, weights, p=None):
+        """``d(F'(p)^T w)/dtheta``, ``s_{k,j} = sum_r w_r d2F_r/dx_j dtheta_k``, of ``F = [cost | c_eq | c_ineq]`` for every
+        declared run-time parameter at the decision vector ``p`` (default ``prob.p``) and the current parameter values,
+        EXACT (``HipEngine.adjoint_parameter``: an evaluation and one launch for all ``K`` weight vectors and all
+        parameters; second-order dual numbers with the second seed on the parameter, no step in ``theta`` and no
+        ``set_parameters`` launch).  ``weights``: ``[K, m]`` over the rows of ``F`` -> ``[K, n_par, number_of_variables]``,
+        or one vector -> ``[n_par, number_of_variables]``.  With ``w = [1, lambda]`` it is ``d(grad_x L)/dtheta``: the
+        block of the linearised KKT system next to :meth:`hessian_vector_product`, :meth:`directional_derivative` /
+        :meth:`adjoint_product` and :meth:`parameter_sensitivity`, the right-hand side of a continuation tangent.  The
+        order of every sum is :meth:`adjoint_product`'s, so the result is reproducible to the bit; a parameter nothing
+        reads gets a row of ``+0.0``.  A problem that declares no parameter, an engine without ``adjoint_parameter``
+        and a weight vector of the wrong length are ``ValueError``s."""
+        W = np.asarray(weights, dtype=float)
+        single = W.ndim == 1
+        if single:
+            W = W[None, :]
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, m] or [m], got shape %s" % (np.shape(weights),))
+        if not self._par_names:
+            raise ValueError("this problem declares no parameter")
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "adjoint_parameter"):
+            raise ValueError("this engine has no exact mixed derivative (it has no adjoint_parameter)")
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+        m = self._rows_of(engine, point)
+        if W.shape[1] != m:
+            raise ValueError("weights must have %d entries (the rows of F) each, got shape %s" % (m, np.shape(weights)))
+        S = np.array(engine.adjoint_parameter(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
+        return S[0] if single else S
+
     # ------------------------------------------------------------------ many points at once
     def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None,
-                       adjoints=None, hessian_products=None):
+                       adjoints=None, hessian_products=None, adjoint_parameter=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -822,8 +853,17 @@ class Problem:
         point by point through its ``hessian_vector``, without one: ``ValueError``).  A point with its own row of
         ``parameters`` is differentiated at those values; one point scanned over ``parameters`` takes its one pair
         along.  It combines with every other keyword.  ``None``: nothing is computed and the call builds, loads and
-        launches exactly what it does without the keyword."""
-        if parameter_jacobian and not self._par_names:
+        launches exactly what it does without the keyword.
+
+        ``adjoint_parameter=W`` (``[B, m]``, one weight vector over the rows of ``F`` per row of ``points``) adds
+        ``BatchResult.adjoint_parameter``, ``[B, n_par, number_of_variables]``: the EXACT ``d(F'(x_k)^T w_k)/dtheta`` of
+        every point with its own vector, for every declared parameter (``BatchSweep.adjoint_parameter``; a stand-in
+        engine is served point by point through its ``adjoint_parameter``, without one: ``ValueError``).  A point with
+        its own row of ``parameters`` is differentiated at those values; one point scanned over ``parameters`` takes
+        its one vector along.  It combines with every other keyword; a problem without parameters is a ``ValueError``.
+        ``None``: nothing is computed and the call builds, loads and launches exactly what it does without the
+        keyword."""
+        if (parameter_jacobian or adjoint_parameter is not None) and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
         if directions is not None:
@@ -839,6 +879,13 @@ class Problem:
                 raise ValueError("adjoints must have shape [B, m] (the rows of F), got %s" % (adjoints.shape,))
             if points.ndim == 2 and adjoints.shape[0] != points.shape[0]:
                 raise ValueError("adjoints holds %d rows for %d points" % (adjoints.shape[0], points.shape[0]))
+        mix_w = None
+        if adjoint_parameter is not None:
+            mix_w = np.asarray(adjoint_parameter, dtype=float)
+            if mix_w.ndim != 2:
+                raise ValueError("adjoint_parameter must have shape [B, m] (the rows of F), got %s" % (mix_w.shape,))
+            if points.ndim == 2 and mix_w.shape[0] != points.shape[0]:
+                raise ValueError("adjoint_parameter holds %d rows for %d points" % (mix_w.shape[0], points.shape[0]))
         hess_w = hess_v = None
         if hessian_products is not None:
             if not isinstance(hessian_products, (tuple, list)) or len(hessian_products) != 2:
@@ -874,6 +921,8 @@ class Problem:
                 adjoints = np.repeat(adjoints, TH.shape[0], axis=0)
             if hess_w is not None:
                 hess_w, hess_v = np.repeat(hess_w, TH.shape[0], axis=0), np.repeat(hess_v, TH.shape[0], axis=0)
+            if mix_w is not None:
+                mix_w = np.repeat(mix_w, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
         if directions is not None:
             directions = np.ascontiguousarray(directions)
@@ -893,6 +942,13 @@ class Problem:
             if hess_w.shape[1] != m_rows:
                 raise ValueError("hessian_products must have shapes [B, %d] and [B, %d], got %s and %s" % (
                     m_rows, n, hess_w.shape, hess_v.shape))
+        if mix_w is not None:
+            if not hasattr(engine, "adjoint_parameter"):
+                raise ValueError("this engine has no exact mixed derivative (it has no adjoint_parameter)")
+            mix_w = np.ascontiguousarray(mix_w)
+            m_rows = self._rows_of(engine, points[0])
+            if mix_w.shape[1] != m_rows:
+                raise ValueError("adjoint_parameter must have shape [B, %d] (the rows of F), got %s" % (m_rows, mix_w.shape))
         used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
@@ -913,7 +969,7 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = along = back = curv = None
+            par_jac = along = back = curv = mixed = None
             try:
                 if parameter_jacobian:
                     par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
@@ -926,13 +982,16 @@ class Problem:
                 if hess_w is not None:
                     curv = np.stack([np.array(engine.hessian_vector(p, hess_w[k:k + 1], hess_v[k:k + 1])[0],
                                               dtype=float).reshape(-1) for k, p in enumerate(lanes())])
+                if mix_w is not None:
+                    mixed = np.stack([np.array(engine.adjoint_parameter(p, mix_w[k:k + 1])[0], dtype=float)[0]
+                                      for k, p in enumerate(lanes())])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
                     res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-                    res.hessian_product = curv
+                    res.hessian_product, res.adjoint_parameter = curv, mixed
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -954,7 +1013,7 @@ class Problem:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-            res.hessian_product = curv
+            res.hessian_product, res.adjoint_parameter = curv, mixed
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -992,10 +1051,15 @@ class Problem:
             if not hasattr(batch, "hessian_vector"):
                 raise ValueError("this engine has no exact Hessian-vector product (its batch has no hessian_vector)")
             curv = batch.hessian_vector(points, hess_w, hess_v)[0]
+        mixed = None
+        if mix_w is not None:
+            if not hasattr(batch, "adjoint_parameter"):
+                raise ValueError("this engine has no exact mixed derivative (its batch has no adjoint_parameter)")
+            mixed = batch.adjoint_parameter(points, mix_w)[0]
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-            res.hessian_product = curv
+            res.hessian_product, res.adjoint_parameter = curv, mixed
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -1004,7 +1068,7 @@ class Problem:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
         res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-        res.hessian_product = curv
+        res.hessian_product, res.adjoint_parameter = curv, mixed
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost
