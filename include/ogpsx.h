@@ -543,6 +543,47 @@ int og_adjoint_parameter_batch_dev(og_batch b, int32_t count, const double* d_X,
                                    double* d_S, void* hip_stream);
 int og_adjoint_parameter_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* S);
 
+/* ---- the exact sparse Hessian of w . F, assembled -----------------------------------------------------
+ * H[d][p] = sum_r W[d][r] d2F_r/dx_j dx_l for every stored pair p = (j, l), l <= j, of a static lower-triangle pattern
+ * in CSR form (indptr[n + 1], cols[nnz]: the partners l of variable j at row j), [k][nnz] row-major, for k weight vectors
+ * W[d][m] over the rows of F = [cost | c_eq | c_ineq]: with W = [1, lambda] the Hessian of the Lagrangian as a sparse
+ * matrix - a sparse-direct Newton or interior-point step, the (1, 1) block of the KKT matrix, a reduced-Hessian check.
+ * The pattern and, per stored entry, its owner (the variable of the pair whose column of the exact Jacobian the terms are
+ * taken from) and the list of the owner's term numbers that read the other variable are DATA the caller passes once
+ * (opengoddard_amd.codegen.HessianPlan: indptr, cols, owner[nnz], tptr[nnz + 1], tlist); every pair outside the pattern is
+ * an exact zero of the Hessian.  A stored entry is og_hessian_vector's Q[owner] for the unit direction on the other
+ * variable restricted to the listed terms (csrc/og_hess.h): for finite weights and a finite point bit for bit that
+ * product (but for a lone product that underflows to -0.0, see the header), reproducible to the bit, vector d of a call
+ * with k vectors bit for bit the call with that vector alone.  A row whose weight is zero is not skipped; every call
+ * writes all k * nnz doubles, no more; a run-time parameter is a constant.
+ * Load rule: the kernels live in a part of the callback module of its own (part_path:
+ * opengoddard_amd.build.build_hessian_matrix_part).  og_hessian_matrix_load loads it and uploads the plan once per
+ * handle - a later call is a no-op and may pass NULLs - and og_problem_destroy closes and frees both; error 4: the part
+ * is missing or cannot be loaded, 5: it belongs to another module, 1 (no kernel ever sees the plan, nothing stays loaded): a null
+ * array, nnz < 0, pointers that are not monotone or do not end at nnz / the length of tlist, a partner above its row or
+ * not ascending within it, an owner that is neither variable of its pair, a term list that does not ascend or names a
+ * term the owner's column does not have.  og_hessian_matrix_nnz: the loaded plan's nnz, -1 while none is loaded.  The
+ * other four fail with error 4 while nothing is loaded, and with error 1 (and a message in og_last_error) for null
+ * pointers, k < 1 or k > 65535, or a count outside 1 .. capacity.
+ * og_hessian_matrix_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own array
+ * when d_F0 is NULL) and the Hessian-matrix kernel, which evaluates an entry's terms once per chunk of 8 weight vectors.
+ * Asynchronous and capturable: a captured graph replays on new contents of d_x and d_W.  No J_T is written and no
+ * registered buffer's bookkeeping moves.  og_hessian_matrix: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], with the ONE weight vector W[c] and at the lane's own parameters
+ * (og_parameters_batch*), and writes H[c][nnz] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit the single-point call at
+ * that point, vector and those values.  Three launches whatever count is: bind, the batched evaluation, the kernel.
+ * A multi-device handle (og_multi_*) has no form of this call and does not split it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_hessian_matrix_load(og_handle h, const char* part_path, int32_t nnz, const int32_t* indptr, const int32_t* cols,
+                           const int32_t* owner, const int32_t* tptr, const int32_t* tlist);
+int32_t og_hessian_matrix_nnz(og_handle h);
+int og_hessian_matrix_dev(og_handle h, const double* d_x, int32_t k, const double* d_W, double* d_H, double* d_F0,
+                          void* hip_stream);
+int og_hessian_matrix(og_handle h, const double* x, int32_t k, const double* W, double* H, double* F0);
+int og_hessian_matrix_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                double* d_H, void* hip_stream);
+int og_hessian_matrix_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* H);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

@@ -71,7 +71,7 @@ def _core_sources():
 
 def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
-                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h", "og_mix.h")]
+                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h", "og_mix.h", "og_hess.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -261,6 +261,21 @@ def build_mix_part(header_source, force=False):
     ``BatchSweep.adjoint_parameter``): the module and the other on-demand parts are what they were, and a user who never
     asks builds and loads what they did before."""
     return _build_on_demand_part(header_source, MIX_PART, mix_part_path, force)
+
+
+HESSIAN_MATRIX_PART = 11        # OGK_PART_HESS, <module>.hess.so: the exact sparse Hessian of w . F
+
+
+def hessian_matrix_part_path(out):
+    return out[:-3] + ".hess.so"
+
+
+def build_hessian_matrix_part(header_source, force=False):
+    """``ogk_exact_hess`` / ``ogk_exact_hess_batch`` (``OGK_PART=11``) -> path of ``<module>.hess.so``.  A part of its
+    own, built when an assembled Hessian is first asked for (``HipEngine.hessian_matrix``, ``BatchSweep.hessian_matrix``):
+    the module and the other on-demand parts are what they were, and a user who never asks builds and loads what they
+    did before.  (``hessian_part_path`` and ``.hvp.so`` stay the Hessian-vector part's.)"""
+    return _build_on_demand_part(header_source, HESSIAN_MATRIX_PART, hessian_matrix_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

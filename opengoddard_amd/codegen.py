@@ -947,6 +947,95 @@ class SweepPlan:
         return {item: hi - lo + i for i, item in enumerate(self.items[j])}
 
 
+class HessianPlan:
+    """The static pattern of the Hessian of ``w . F`` and, per stored entry, which terms can be non-zero - data for
+    ``og_hessian_matrix_load`` (include/ogpsx.h; csrc/og_hess.h walks it), never part of the generated header::
+
+        indptr[n+1], cols[nnz]      the lower triangle in CSR form: the partners ``l <= j`` of variable j at row j,
+                                    ascending
+        owner[nnz]                  the variable of the pair whose column (csrc/og_adj.h) the entry's terms are taken
+                                    from: the one with fewer terms, the larger index on a tie
+        tptr[nnz+1], tlist          the owner's term numbers (og_adj.h: row items, then the own collocation block)
+                                    that read the other variable of the pair, ascending
+        terms[n]                    the number of terms of every column
+
+    A pair is stored iff some term of one variable's column reads the other variable.  What a term reads: a row item
+    (group, output, element) the leaves of ``Group.deps`` / ``out_deps`` at that element; defect row k of the own
+    collocation block of x_j the variable itself (the operand term, every k - so every collocated variable has its
+    diagonal) and, where ``og_adj_col``'s ``reads`` bits let the dynamics term in (bit 1: every k, bit 0: k == l), the
+    leaves of that state's dynamics term at node k.  Every other second derivative is an exact zero."""
+
+    def __init__(self, P, plan=None):
+        plan = plan or SweepPlan(P)
+        n = P.n
+
+        def leaves(deps, length, k):
+            out = set()
+            for kind, base, cnt in deps:
+                if kind == 1:
+                    out.add(base + k)
+                elif kind == 0:
+                    out.add(base)
+                else:
+                    out.update(range(base, base + cnt))
+            return out
+
+        memo = {}
+
+        def item_reads(gi, o, k):
+            key = (gi, o, k)
+            if key not in memo:
+                g = P.groups[gi]
+                memo[key] = leaves(g.out_deps[o] if g.kind == "defect" else g.deps, g.length, k)
+            return memo[key]
+
+        slot_of = {}
+        for si, sl in enumerate(P.mv):
+            for l in range(sl.length):
+                slot_of[sl.leaf_base + l] = (si, l)
+        reads = []                      # reads[j][t]: the variables term t of column j reads
+        for j in range(n):
+            col = [item_reads(gi, o, k) for gi, o, k in plan.items[j]]
+            if j in slot_of and plan.own[j][1] > plan.own[j][0]:
+                si, l = slot_of[j]
+                gi = plan.slot_group[si]
+                o = si - P.groups[gi].mv_slots[0]
+                for k in range(P.mv[si].length):
+                    tail = plan.mv_generic[si] or (plan.mv_diag[si] and k == l)
+                    # (the bits are the group's: this state's own dynamics term may not read x_j, and has no curvature
+                    # along it then)
+                    tail = tail and j in item_reads(gi, o, k)
+                    col.append({j} | (item_reads(gi, o, k) if tail else set()))
+            reads.append(col)
+        self.terms = [len(col) for col in reads]
+        by_partner = []                 # by_partner[j][b]: the terms of column j that read x_b, ascending
+        for col in reads:
+            inv = {}
+            for t, rd in enumerate(col):
+                for b in rd:
+                    inv.setdefault(b, []).append(t)
+            by_partner.append(inv)
+        rows = [set() for _ in range(n)]
+        for a in range(n):
+            for b in by_partner[a]:
+                rows[max(a, b)].add(min(a, b))
+        self.indptr, self.cols, self.owner, self.tptr, self.tlist = [0], [], [], [0], []
+        for j in range(n):
+            for l in sorted(rows[j]):
+                own, other = (l, j) if self.terms[l] < self.terms[j] else (j, l)
+                self.cols.append(l)
+                self.owner.append(own)
+                self.tlist.extend(by_partner[own].get(other, ()))
+                self.tptr.append(len(self.tlist))
+            self.indptr.append(len(self.cols))
+        self.n, self.nnz = n, len(self.cols)
+
+    def arrays(self):
+        """``(indptr, cols, owner, tptr, tlist)`` as contiguous ``int32`` arrays (``tlist`` never empty: one unused 0)."""
+        return tuple(np.ascontiguousarray(a if len(a) else [0], dtype=np.int32)
+                     for a in (self.indptr, self.cols, self.owner, self.tptr, self.tlist))
+
+
 def _parameters_read(P, eid):
     """Indices of the run-time parameters the element ``eid`` reads (through the terms of sums too)."""
     if not P.n_par:

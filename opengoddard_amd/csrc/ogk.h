@@ -95,8 +95,33 @@ enum ogk_mode {
 #define OGK_MIX 23
 #define OGK_BATCH_MIX 24
 
+// The two modes of the Hessian-matrix part (OGK_PART_HESS; macros for the same reason): the exact sparse Hessian of
+// w . F, every stored entry of a static pattern (csrc/og_hess.h; the pattern and the entries' term lists are data,
+// codegen.HessianPlan, which the runtime uploads as the device plan below).  OGK_HESS (ogk_launch): K = col_hi - col_lo
+// weight vectors of one point, vector d read at args->h + d * m as in OGK_ADJ, its [nnz] doubles in pattern order written
+// to args->jt + d * nnz; args->prow is the device plan (no packed rows travel in this mode) and uhi - ulo the workgroups
+// of one chunk of vectors, OGK_HESS_WORKGROUPS of the plan's head.  OGK_BATCH_HESS
+// (ogk_launch_batch): one weight vector per lane, lane c reads H + c * m and writes vals + c * nnz of the launch's own
+// ogk_batch_args, whose X is the device plan (cast; OGK_BATCH_BIND before it binds the points) and whose nnz is the
+// number of workgroups of one lane; every lane at its own parameters.  Both need an evaluation at the same point before them on the same stream
+// (y0), write every stored entry of every vector in the order of sums that og_hess.h fixes, and touch no
+// jt_state / jt_launches word.  ogk_hess_terms (exported by this part only): the number of terms of every column, what
+// a plan's term numbers are checked against before anything is launched with it.
+//
+// The device plan, int32 words: [0] nnz, [1] n_light, [2] n_units, [3] [4] [5] the offsets (in words) of tptr, tlist and
+// unit, [6] [7] zero; from word 8 on one record {owner, partner, pos, 0} per stored entry - the n_light entries of at
+// most OGK_HESS_LIGHT_TERMS listed terms first, grouped by owner, then the others - pos its place in pattern order and
+// in the output; tptr[nnz + 1] by pos and tlist as in the plan; unit[n_units + 1]: runs of light entries of ONE owner, at
+// most OGK_HESS_UNIT_ENTRIES each (a wavefront's work: the owner's column lookup once per run).
+#define OGK_HESS 25
+#define OGK_BATCH_HESS 26
+#define OGK_HESS_LIGHT_TERMS 64
+#define OGK_HESS_UNIT_ENTRIES 16
+#define OGK_HESS_HEAD 8
+#define OGK_HESS_WORKGROUPS(nnz, n_light, n_units) (((nnz) - (n_light)) + ((n_units) + 3) / 4)   /* four units per workgroup */
+
 // The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
-// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART, MIX_PART).
+// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART, MIX_PART, HESSIAN_MATRIX_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -109,6 +134,7 @@ enum ogk_mode {
 #define OGK_PART_ADJ 8          /* <module>.adj.so, on demand: OGK_ADJ, OGK_BATCH_ADJ */
 #define OGK_PART_HVP 9          /* <module>.hvp.so, on demand: OGK_HVP, OGK_BATCH_HVP */
 #define OGK_PART_MIX 10         /* <module>.mix.so, on demand: OGK_MIX, OGK_BATCH_MIX */
+#define OGK_PART_HESS 11        /* <module>.hess.so, on demand: OGK_HESS, OGK_BATCH_HESS */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {
@@ -236,6 +262,10 @@ int ogk_launch(const ogk_args* args, int mode, void* stream);
 // launch into each lane's *jt_launches); every value also goes to its place in the lane's packed array when the
 // record's pvals is set.
 int ogk_launch_batch(const ogk_batch_args* args, int mode, void* stream);
+// exported by the Hessian-matrix part only (OGK_PART_HESS): terms[n], the number of terms of every column of the exact
+// Jacobian in the numbering of csrc/og_adj.h (counted on the device from the module's tables, one small blocking launch
+// that involves no plan); returns a hipError_t value
+int ogk_hess_terms(int32_t* terms);
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,7 @@
 #include <hip/hip_runtime.h>
 #include "ogk.h"
 #include "og_dual.h"
-#if defined(OGK_PART) && (OGK_PART == OGK_PART_HVP || OGK_PART == OGK_PART_MIX)
+#if defined(OGK_PART) && (OGK_PART == OGK_PART_HVP || OGK_PART == OGK_PART_MIX || OGK_PART == OGK_PART_HESS)
 #include "og_dual2.h"       // (ahead of the generated header, whose functions name ogm:: at their definition)
 #endif
 #include OG_GEN_HEADER
@@ -217,6 +217,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #endif
 #if defined(OGK_PART) && OGK_PART == OGK_PART_MIX
 #define OGK_HAS_MIX 1        // OGK_MIX, OGK_BATCH_MIX: exact mixed derivatives d(F'(x)^T w)/dtheta; built on demand
+#endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_HESS
+#define OGK_HAS_HESS 1       // OGK_HESS, OGK_BATCH_HESS: the exact sparse Hessian of w . F; built on demand
 #endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
@@ -1597,7 +1600,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
 #if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR) || \
-    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP) || defined(OGK_HAS_MIX)
+    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP) || defined(OGK_HAS_MIX) || defined(OGK_HAS_HESS)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -2148,6 +2151,173 @@ __global__ __launch_bounds__(MIX_THREADS) void ogk_exact_mix_batch(const ogk_arg
 }
 #endif
 
+// ------------------------------------------------------------------------------------------
+// Modes 25 and 26 (the Hessian-matrix part, OGK_PART_HESS): the exact sparse Hessian of w . F, [nnz] doubles per weight
+// vector in the order of a static lower-triangle pattern.  A stored entry is the sum that og_hess.h defines: the terms of
+// its owner's column that read the partner (the device plan, ogk.h: data the runtime uploads, not generated code), each
+// the mixed part of the item on second-order dual numbers with one unit seed on the owner and one on the partner, times
+// the weight of its row, in the chains and the tree of og_adj.h.  The mixed parts do not depend on w: a thread
+// evaluates its term ONCE and applies it to every weight vector of its chunk (HESS_CHUNK of them, blockIdx.y), as
+// ogk_exact_adj shares its first-order entries.  A thread takes the list position, not the chain: it adds its product
+// into chain t & 255 of its term's own number t in LDS - round r = t >> 8 after round r - 1, so that two listed terms
+// of one chain meet in ascending order - and a wavefront's 64 lanes then are 64 chains, __shfl_down the tree's levels
+// s = 32 .. 1.  The work items are the stored entries:
+//   - an entry with more than OGK_HESS_LIGHT_TERMS listed terms (the diagonal of a final time: all its thousand terms;
+//     the diagonal of a state on more than 64 nodes) gets a workgroup, which walks the list 256 positions at a time;
+//     wavefront q reduces block q of 64 chains and the four sums meet in LDS; these workgroups lead the grid;
+//   - every other entry is summed inside ONE wavefront, a position per lane.  A wavefront takes a run of entries of one
+//     owner (a unit of the plan), four units per workgroup, so the owner's column lookup (og_adj_col) and its records
+//     stay scalar loads once per run; its 256 chains are its own quarter of the LDS array, a block of 64 chains that
+//     no listed term falls into is +0.0 without being read; no workgroup barrier.
+// The result is the host probe's (og_hess_entry) bit for bit whatever the scheduling, and vector d of K is the call with
+// that vector alone.  Every stored entry of every vector is written, +0.0 for an entry without a listed term; nothing
+// else is: no atomics, no J_T, no fill, no jt_state / jt_launches word.  y0 is the evaluation's.
+// ------------------------------------------------------------------------------------------
+#ifdef OGK_HAS_HESS
+#include "og_hess.h"
+constexpr int HESS_THREADS = OG_ADJ_CHAINS;
+constexpr int HESS_WAVES = HESS_THREADS / 64;
+constexpr int HESS_CHUNK = 8;           // weight vectors per chunk: the heavy workgroup's chains, 16 KiB of LDS
+static_assert(HESS_WAVES == 4 && HESS_CHUNK >= HESS_WAVES && HESS_CHUNK <= 64 && OGK_HESS_LIGHT_TERMS == 64,
+              "og_adj_tree combines four blocks of 64 chains; a light entry is one lane per listed term");
+
+struct HessTables {
+    __device__ __forceinline__ int4 col(const int j) const { return OGT_COL[j]; }
+    __device__ __forceinline__ int4 elem(const int e) const { return OGT_ELEM[e]; }
+    __device__ __forceinline__ const ogt_int8& slot(const int s) const { return OGT_SLOT[s]; }
+};
+
+// what a wavefront wrote to LDS is what its other lanes read next (the accesses of one wavefront stay in order)
+__device__ __forceinline__ void hess_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// the levels s = 32 .. 1 of og_adj_tree over the 64 chains of one block, valid in lane 0
+__device__ __forceinline__ double hess_block_tree(double r) {
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) r = r + __shfl_down(r, s, 64);
+    return r;
+}
+
+// plan: the device plan (ogk.h).  w: the chunk's first weight vector (the next at w + M), H: row 0 of its part of the
+// result (the next at H + nnz), kc: the chunk's vectors, 1 .. HESS_CHUNK.  blockIdx.x: the heavy entries first, then four
+// units of light entries per workgroup.
+__device__ __forceinline__ void exact_hess_block(const ogk_args& a, const int* __restrict__ plan, const double* w,
+                                                 double* H, const int kc) {
+    __shared__ double chains[HESS_CHUNK][OG_ADJ_CHAINS];
+    __shared__ double part[HESS_CHUNK][HESS_WAVES];
+    const int id = (int)blockIdx.x, tid = (int)threadIdx.x, lane = tid & 63;
+    // (the same in all 64 lanes of a wavefront - said to the compiler, so that the plan and the tables stay scalar loads)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nnz = plan[0], n_light = plan[1], n_units = plan[2];
+    const int4* ent = (const int4*)(plan + OGK_HESS_HEAD);
+    const int* tptr = plan + plan[3];
+    const int* tlist = plan + plan[4];
+    const int* unit = plan + plan[5];
+    const HessTables tab;
+    if (id < nnz - n_light) {                       // the whole workgroup: every thread reaches every barrier
+        const int4 E = ent[n_light + id];
+        const int owner = E.x, partner = E.y, pos = E.z, t0 = tptr[pos], t1 = tptr[pos + 1];
+        const OgAdjCol c = og_adj_col<OgGen>(tab, owner, a.x0, a.cvec);
+#pragma unroll
+        for (int d = 0; d < HESS_CHUNK; ++d) chains[d][tid] = 0.0;
+        __syncthreads();
+        for (int base = t0; base < t1; base += HESS_THREADS) {
+            const int last = (base + HESS_THREADS < t1 ? base + HESS_THREADS : t1) - 1;
+            const int r_lo = tlist[base] >> 8, r_hi = tlist[last] >> 8;
+            const bool mine = base + tid <= last;
+            int t = 0, row = 0;
+            double e = 0.0;
+            if (mine) {
+                t = tlist[base + tid];
+                e = og_hess_term<OgGen>(tab, c, owner, partner, t, a.x0, a.y0, a.cvec, a.dfrag, &row);
+            }
+            for (int r = r_lo; r <= r_hi; ++r) {
+                if (mine && (t >> 8) == r) {
+                    const int chain = t & (OG_ADJ_CHAINS - 1);
+#pragma unroll
+                    for (int d = 0; d < HESS_CHUNK; ++d)
+                        if (d < kc) chains[d][chain] = __builtin_fma(w[(long)d * OgGen::M + row], e, chains[d][chain]);
+                }
+                __syncthreads();
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < HESS_CHUNK; ++d)
+            if (d < kc) {
+                const double r = hess_block_tree(chains[d][tid]);
+                if (lane == 0) part[d][wave] = r;
+            }
+        __syncthreads();
+        if (tid < kc) H[(long)tid * nnz + pos] = (part[tid][0] + part[tid][1]) + (part[tid][2] + part[tid][3]);
+        return;
+    }
+    const int u = (id - (nnz - n_light)) * HESS_WAVES + wave;
+    if (u >= n_units) return;                       // (the whole wavefront)
+    const int e_lo = unit[u], e_hi = unit[u + 1];
+    const int owner = ent[e_lo].x;
+    const OgAdjCol c = og_adj_col<OgGen>(tab, owner, a.x0, a.cvec);
+    // this wavefront's 256 chains: a quarter of the array (HESS_CHUNK >= HESS_WAVES), one weight vector at a time
+    double* ch = &chains[0][0] + wave * OG_ADJ_CHAINS;
+#pragma unroll 1
+    for (int en = e_lo; en < e_hi; ++en) {
+        const int4 E = ent[en];
+        const int partner = E.y, pos = E.z, t0 = tptr[pos], nt = tptr[pos + 1] - t0;
+        const bool mine = lane < nt;
+        int t = 0, row = 0, r_lo = 0, r_hi = -1;
+        double e = 0.0;
+        if (nt > 0) r_lo = tlist[t0] >> 8, r_hi = tlist[t0 + nt - 1] >> 8;
+        if (mine) {
+            t = tlist[t0 + lane];
+            e = og_hess_term<OgGen>(tab, c, owner, partner, t, a.x0, a.y0, a.cvec, a.dfrag, &row);
+        }
+        const int chain = t & (OG_ADJ_CHAINS - 1);
+        bool has[HESS_WAVES];                       // does a listed term fall into block q of the chains?
+#pragma unroll
+        for (int q = 0; q < HESS_WAVES; ++q) has[q] = __ballot(mine && (chain >> 6) == q) != 0;
+#pragma unroll 1
+        for (int d = 0; d < kc; ++d) {
+#pragma unroll
+            for (int q = 0; q < HESS_WAVES; ++q)
+                if (has[q]) ch[q * 64 + lane] = 0.0;
+            hess_wave_sync();
+            const double wr = mine ? w[(long)d * OgGen::M + row] : 0.0;
+            for (int r = r_lo; r <= r_hi; ++r) {
+                if (mine && (t >> 8) == r) ch[chain] = __builtin_fma(wr, e, ch[chain]);
+                hess_wave_sync();
+            }
+            // (p0 + p1) + (p2 + p3); a block without a listed term is +0.0 in every chain and so in its sum
+            double p[HESS_WAVES];
+#pragma unroll
+            for (int q = 0; q < HESS_WAVES; ++q) p[q] = has[q] ? hess_block_tree(ch[q * 64 + lane]) : 0.0;
+            if (lane == 0) H[(long)d * nnz + pos] = (p[0] + p[1]) + (p[2] + p[3]);
+            hess_wave_sync();
+        }
+    }
+}
+
+// blockIdx.y: the chunk of the K = nw weight vectors, read at h + d * m, written to jt + d * nnz; prow: the device plan
+__global__ __launch_bounds__(HESS_THREADS) void ogk_exact_hess(const ogk_args a, const int nw) {
+    const int* plan = (const int*)a.prow;
+    const int d0 = (int)blockIdx.y * HESS_CHUNK;
+    const int kc = nw - d0 < HESS_CHUNK ? nw - d0 : HESS_CHUNK;
+    exact_hess_block(a, plan, a.h + (long)d0 * OgGen::M, a.jt + (long)d0 * plan[0], kc);
+}
+
+// the same on a lane's record (blockIdx.z: the lane): one weight vector per lane, row `lane` of W[count][m], the result
+// in row `lane` of H[count][nnz] (the launch's own arguments, and so is the plan)
+__global__ __launch_bounds__(HESS_THREADS) void ogk_exact_hess_batch(const ogk_args* __restrict__ lanes,
+                                                                     const int* __restrict__ plan, const double* W,
+                                                                     double* H) {
+    const long lane = (long)blockIdx.z;
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_hess_block(a, plan, W + lane * OgGen::M, H + lane * plan[0], 1);
+}
+static_assert(OGK_HESS_WORKGROUPS(9, 2, 5) == 7 + (5 + HESS_WAVES - 1) / HESS_WAVES, "the runtime sizes the grid (ogk.h)");
+#endif
+
 #ifdef OGK_HAS_SWEEP
 __global__ __launch_bounds__(SWEEP_THREADS) void ogk_sweep(const ogk_args a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2478,6 +2648,18 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
 #endif
     }
 #endif
+#ifdef OGK_HAS_HESS
+    if (mode == OGK_HESS) {
+        // ncols weight vectors (gridDim.y: their chunks); uhi - ulo: the workgroups of one chunk (OGK_HESS_WORKGROUPS)
+        const int grid = args->uhi - args->ulo;
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || !args->prow || ncols < 1 || ncols > 65535 || grid < 0)
+            return (int)hipErrorInvalidValue;
+        if (grid > 0)
+            hipLaunchKernelGGL(ogk_exact_hess, dim3(grid, (ncols + HESS_CHUNK - 1) / HESS_CHUNK), dim3(HESS_THREADS), 0,
+                               stream, *args, ncols);
+        return (int)hipGetLastError();
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2603,5 +2785,49 @@ extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_
     (void)stream;
     return (int)hipErrorInvalidValue;               // a module without run-time parameters
 #endif
+}
+#endif
+
+#ifdef OGK_HAS_HESS
+// the Hessian-matrix part's batched mode, under the entry name of the batch parts as the adjoint part's is; any other mode
+// is another part's.  H: the weight vectors W[count][m], vals: the result [count][nnz], X: the device plan, nnz: the
+// workgroups of one lane (the lane records hold none of them)
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mode != OGK_BATCH_HESS) return OGK_OTHER_PART;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || !b->H || !b->vals || !b->X ||
+        b->nnz < 0 || b->nnz > 0x7fffffff)
+        return (int)hipErrorInvalidValue;
+    if (b->nnz > 0)
+        hipLaunchKernelGGL(ogk_exact_hess_batch, dim3((unsigned)b->nnz, 1, b->count), dim3(HESS_THREADS), 0, stream,
+                           (const ogk_args*)b->lanes, (const int*)b->X, b->H, b->vals);
+    return (int)hipGetLastError();
+}
+
+// terms[n]: items + the nodes of the own collocation block, as og_adj_col counts them.  The tables are device data of
+// this module only, so one thread per variable counts on the device (no plan is involved yet) and the counts come back
+// with a blocking copy
+__global__ __launch_bounds__(256) void ogk_hess_count_terms(int* __restrict__ terms) {
+    const int j = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (j >= OgGen::N_VAR) return;
+    const int4 rec = OGT_COL[j];
+    int N = 0;
+    if ((rec.w & 0x3fffffff) > rec.z)
+        for (int s = 0; s < OgGen::N_MV; ++s) {
+            const int leaf = OGT_SLOT[s].v[2], len = OGT_SLOT[s].v[0];
+            if (j >= leaf && j < leaf + len) N = len;
+        }
+    terms[j] = rec.y - rec.x + N;
+}
+
+extern "C" int ogk_hess_terms(int32_t* terms) {
+    int* d_terms = nullptr;
+    hipError_t e = hipMalloc(&d_terms, sizeof(int) * OgGen::N_VAR);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(ogk_hess_count_terms, dim3((OgGen::N_VAR + 255) / 256), dim3(256), 0, (hipStream_t)0, d_terms);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(terms, d_terms, sizeof(int) * OgGen::N_VAR, hipMemcpyDeviceToHost);
+    hipFree(d_terms);
+    return (int)e;
 }
 #endif

@@ -237,6 +237,17 @@ struct og_problem_s {
     ogk_launch_batch_fn mix_launch_batch = nullptr;
     double* d_mix = nullptr;
     size_t mix_capacity = 0;
+    // the exact sparse Hessian (og_hessian_matrix_load): the same arrangement, and the device plan (csrc/ogk.h) built
+    // from the caller's pattern and term lists; hess_nnz < 0: nothing loaded; hess_grid: workgroups of one chunk of
+    // weight vectors; d_hess: [W[k][m] | H[k][nnz]] staging of the host-pointer call, hess_capacity vectors large
+    void* hess_module = nullptr;
+    ogk_launch_fn hess_launch = nullptr;
+    ogk_launch_batch_fn hess_launch_batch = nullptr;
+    int32_t* d_hess_plan = nullptr;
+    int32_t hess_nnz = -1;
+    int32_t hess_grid = 0;
+    double* d_hess = nullptr;
+    size_t hess_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -888,6 +899,7 @@ void og_problem_destroy(og_handle p) {
     if (p->adj_module) dlclose(p->adj_module);
     if (p->hvp_module) dlclose(p->hvp_module);
     if (p->mix_module) dlclose(p->mix_module);
+    if (p->hess_module) dlclose(p->hess_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -898,6 +910,8 @@ void og_problem_destroy(og_handle p) {
     hipFree(p->d_adj);
     hipFree(p->d_hvp);
     hipFree(p->d_mix);
+    hipFree(p->d_hess_plan);
+    hipFree(p->d_hess);
     hipFree(p->d_x);
     hipFree(p->d_f0);
     hipFree(p->d_jt);
@@ -1432,6 +1446,7 @@ struct og_batch_s {
     double* d_aj = nullptr;                 // [W[capacity][m] | G[capacity][n]] staging of the host-pointer og_adjoint_batch
     double* d_hj = nullptr;                 // [W[capacity][m] | Q[capacity][n]] staging of the host-pointer og_hessian_vector_batch
     double* d_mj = nullptr;                 // [W[capacity][m] | S[capacity][n_par][n]] staging of the host-pointer og_adjoint_parameter_batch
+    double* d_hm = nullptr;                 // [W[capacity][m] | H[capacity][nnz]] staging of the host-pointer og_hessian_matrix_batch
 };
 
 namespace {
@@ -1613,6 +1628,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_aj);
     hipFree(b->d_hj);
     hipFree(b->d_mj);
+    hipFree(b->d_hm);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
     if (b->h_down) hipHostFree(b->h_down);
@@ -2437,6 +2453,215 @@ int og_hessian_vector_batch(og_batch b, int32_t count, const double* X, const do
     rc = og_hessian_vector_batch_dev(b, count, b->d_xh, d_W, b->d_xh + cap * n, b->d_f, d_Q, p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(Q, d_Q, sizeof(double) * c * n, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- the exact sparse Hessian of w . F, assembled (include/ogpsx.h) ----
+static int hessian_matrix_check(const og_problem_s* p, const char* who) {
+    if (!p->hess_launch || p->hess_nnz < 0)
+        return fail(4, std::string(who) + ": the module's Hessian-matrix part is not loaded (og_hessian_matrix_load)");
+    return 0;
+}
+
+// The caller's plan against the term counts of the module's columns -> "" or what is wrong with it
+static std::string hessian_plan_fault(int32_t n, int32_t nnz, const int32_t* indptr, const int32_t* cols, const int32_t* owner,
+                                      const int32_t* tptr, const int32_t* tlist, const std::vector<int32_t>& terms) {
+    if (indptr[0] != 0 || indptr[n] != nnz) return "indptr does not run from 0 to nnz";
+    if (tptr[0] != 0) return "tptr does not start at 0";
+    for (int32_t j = 0; j < n; ++j)
+        if (indptr[j + 1] < indptr[j] || indptr[j + 1] > nnz) return "indptr is not monotone at row " + std::to_string(j);
+    for (int32_t q = 0; q < nnz; ++q)               // (before any list is read: every list then ends inside tlist)
+        if (tptr[q + 1] < tptr[q]) return "tptr is not monotone at entry " + std::to_string(q);
+    for (int32_t j = 0; j < n; ++j)
+        for (int32_t q = indptr[j]; q < indptr[j + 1]; ++q) {
+            const std::string at = " (entry " + std::to_string(q) + ", row " + std::to_string(j) + ")";
+            const int32_t l = cols[q];
+            if (l < 0 || l > j) return "a partner outside 0 .. its row" + at;
+            if (q > indptr[j] && l <= cols[q - 1]) return "the partners of a row do not ascend" + at;
+            if (owner[q] != j && owner[q] != l) return "an owner that is neither variable of its pair" + at;
+            for (int32_t i = tptr[q]; i < tptr[q + 1]; ++i) {
+                if (tlist[i] < 0 || tlist[i] >= terms[owner[q]]) return "a term the owner's column does not have" + at;
+                if (i > tptr[q] && tlist[i] <= tlist[i - 1]) return "a term list that does not ascend" + at;
+            }
+        }
+    return "";
+}
+
+int og_hessian_matrix_load(og_handle p, const char* part_path, int32_t nnz, const int32_t* indptr, const int32_t* cols,
+                           const int32_t* owner, const int32_t* tptr, const int32_t* tlist) {
+    if (!p) return fail(1, "og_hessian_matrix_load: null handle");
+    if (p->hess_launch && p->hess_nnz >= 0) return 0;
+    if (nnz < 0 || !indptr || !cols || !owner || !tptr || !tlist)
+        return fail(1, "og_hessian_matrix_load: null plan array or negative nnz");
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, part_path, "og_hessian_matrix_load", "Hessian-matrix part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    typedef int (*ogk_hess_terms_fn)(int32_t*);
+    ogk_hess_terms_fn terms_fn = (ogk_hess_terms_fn)dlsym(mod, "ogk_hess_terms");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the Hessian-matrix part knows the mode)
+    if (!fn || !terms_fn || fn(&probe, OGK_HESS, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_hessian_matrix_load: the Hessian-matrix part does not belong to the handle's module");
+    }
+    const int32_t n = p->n;
+    std::vector<int32_t> terms((size_t)n);
+    rc = terms_fn(terms.data());
+    if (rc) {
+        dlclose(mod);
+        return fail(100 + rc, "og_hessian_matrix_load: reading the module's column tables failed");
+    }
+    const std::string fault = hessian_plan_fault(n, nnz, indptr, cols, owner, tptr, tlist, terms);
+    if (!fault.empty()) {
+        dlclose(mod);
+        return fail(1, "og_hessian_matrix_load: malformed plan: " + fault);
+    }
+    // the device plan (csrc/ogk.h): light entries grouped by owner - ascending, a stable order - in units of one owner,
+    // then the entries a workgroup sums
+    const int32_t ntl = tptr[nnz];
+    std::vector<int32_t> row_of((size_t)nnz), light, heavy;
+    for (int32_t j = 0; j < n; ++j)
+        for (int32_t q = indptr[j]; q < indptr[j + 1]; ++q) row_of[q] = j;
+    for (int32_t q = 0; q < nnz; ++q) (tptr[q + 1] - tptr[q] <= OGK_HESS_LIGHT_TERMS ? light : heavy).push_back(q);
+    std::stable_sort(light.begin(), light.end(), [&](int32_t a, int32_t b) { return owner[a] < owner[b]; });
+    std::vector<int32_t> unit;
+    for (size_t i = 0; i < light.size(); ++i)
+        if (i == 0 || owner[light[i]] != owner[light[i - 1]] || (int32_t)i - unit.back() >= OGK_HESS_UNIT_ENTRIES)
+            unit.push_back((int32_t)i);
+    const int32_t n_light = (int32_t)light.size(), n_units = (int32_t)unit.size();
+    unit.push_back(n_light);
+    const size_t off_tptr = OGK_HESS_HEAD + 4 * (size_t)nnz, off_tlist = off_tptr + (size_t)nnz + 1,
+                 off_unit = off_tlist + (size_t)ntl, total = off_unit + unit.size();
+    if (total > 0x7fffffffu) {
+        dlclose(mod);
+        return fail(1, "og_hessian_matrix_load: the plan exceeds 2^31 words");
+    }
+    std::vector<int32_t> plan(total, 0);
+    plan[0] = nnz, plan[1] = n_light, plan[2] = n_units;
+    plan[3] = (int32_t)off_tptr, plan[4] = (int32_t)off_tlist, plan[5] = (int32_t)off_unit;
+    for (int32_t e = 0; e < nnz; ++e) {
+        const int32_t q = e < n_light ? light[e] : heavy[e - n_light];
+        int32_t* rec = plan.data() + OGK_HESS_HEAD + 4 * (size_t)e;
+        rec[0] = owner[q], rec[1] = owner[q] == row_of[q] ? cols[q] : row_of[q], rec[2] = q;
+    }
+    memcpy(plan.data() + off_tptr, tptr, sizeof(int32_t) * ((size_t)nnz + 1));
+    if (ntl > 0) memcpy(plan.data() + off_tlist, tlist, sizeof(int32_t) * (size_t)ntl);
+    memcpy(plan.data() + off_unit, unit.data(), sizeof(int32_t) * unit.size());
+    int32_t* d_plan = nullptr;
+    hipError_t e = hipMalloc(&d_plan, sizeof(int32_t) * total);
+    if (e == hipSuccess) e = hipMemcpy(d_plan, plan.data(), sizeof(int32_t) * total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d_plan);
+        dlclose(mod);
+        return fail(100 + (int)e, std::string("og_hessian_matrix_load: ") + hipGetErrorString(e));
+    }
+    p->hess_module = mod;
+    p->hess_launch = fn;
+    p->hess_launch_batch = batch_fn;
+    p->d_hess_plan = d_plan;
+    p->hess_nnz = nnz;
+    p->hess_grid = OGK_HESS_WORKGROUPS(nnz, n_light, n_units);
+    return 0;
+}
+
+int32_t og_hessian_matrix_nnz(og_handle p) { return p && p->hess_launch ? p->hess_nnz : -1; }
+
+int og_hessian_matrix_dev(og_handle p, const double* d_x, int32_t k, const double* d_W, double* d_H, double* d_F0,
+                          void* hip_stream) {
+    if (!p || !d_x || !d_W || !d_H) return fail(1, "og_hessian_matrix_dev: null argument");
+    int rc = hessian_matrix_check(p, "og_hessian_matrix_dev");
+    if (!rc) rc = adjoint_count_check(k, "og_hessian_matrix_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (as og_adjoint_dev: no J_T among the arguments, the weight vectors in the step pointer and their number as a column
+    // range; the device plan in the packed-rows pointer and the grid in the unpack range, which neither launch uses)
+    fill_args(p, &a, d_x, d_W, d_F0 ? d_F0 : p->d_f0, nullptr, 0, k);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_H;
+    a.prow = p->d_hess_plan;
+    a.ulo = 0, a.uhi = p->hess_grid;
+    if (!rc) rc = p->hess_launch(&a, OGK_HESS, hip_stream);
+    return launched(rc, "og_hessian_matrix_dev");
+}
+
+int og_hessian_matrix(og_handle p, const double* x, int32_t k, const double* W, double* H, double* F0) {
+    if (!p || !x || !W || !H) return fail(1, "og_hessian_matrix: null argument");
+    int rc = hessian_matrix_check(p, "og_hessian_matrix");
+    if (!rc) rc = adjoint_count_check(k, "og_hessian_matrix");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t m = (size_t)p->m, kk = (size_t)k, nnz = (size_t)p->hess_nnz;
+    if (kk > p->hess_capacity) {
+        if (p->d_hess) OG_HIP(hipFree(p->d_hess));
+        p->d_hess = nullptr;
+        p->hess_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_hess, sizeof(double) * kk * (m + nnz)));
+        p->hess_capacity = kk;
+    }
+    double *d_W = p->d_hess, *d_H = p->d_hess + kk * m;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * kk * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_hessian_matrix_dev(p, p->d_x, k, d_W, d_H, p->d_f0, p->stream);
+    if (rc) return rc;
+    if (nnz) OG_HIP(hipMemcpyAsync(H, d_H, sizeof(double) * kk * nnz, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_hessian_matrix_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                double* d_H, void* hip_stream) {
+    int rc = batch_check(b, count, "og_hessian_matrix_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_W || !d_H) return fail(1, "og_hessian_matrix_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = hessian_matrix_check(p, "og_hessian_matrix_batch_dev");
+    if (!rc) rc = adjoint_count_check(count, "og_hessian_matrix_batch_dev");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1: its evaluation counts no launch into a lane's *jt_launches - this call writes no J_T.  The records
+    // learn X and F0 only; the weight vectors [count][m], the result [count][nnz], the device plan and the grid are
+    // arguments of the Hessian-matrix launch itself (csrc/ogk.h: OGK_BATCH_HESS)
+    rc = batch_bind(b, count, d_X, nullptr, d_F0 ? d_F0 : b->d_f, nullptr, 1, s, "og_hessian_matrix_batch_dev");
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        ogk_batch_args ba = batch_args(b, 1, count);
+        ba.X = (const double*)p->d_hess_plan;
+        ba.H = d_W, ba.vals = d_H, ba.nnz = (int64_t)p->hess_grid;
+        rc = p->hess_launch_batch(&ba, OGK_BATCH_HESS, s);
+    }
+    return launched(rc, "og_hessian_matrix_batch_dev");
+}
+
+int og_hessian_matrix_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* H) {
+    int rc = batch_check(b, count, "og_hessian_matrix_batch");
+    if (rc) return rc;
+    if (!X || !W || !H) return fail(1, "og_hessian_matrix_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = hessian_matrix_check(p, "og_hessian_matrix_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity, nnz = (size_t)p->hess_nnz;
+    if (!b->d_hm) OG_HIP(hipMalloc(&b->d_hm, sizeof(double) * cap * (m + nnz)));
+    double *d_W = b->d_hm, *d_H = b->d_hm + cap * m;
+    rc = batch_upload(b, c, X, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_hessian_matrix_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_H, p->stream);
+    if (rc) return rc;
+    if (nnz) OG_HIP(hipMemcpyAsync(H, d_H, sizeof(double) * c * nnz, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
     OG_HIP(hipStreamSynchronize(p->stream));
     return 0;

@@ -276,6 +276,61 @@ class HipEngine:
         _native.check(self._lib.og_hessian_vector_dev(self._handle, d_x, int(k), d_W, d_V, d_Q, d_F0, stream),
                       "og_hessian_vector_dev")
 
+    # ------------------------------------------------------------------ the exact sparse Hessian of w . F
+    hessian_matrix_part_path = None     # until the first Hessian-matrix call
+
+    def _hessian_plan(self):
+        """``codegen.HessianPlan`` of this program, computed by the first call that needs it."""
+        if getattr(self, "_hess_plan", None) is None:
+            self._hess_plan = codegen.HessianPlan(self.program)
+        return self._hess_plan
+
+    def _load_hessian_matrix_part(self):
+        """The module's Hessian-matrix part (``build.build_hessian_matrix_part``): compiled by the first Hessian-matrix
+        call, loaded once per handle together with the plan (``og_hessian_matrix_load``)."""
+        if self.hessian_matrix_part_path is None:
+            path = build.build_hessian_matrix_part(self.header)
+            plan = self._hessian_plan()
+            ip = C.POINTER(C.c_int32)
+            arrays = plan.arrays()
+            _native.check(self._lib.og_hessian_matrix_load(self._handle, path.encode(), plan.nnz,
+                                                           *[a.ctypes.data_as(ip) for a in arrays]),
+                          "og_hessian_matrix_load")
+            self.hessian_matrix_part_path = path
+
+    def hessian_pattern(self):
+        """``(indptr[n + 1], cols[nnz])``: the static lower-triangle pattern of the Hessian of ``w . F`` in CSR form - the
+        partners ``l <= j`` of variable ``j`` at row ``j`` (``codegen.HessianPlan``; no device work).  Every pair outside
+        it is an exact zero of the Hessian."""
+        plan = self._hessian_plan()
+        return np.array(plan.indptr, dtype=np.int32), np.array(plan.cols, dtype=np.int32)
+
+    def hessian_matrix(self, x, W):
+        """``(H, F0)``: ``H[d, p] = sum_r W[d, r] d2F_r/dx_j dx_l`` for every stored pair ``p = (j, l)`` of
+        :meth:`hessian_pattern`, ``[K, nnz]``, the EXACT Hessian of ``W[d] . F`` at ``x`` for each of the ``K`` weight
+        vectors ``W[K, m]`` (``og_hessian_matrix``: an evaluation and one launch that evaluates only the terms that can
+        be non-zero, once per chunk of 8 vectors; the order of every sum fixed - csrc/og_hess.h), and ``F0 = F(x)``.
+        An entry is bit for bit :meth:`hessian_vector` with the unit direction on one variable of the pair, read at the
+        other.  Run-time parameters are constants.  With ``devices=[...]`` the first device's handle serves it; the call
+        is not split."""
+        self._load_hessian_matrix_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if W.ndim != 2 or W.shape[1] != self.m or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, %d] with K >= 1, got %s" % (self.m, W.shape))
+        H, F0 = np.empty((W.shape[0], self._hessian_plan().nnz)), np.empty(self.m)
+        _native.check(self._lib.og_hessian_matrix(self._handle, _native.dptr(x), W.shape[0], _native.dptr(W),
+                                                  _native.dptr(H), _native.dptr(F0)), "og_hessian_matrix")
+        return H, F0
+
+    def hessian_matrix_dev(self, d_x, k, d_W, d_H, d_F0=None, stream=0):
+        """``og_hessian_matrix_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_W`` ``[k, m]``, ``d_H`` ``[k, nnz]``,
+        ``d_F0`` ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_hessian_matrix_part()
+        _native.check(self._lib.og_hessian_matrix_dev(self._handle, d_x, int(k), d_W, d_H, d_F0, stream),
+                      "og_hessian_matrix_dev")
+
     # ------------------------------------------------------------------ exact d(F'(x)^T w)/dtheta
     def _load_mix_part(self):
         """The module's mixed part (``build.build_mix_part``): compiled by the first mixed-derivative call, loaded once
@@ -703,6 +758,34 @@ class BatchSweep:
         self.engine._load_hessian_part()
         _native.check(self._lib.og_hessian_vector_batch_dev(self._handle, int(count), d_X, d_W, d_V, d_F0, d_Q, stream),
                       "og_hessian_vector_batch_dev")
+
+    def hessian_matrix(self, X, W, count=None):
+        """``(H[B, nnz], F0[B, m])``: lane ``k``'s exact sparse Hessian of ``W[k] . F`` at ``X[k]`` in the order of
+        :meth:`HipEngine.hessian_pattern` - one weight vector (``m`` entries) per lane, at the lane's own parameters
+        (:meth:`set_parameters`) - bit for bit :meth:`HipEngine.hessian_matrix` at that point, vector and those values
+        (``og_hessian_matrix_batch``; three launches whatever ``B`` is).  ``count``: only the first ``count`` rows
+        (default: all).  No lane's J_T is written."""
+        X = self._points(X, "X")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.m:
+            raise ValueError("BatchSweep: W must have shape [B, %d], got %s" % (self.m, W.shape))
+        if W.shape[0] != X.shape[0]:
+            raise ValueError("BatchSweep: %d weight vectors for %d points" % (W.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_hessian_matrix_part()
+        H, F0 = np.empty((B, self.engine._hessian_plan().nnz)), np.empty((B, self.m))
+        _native.check(self._lib.og_hessian_matrix_batch(self._handle, B, _native.dptr(X), _native.dptr(W), _native.dptr(F0),
+                                                        _native.dptr(H)), "og_hessian_matrix_batch")
+        return H, F0
+
+    def hessian_matrix_dev(self, count, d_X, d_W, d_H, d_F0=None, stream=0):
+        """``og_hessian_matrix_batch_dev``: ``d_X`` ``[count, n]``, ``d_W`` ``[count, m]``, ``d_H`` ``[count, nnz]``,
+        ``d_F0`` ``[count, m]`` or None."""
+        self.engine._load_hessian_matrix_part()
+        _native.check(self._lib.og_hessian_matrix_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_H, stream),
+                      "og_hessian_matrix_batch_dev")
 
     def adjoint_parameter(self, X, W, count=None):
         """``(S[B, n_par, n], F0[B, m])``: lane ``k``'s exact ``d(F'(X[k])^T W[k])/dtheta`` - one weight vector (``m``

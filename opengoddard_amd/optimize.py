@@ -50,6 +50,38 @@ def _noop():
     pass
 
 
+class SparseHessian:
+    """What :meth:`Problem.hessian_matrix` returns: ``values`` (``[K, nnz]``, or ``[nnz]`` for one weight vector) are the
+    stored entries of the lower triangle in CSR form, ``cols[indptr[j]:indptr[j + 1]]`` the partners ``l <= j`` of
+    variable ``j``."""
+
+    def __init__(self, values, indptr, cols):
+        self.values, self.indptr, self.cols = values, np.asarray(indptr), np.asarray(cols)
+        self.n = self.indptr.size - 1
+
+    def _row(self, d):
+        return self.values if self.values.ndim == 1 else self.values[d]
+
+    def tocsr(self, d=0, symmetric=True):
+        """Weight vector ``d``'s Hessian as a ``scipy.sparse.csr_matrix``: the lower triangle mirrored
+        (``symmetric=True``, the default) or as stored."""
+        import scipy.sparse as sp
+        vals = self._row(d)
+        lower = sp.csr_matrix((vals, self.cols, self.indptr), shape=(self.n, self.n))
+        if not symmetric:
+            return lower
+        rows = np.repeat(np.arange(self.n), np.diff(self.indptr))
+        off = rows != self.cols
+        return (lower + sp.csr_matrix((vals[off], (self.cols[off], rows[off])), shape=(self.n, self.n))).tocsr()
+
+    def toarray(self, d=0):
+        """Weight vector ``d``'s Hessian as a dense symmetric ``[n, n]`` array."""
+        rows = np.repeat(np.arange(self.n), np.diff(self.indptr))
+        out = np.zeros((self.n, self.n))
+        out[rows, self.cols] = out[self.cols, rows] = self._row(d)
+        return out
+
+
 class BatchResult:
     """What :meth:`Problem.evaluate_batch` returns for ``B`` points: ``cost[B]``, ``equality[B, m_eq]``,
     ``inequality[B, m_ineq]`` and ``violation[B]`` - SLSQP's measure of infeasibility, ``sum |c_eq| +
@@ -78,6 +110,8 @@ class BatchResult:
         self.adjoint = None             # [B, n]: exact F'(x_k)^T w_k (evaluate_batch(adjoints=W))
         self.hessian_product = None     # [B, n]: exact grad^2 (w_k . F)(x_k) v_k (evaluate_batch(hessian_products=(W, V)))
         self.adjoint_parameter = None   # [B, n_par, n]: exact d(F'(x_k)^T w_k)/dtheta (evaluate_batch(adjoint_parameter=W))
+        self.hessian = None             # [B, nnz]: exact sparse Hessian of w_k . F at x_k (evaluate_batch(hessians=W))
+        self.hessian_pattern = None     # (indptr, cols) of it: the lower triangle in CSR form
 
     def __len__(self):
         return self.cost.shape[0]
@@ -771,6 +805,44 @@ class Problem:
                      copy=True)
         return Q[0] if single else Q
 
+    def hessian_pattern(self, obj):
+        """``(indptr, cols)``: the static lower-triangle pattern of the Hessian of ``w . F`` in CSR form - the partners
+        ``l <= j`` of variable ``j`` at row ``j`` - from the traced callbacks (no GPU work).  Every pair outside it is an
+        exact zero of the Hessian, whatever the weights and the point."""
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "hessian_pattern"):
+            raise ValueError("this engine has no exact sparse Hessian (it has no hessian_pattern)")
+        return engine.hessian_pattern()
+
+    def hessian_matrix(self, obj, weights):
+        """The Hessian ``sum_r w_r grad^2 F_r`` of ``F = [cost | c_eq | c_ineq]`` at ``prob.p`` and the current
+        parameter values as a SPARSE matrix, EXACT (``HipEngine.hessian_matrix``: an evaluation and one launch that
+        evaluates only the second derivatives that can be non-zero, once for up to 8 weight vectors; second-order dual
+        numbers, no step).  ``weights``: ``[K, m]`` over the rows of ``F``, or one ``[m]``; with ``w = [1, lambda]`` it is
+        the Hessian of the Lagrangian - a sparse-direct Newton or interior-point step, the (1, 1) block of the KKT
+        matrix next to :meth:`adjoint_product` / :meth:`directional_derivative`, a reduced-Hessian check, the truth a
+        quasi-Newton factor is compared with.  Returns a :class:`SparseHessian`: ``values`` (``[K, nnz]``, or ``[nnz]``
+        for one vector) in the order of ``indptr`` / ``cols`` (the lower triangle in CSR form, :meth:`hessian_pattern`),
+        ``tocsr(d=0, symmetric=True)`` and ``toarray(d=0)``.  Every stored entry is bit for bit
+        :meth:`hessian_vector_product` with a unit direction; run-time parameters are constants.  An engine without
+        ``hessian_matrix`` and a weight vector of the wrong length are ``ValueError``s."""
+        W = np.asarray(weights, dtype=float)
+        single = W.ndim == 1
+        if single:
+            W = W[None, :]
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, m] or [m], got shape %s" % (np.shape(weights),))
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "hessian_matrix") or not hasattr(engine, "hessian_pattern"):
+            raise ValueError("this engine has no exact sparse Hessian (it has no hessian_matrix / hessian_pattern)")
+        point = np.asarray(self.p, dtype=float).reshape(-1)
+        m = self._rows_of(engine, point)
+        if W.shape[1] != m:
+            raise ValueError("weights must have %d entries (the rows of F) each, got shape %s" % (m, np.shape(weights)))
+        H = np.array(engine.hessian_matrix(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
+        indptr, cols = engine.hessian_pattern()
+        return SparseHessian(H[0] if single else H, indptr, cols)
+
     def adjoint_parameter_sensitivity(self, obj, weights, p=None):
         """``d(F'(p)^T w)/dtheta``, ``s_{k,j} = sum_r w_r d2F_r/dx_j dtheta_k``, of ``F = [cost | c_eq | c_ineq]`` for every
         declared run-time parameter at the decision vector ``p`` (default ``prob.p``) and the current parameter values,
@@ -803,7 +875,7 @@ class Problem:
 
     # ------------------------------------------------------------------ many points at once
     def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None,
-                       adjoints=None, hessian_products=None, adjoint_parameter=None):
+                       adjoints=None, hessian_products=None, adjoint_parameter=None, hessians=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -862,7 +934,16 @@ class Problem:
         its own row of ``parameters`` is differentiated at those values; one point scanned over ``parameters`` takes
         its one vector along.  It combines with every other keyword; a problem without parameters is a ``ValueError``.
         ``None``: nothing is computed and the call builds, loads and launches exactly what it does without the
-        keyword."""
+        keyword.
+
+        ``hessians=W`` (``[B, m]``, one weight vector over the rows of ``F`` per row of ``points``) adds
+        ``BatchResult.hessian``, ``[B, nnz]``, and ``BatchResult.hessian_pattern``: the EXACT sparse Hessian of
+        ``w_k . F`` at every point with its own vector, the stored entries of :meth:`hessian_pattern` in its order
+        (``BatchSweep.hessian_matrix``; a stand-in engine is served point by point through its ``hessian_matrix`` and
+        ``hessian_pattern``, without them: ``ValueError``).  A point with its own row of ``parameters`` is
+        differentiated at those values; one point scanned over ``parameters`` takes its one vector along.  It combines
+        with every other keyword.  ``None``: nothing is computed and the call builds, loads and launches exactly what it
+        does without the keyword."""
         if (parameter_jacobian or adjoint_parameter is not None) and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
@@ -886,6 +967,13 @@ class Problem:
                 raise ValueError("adjoint_parameter must have shape [B, m] (the rows of F), got %s" % (mix_w.shape,))
             if points.ndim == 2 and mix_w.shape[0] != points.shape[0]:
                 raise ValueError("adjoint_parameter holds %d rows for %d points" % (mix_w.shape[0], points.shape[0]))
+        full_w = None
+        if hessians is not None:
+            full_w = np.asarray(hessians, dtype=float)
+            if full_w.ndim != 2:
+                raise ValueError("hessians must have shape [B, m] (the rows of F), got %s" % (full_w.shape,))
+            if points.ndim == 2 and full_w.shape[0] != points.shape[0]:
+                raise ValueError("hessians holds %d rows for %d points" % (full_w.shape[0], points.shape[0]))
         hess_w = hess_v = None
         if hessian_products is not None:
             if not isinstance(hessian_products, (tuple, list)) or len(hessian_products) != 2:
@@ -923,6 +1011,8 @@ class Problem:
                 hess_w, hess_v = np.repeat(hess_w, TH.shape[0], axis=0), np.repeat(hess_v, TH.shape[0], axis=0)
             if mix_w is not None:
                 mix_w = np.repeat(mix_w, TH.shape[0], axis=0)
+            if full_w is not None:
+                full_w = np.repeat(full_w, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
         if directions is not None:
             directions = np.ascontiguousarray(directions)
@@ -949,6 +1039,13 @@ class Problem:
             m_rows = self._rows_of(engine, points[0])
             if mix_w.shape[1] != m_rows:
                 raise ValueError("adjoint_parameter must have shape [B, %d] (the rows of F), got %s" % (m_rows, mix_w.shape))
+        if full_w is not None:
+            if not hasattr(engine, "hessian_matrix") or not hasattr(engine, "hessian_pattern"):
+                raise ValueError("this engine has no exact sparse Hessian (it has no hessian_matrix / hessian_pattern)")
+            full_w = np.ascontiguousarray(full_w)
+            m_rows = self._rows_of(engine, points[0])
+            if full_w.shape[1] != m_rows:
+                raise ValueError("hessians must have shape [B, %d] (the rows of F), got %s" % (m_rows, full_w.shape))
         used = TH if TH is not None else np.tile(np.asarray(self._par_values, dtype=float), (B, 1))
         lb = np.array([-np.inf if b[0] is None else b[0] for b in self.bounds], dtype=float)
         ub = np.array([np.inf if b[1] is None else b[1] for b in self.bounds], dtype=float)
@@ -969,8 +1066,11 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = along = back = curv = mixed = None
+            par_jac = along = back = curv = mixed = full = None
             try:
+                if full_w is not None:
+                    full = np.stack([np.array(engine.hessian_matrix(p, full_w[k:k + 1])[0], dtype=float).reshape(-1)
+                                     for k, p in enumerate(lanes())])
                 if parameter_jacobian:
                     par_jac = np.stack([np.array(engine.parameter_jacobian(p)[0], dtype=float, copy=True) for p in lanes()])
                 if directions is not None:
@@ -992,6 +1092,8 @@ class Problem:
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
                     res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
                     res.hessian_product, res.adjoint_parameter = curv, mixed
+                    if full is not None:
+                        res.hessian, res.hessian_pattern = full, engine.hessian_pattern()
                     return res
                 rows, dense, steps = [], [], []
                 if jacobian == "exact":
@@ -1014,6 +1116,8 @@ class Problem:
             res = BatchResult(np.stack(rows), m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
             res.hessian_product, res.adjoint_parameter = curv, mixed
+            if full is not None:
+                res.hessian, res.hessian_pattern = full, engine.hessian_pattern()
             m = rows[0].size
             # a stand-in knows no pattern: every entry of the dense matrix is one
             res.pattern = (np.arange(n + 1, dtype=np.int64) * m, np.tile(np.arange(m, dtype=np.int32), n))
@@ -1056,10 +1160,16 @@ class Problem:
             if not hasattr(batch, "adjoint_parameter"):
                 raise ValueError("this engine has no exact mixed derivative (its batch has no adjoint_parameter)")
             mixed = batch.adjoint_parameter(points, mix_w)[0]
+        full = full_pattern = None
+        if full_w is not None:
+            if not hasattr(batch, "hessian_matrix"):
+                raise ValueError("this engine has no exact sparse Hessian (its batch has no hessian_matrix)")
+            full, full_pattern = batch.hessian_matrix(points, full_w)[0], engine.hessian_pattern()
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
             res.hessian_product, res.adjoint_parameter = curv, mixed
+            res.hessian, res.hessian_pattern = full, full_pattern
             return res
         if jacobian == "exact":
             F0, vals, nonfinite = batch.exact(points)
@@ -1069,6 +1179,7 @@ class Problem:
         res = BatchResult(F0, engine.m_eq)
         res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
         res.hessian_product, res.adjoint_parameter = curv, mixed
+        res.hessian, res.hessian_pattern = full, full_pattern
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
         # column 0 of J_T: the pattern entries whose row is the cost
