@@ -16,10 +16,16 @@
 //       depend on the seeded variables therefore keeps dd = 0 through sqrt(0), log(0), asin(1), 0/0-type quotients and
 //       x^y at x = 0 instead of producing 0 * inf.  (Rule (a) binds d1 and d2 to og_dual.h's expressions, guarded or
 //       not; (b) is about dd.)  Where og_dual.h takes the slope as 0 (sqrt, cbrt and hypot at 0), dd is 0 as well.
+//       The kernels seed a leaf as (x_i, i == j, v_i, 0), so almost every intermediate has some seeds zero and others
+//       not: with one whole slot zero and both dd zero, dd stays exactly 0 whatever the value is.  The one exception is
+//       double / ogdual2 at a divisor where og_dual.h's unguarded slope -(q b.d) / b.v is itself not finite.
 // Piecewise-linear operations (fabs_, the generated ternaries for max / min, mod_, fmod_, interp_linear) take their
 // branch from v and have no curvature of their own: dd is the first-order rule applied to dd.
+// A coefficient that is exactly zero is left out like a zero seed where it would meet an infinity (pow_: y (y - 1) at
+// y = 1, x = 0), and no mixed part is formed as a difference of nearly equal numbers (hypot_).
 //
-// Same source for hipcc and a host compiler.
+// Same source for hipcc and a host compiler: tests/test_dual2_gpu.py holds the device to the host's bits for every rule,
+// form and seed pattern; tests/test_dual2_seeds.py holds the host to closed-form derivatives.
 #ifndef OG_DUAL2_H
 #define OG_DUAL2_H
 
@@ -202,7 +208,9 @@ OG_HDI ogdual2 cbrt_(const ogdual2 a) {
     return ogdual2(c, a.d1 == 0.0 ? 0.0 : a.d1 / g, a.d2 == 0.0 ? 0.0 : a.d2 / g,
                    og2_mixed(a, -2.0 / (3.0 * g * a.v), a.dd / g));
 }
-// h = hypot(x, y): h^2 = x^2 + y^2 differentiated twice gives h h.dd = x.d1 x.d2 + y.d1 y.d2 + x x.dd + y y.dd - h.d1 h.d2
+// h = hypot(x, y), cx = x / h, cy = y / h: h.dd = (x.d1 x.d2 + y.d1 y.d2 - h.d1 h.d2) / h + cx x.dd + cy y.dd, and by
+// Lagrange's identity the bracket is t1 t2 with t = cx y.d - cy x.d along each seed: a product, not the difference of two
+// numbers that agree to (y/x)^2 where one argument is constant or dominant (hypot(x, 1e-8), the smoothed |x|).
 OG_HDI ogdual2 hypot_(const ogdual2 x, const ogdual2 y) {
     const double h = hypot_(x.v, y.v);
     if (h == 0.0) return ogdual2(h, 0.0, 0.0, 0.0);
@@ -211,9 +219,10 @@ OG_HDI ogdual2 hypot_(const ogdual2 x, const ogdual2 y) {
     const bool first = (x.d1 != 0.0 || y.d1 != 0.0) && (x.d2 != 0.0 || y.d2 != 0.0);
     double dd = 0.0;
     if (first || x.dd != 0.0 || y.dd != 0.0) {
-        const double cross = og2_term(x.d1, x.d2, 1.0) + og2_term(y.d1, y.d2, 1.0);
-        const double lin = og2_term(x.dd, x.v) + og2_term(y.dd, y.v);
-        dd = ((cross + lin) - og2_term(d1, d2, 1.0)) / h;
+        const double cx = x.v / h, cy = y.v / h;
+        const double t1 = og2_term(y.d1, cx) - og2_term(x.d1, cy), t2 = og2_term(y.d2, cx) - og2_term(x.d2, cy);
+        const double lin = og2_term(x.dd, cx) + og2_term(y.dd, cy);
+        dd = (first ? t1 * t2 / h : 0.0) + lin;
     }
     return ogdual2(h, d1, d2, dd);
 }
@@ -240,7 +249,8 @@ OG_HDI ogdual2 fmod_(const double a, const ogdual2 b) { return fmod_(ogdual2(a),
 //   x.d1 x.d2  y (y - 1) x^(y-2)              y A x.dd
 //   x.d1 y.d2  (A + y A L)                    p L y.dd
 //   y.d1 x.d2  A      and   y.d1 L times the first-order part along 2 (y A x.d2 + p L y.d2)
-// each left out when its seeds are zero; the parts with log x stay out where p is 0, as in og_dual.h.
+// each left out when its seeds are zero; the parts with log x stay out where p is 0, as in og_dual.h, and the curvature
+// term where y (y - 1) is exactly 0: x ** 1 is x, also at x = 0 where x^(y-2) is infinite.
 OG_HDI ogdual2 pow_(const ogdual2 x, const ogdual2 y) {
     const double p = pow_(x.v, y.v);
     const bool xs = x.d1 != 0.0 || x.d2 != 0.0 || x.dd != 0.0, ys = (y.d1 != 0.0 || y.d2 != 0.0 || y.dd != 0.0) && p != 0.0;
@@ -250,7 +260,8 @@ OG_HDI ogdual2 pow_(const ogdual2 x, const ogdual2 y) {
     if (y.d1 != 0.0 && p != 0.0) d1 += p * L * y.d1;
     if (x.d2 != 0.0) d2 += y.v * A * x.d2;
     if (y.d2 != 0.0 && p != 0.0) d2 += p * L * y.d2;
-    if (x.d1 != 0.0 && x.d2 != 0.0) dd += y.v * (y.v - 1.0) * pow_(x.v, y.v - 2.0) * x.d1 * x.d2;
+    const double curv = y.v * (y.v - 1.0);
+    if (x.d1 != 0.0 && x.d2 != 0.0 && curv != 0.0) dd += curv * pow_(x.v, y.v - 2.0) * x.d1 * x.d2;
     if (x.dd != 0.0) dd += y.v * A * x.dd;
     if (p != 0.0) {
         if (x.d1 != 0.0 && y.d2 != 0.0) dd += (A + y.v * A * L) * x.d1 * y.d2;
