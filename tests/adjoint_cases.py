@@ -4,7 +4,7 @@ GPU cases' modules, batch parts and adjoint parts ahead of the GPU run): weight 
 ``directional_cases`` (``dc.case``), the probe's flags ``parameter_exact_cases.PROBE_FLAGS``.
 
 What the GPU shapes cover (``COVERAGE`` below, checked on the CPU by tests/test_adjoint.py against the term counts and
-``reads`` words the probe reports; a term is one entry of a column of the exact Jacobian).  The four shapes of the
+``reads`` words the probe reports; a term is one entry of a column of the exact Jacobian).  The six shapes of the
 directional GPU test have no column with more than 256 terms - nor has any surface problem - so ``B90``, the
 brachistochrone on 90 nodes, joins them:
 
@@ -16,9 +16,11 @@ brachistochrone on 90 nodes, joins them:
   the control columns of ``B90``;
 * no term at all: the variables 195 .. 324 of ``layout_8``, which no callback of that random layout reads;
 * a collocation slot's ``reads`` word (bit 0: the dynamics term at node k reads the state at node k, bit 1: it reads the
-  state's slice in some other way) takes the values 0 and 1 on the surface problems and the parameterised ones, never 2
-  or 3: 1 on all five shapes, 0 on ``B5``, ``B90`` and ``layout_8``; a column that is no node of a collocated state
-  (controls, final times; -1 here) on all of them.
+  state's slice in some other way, and then every entry of the column's own block has a dynamics part) takes the values
+  0 and 1 on the surface problems and the parameterised ones: 1 on all five of their shapes, 0 on ``B5``, ``B90`` and
+  ``layout_8``.  ``NL2`` and ``NL0`` of ``nonlocal_cases`` bring the other two: 2 on ``NL2`` (``np.sum(x * x)`` and
+  nothing else of ``x`` in its own row), 3 on ``NL0`` (``cos(x - x[0])``; ``v[0]`` next to ``v``).  A column that is no
+  node of a collocated state (controls, final times; -1 here) is on all of them.
 """
 import os
 import subprocess
@@ -160,6 +162,8 @@ COVERAGE = {
     "layout_8": (0, 130, {-1, 0, 1}),
     "P2U": (0, 0, {-1, 1}),
     "B90": (1, 0, {-1, 0, 1}),
+    "NL2": (0, 0, {-1, 1, 2}),
+    "NL0": (0, 0, {-1, 3}),
 }
 
 

@@ -5,7 +5,9 @@ references of ``F'(x) v`` and the host probe of ``csrc/og_dir.h``.
 Cases: ``brachistochrone``; ``table_ascent`` (``interp1d``); the edge problems ``ragged_two_phase`` and
 ``wide_functions`` and the random layouts 5 and 8 of tests/test_exact_surface.py (their own four named points); the
 parameterised ``P2U`` and ``G17`` of tests/parameter_exact_cases.py (imported: their own points and parameter sets);
-``B5``, the brachistochrone on 5 nodes.  Every case adds seeded 2 % perturbations of its first point.
+``B5``, the brachistochrone on 5 nodes.  Every case adds seeded 2 % perturbations of its first point.  ``NL2`` and ``NL0``
+are built by ``nonlocal_cases`` (dynamics that read a state across the nodes of its phase: bit 1 of a slot's ``reads``
+word, which no other case here sets), with its own three points.
 """
 import os
 import subprocess
@@ -23,11 +25,13 @@ BOUND = surface.BOUND           # 1e-12, of max(1, sum_j |J_rj v_j|) per row
 
 SURFACE_KEYS = ("brachistochrone", "table_ascent", "ragged_two_phase", "wide_functions", "layout_5", "layout_8")
 PARAMETER_KEYS = ("P2U", "G17")
-CPU_KEYS = SURFACE_KEYS + PARAMETER_KEYS
+NONLOCAL_KEYS = ("NL2", "NL0")
+CPU_KEYS = SURFACE_KEYS + PARAMETER_KEYS + NONLOCAL_KEYS
 # the GPU test's shapes: 5 nodes (N no multiple of 4, one partly filled workgroup); 17 nodes (across the 16-row block of
 # the operand image); two phases of 65 and 31 nodes (DFRAG_OFF, 423 entries: blockIdx.x = 1 with a ragged workgroup);
-# a parameterised module
-GPU_KEYS = ("B5", "G17", "layout_8", "P2U")
+# a parameterised module; two phases of 21 and 6 nodes whose own collocation blocks are full (a sum of squares over the
+# state's slice; its first and last value)
+GPU_KEYS = ("B5", "G17", "layout_8", "P2U") + NONLOCAL_KEYS
 
 
 class Case:
@@ -90,7 +94,11 @@ _CASES = {}
 
 def case(key):
     if key not in _CASES:
-        _CASES[key] = Case(key)
+        if key in NONLOCAL_KEYS:
+            import nonlocal_cases               # (it imports this module for ``Case``)
+            _CASES[key] = nonlocal_cases.case(key)
+        else:
+            _CASES[key] = Case(key)
     return _CASES[key]
 
 

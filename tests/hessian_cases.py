@@ -2,10 +2,12 @@
 GPU cases' modules, batch parts and Hessian parts ahead of the GPU run): the rules of ``csrc/og_dual2.h`` against mpmath,
 the pairs ``(w, v)``, the host probe of ``csrc/og_hvp.h`` and its independent reference.
 
-Shapes, points and parameter sets are those of ``adjoint_cases.GPU_KEYS`` (``B5``, ``G17``, ``layout_8``, ``P2U``,
-``B90``), the weights ``adjoint_cases.weights`` and the directions ``directional_cases``' (``Case.directions``).  What the
-five contain (checked by tests/test_hessian.py from the probe's structure report): a column of more than 256 terms and a
-column the tracer marks heavy (the final time of ``B90``, both), columns with no term (``layout_8``), light columns (all).
+Shapes, points and parameter sets are those of ``adjoint_cases.GPU_KEYS`` (``B5``, ``G17``, ``layout_8``, ``P2U``, ``NL2``,
+``NL0``, ``B90``), the weights ``adjoint_cases.weights`` and the directions ``directional_cases``' (``Case.directions``).
+What the seven contain (checked by tests/test_hessian.py from the probe's structure report): a column of more than 256
+terms and a column the tracer marks heavy (the final time of ``B90``, both), columns with no term (``layout_8``), light
+columns (all), every value of a slot's ``reads`` word (2 and 3 on ``NL2`` and ``NL0`` of ``nonlocal_cases``: curvature in
+every entry of a state's own block).
 """
 import os
 import subprocess

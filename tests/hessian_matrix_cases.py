@@ -2,8 +2,8 @@
 compiles the GPU cases' modules, batch parts, Hessian parts and Hessian-matrix parts ahead of the GPU run): the plan
 (``codegen.HessianPlan``) of every shape and the host probe of ``csrc/og_hess.h``.
 
-Shapes, points and parameter sets are those of ``hessian_cases.GPU_KEYS`` (``B5``, ``G17``, ``layout_8``, ``P2U``,
-``B90``), the weights ``adjoint_cases.weights``.  The reference of the bit-for-bit tests is the existing probe of
+Shapes, points and parameter sets are those of ``hessian_cases.GPU_KEYS`` (``B5``, ``G17``, ``layout_8``, ``P2U``, ``NL2``,
+``NL0``, ``B90``), the weights ``adjoint_cases.weights``.  The reference of the bit-for-bit tests is the existing probe of
 ``csrc/og_hvp.h`` (``hessian_cases.run_probe``) with the ``n`` unit directions.
 """
 import os

@@ -7,8 +7,10 @@ collocation operand reads it: the operand term of a column's own block is not ze
 ``P2``, ``G9`` / ``G17`` (``n`` no multiple of 4: the last workgroup of the wavefront mapping is partly filled), ``E``
 (every operator applied to a parameter, parameter values on every switch) - and ``B90g``: the 90-node brachistochrone of
 ``adjoint_cases.ManyTerms`` with the gravity declared a parameter, the only shape whose heavy column (the final time, 272
-terms: a thread's second trip through its chain, the workgroup path) reads a parameter.  These are the smallest shapes at
-which each path of the kernel runs.
+terms: a thread's second trip through its chain, the workgroup path) reads a parameter - and ``NLP`` of
+``nonlocal_cases``: ``dx[0] = v - a * (x - x.mean())`` sets bit 1 of the ``reads`` word of ``x``, so the term
+``d2 tail_k / dx_l da`` of og_mix.h is not zero off the diagonal of that state's own block (the only case where it is
+not), at both of its parameter sets.  These are the smallest shapes at which each path of the kernel runs.
 """
 import os
 import subprocess
@@ -23,7 +25,7 @@ from oracle import exact_jac
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_SOURCE = os.path.join(ROOT, "tests", "mix_probe.cpp")
-KEYS = ("P2U", "P2", "G9", "G17", "E", "B90g")
+KEYS = ("P2U", "P2", "G9", "G17", "E", "B90g", "NLP")
 B90G_THETA = (np.array([1.0]), np.array([0.8125]), np.array([1.375]))
 
 
@@ -44,7 +46,11 @@ class Case:
             self.points = [base * (1.0 + 0.02 * rng.standard_normal(base.size)) + 0.01 * rng.random(base.size)
                            for _ in range(2)]
         else:
-            C = ec.case(key)
+            if key == "NLP":
+                import nonlocal_cases
+                C = nonlocal_cases.case(key)
+            else:
+                C = ec.case(key)
             self.prob, self.obj, self.program, self.header = C.prob, C.obj, C.program, C.header
             self.names, self.thetas, self.points = tuple(C.names), list(C.thetas), list(C.points)
         self.n, self.m, self.n_par = self.program.n, self.program.m, self.program.n_par

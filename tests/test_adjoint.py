@@ -175,15 +175,21 @@ def test_the_gpu_shapes_cover_what_the_cases_file_states(key, probe_dir):
         assert np.array_equal(F0, F0t) and ac.worst_error(G, prod, scale) <= ac.BOUND
 
 
-def test_the_surface_problems_produce_no_other_reads_word(probe_dir):
-    seen = set()
+def test_the_reads_words_of_the_surface_problems_and_of_all_shapes(probe_dir):
+    """The surface problems and the parameterised ones produce 0 and 1 only; the shapes of ``nonlocal_cases`` bring 2 and
+    3, so the GPU shapes between them hold every value of the word."""
+    seen = {}
     for key in ac.CPU_KEYS:
         C = ac.case(key)
         exe = ac.build_probe(C, probe_dir, "g++")
         reads = ac.run_probe(C, exe, probe_dir, C.points[0], ac.weights(C)[:1], C.thetas[0], structure=True)[3]
-        seen |= set(int(r) for r in reads)
+        seen[key] = set(int(r) for r in reads)
+    assert set(dc.NONLOCAL_KEYS) == {"NL2", "NL0"} and set(dc.NONLOCAL_KEYS) <= set(ac.CPU_KEYS)
+    surface_keys = dc.SURFACE_KEYS + dc.PARAMETER_KEYS
+    assert set().union(*(seen[key] for key in surface_keys)) == {-1, 0, 1}
+    assert seen["NL2"] == ac.COVERAGE["NL2"][2] == {-1, 1, 2} and seen["NL0"] == ac.COVERAGE["NL0"][2] == {-1, 3}
     covered = set().union(*(c[2] for c in ac.COVERAGE.values()))
-    assert seen == {-1, 0, 1} and seen <= covered
+    assert covered == {-1, 0, 1, 2, 3} and set().union(*seen.values()) == covered
 
 
 # ------------------------------------------------------------------------------------------------ 2. host logic

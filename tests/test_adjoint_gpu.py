@@ -5,7 +5,8 @@ own distance from the twin's ``J^T w`` tests/test_adjoint.py bounds.  Shapes (``
 batch parts and adjoint parts are compiled by ``__graft_entry__.build``): B5 - 5 nodes, every workgroup mostly idle
 lanes; G17 - 17 nodes cross the 16-row block of the operand image, parameterised; layout_8 - phases of 65 and 31 nodes,
 a second phase's panel offset, 130 variables without a term; P2U - a parameterised module; B90 - 90 nodes, the final
-time's 272 terms take a thread through its chain twice.  What each shape covers is stated in ``adjoint_cases`` and
+time's 272 terms take a thread through its chain twice; NL2, NL0 - a slot's ``reads`` word at 2 and 3 (every entry of a
+state's own block has a dynamics part).  What each shape covers is stated in ``adjoint_cases`` and
 checked on the CPU."""
 
 import numpy as np

@@ -5,7 +5,8 @@ every entry with ``og_dir_entry`` (csrc/og_dir.h), so every comparison is BITWIS
 tests/test_directional.py bounds.  Shapes (``directional_cases.GPU_KEYS``; their modules, batch parts and directional
 parts are compiled by ``__graft_entry__.build``): B5 - one phase of 5 nodes, N no multiple of 4, one partly filled
 workgroup; G17 - 17 nodes cross the 16-row block of the operand image; layout_8 - phases of 65 and 31 nodes, a second
-phase's panel offset, 423 entries: a second workgroup, ragged; P2U - a parameterised module."""
+phase's panel offset, 423 entries: a second workgroup, ragged; P2U - a parameterised module; NL2, NL0 - dynamics that
+read a state across the nodes of its phase (``nonlocal_cases``)."""
 
 import numpy as np
 import pytest

@@ -140,10 +140,16 @@ def test_first_order_parts_are_the_adjoint_probes_bits(key, probe_dir):
 
 
 def test_the_shapes_cover_every_path_of_the_kernel(probe_dir):
-    terms, heavy = {}, {}
+    terms, heavy, reads = {}, {}, {}
     for key in hc.GPU_KEYS:
         r = _probed(key, probe_dir)[6]
-        terms[key], heavy[key] = r.terms, r.heavy
+        terms[key], heavy[key], reads[key] = r.terms, r.heavy, set(int(v) for v in r.reads)
+    assert len(hc.GPU_KEYS) == 7
+    # every value of a slot's `reads` word: bit 1 (og_hvp.h: the second-order part of every entry of the own block, not
+    # of the diagonal alone) on NL2 without bit 0 and on NL0 with it
+    assert reads["NL2"] == {-1, 1, 2} and reads["NL0"] == {-1, 3}
+    assert set().union(*reads.values()) == {-1, 0, 1, 2, 3}
+    assert all(2 not in v and 3 not in v for key, v in reads.items() if key not in ("NL2", "NL0"))
     assert any((t > 256).any() for t in terms.values())             # a thread's second trip through its chain
     assert any((t == 0).any() for t in terms.values())              # a column with no term
     assert all(((t > 0) & (t < 64) & (h == 0)).any() for t, h in zip(terms.values(), heavy.values()))   # light columns

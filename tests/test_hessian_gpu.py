@@ -2,7 +2,7 @@
 ``BatchSweep.hessian_vector``, ``Problem.hessian_vector_product``, ``evaluate_batch(hessian_products=)``).  The kernels sum
 the terms of ``csrc/og_hvp.h`` in the order ``csrc/og_adj.h`` fixes, so every comparison is BITWISE against the host probe
 of those headers (tests/hvp_probe.cpp, g++), whose own distance from an independent reference tests/test_hessian.py
-bounds.  Shapes (``hessian_cases.GPU_KEYS``, the adjoint test's five; their modules, batch parts and Hessian parts are
+bounds.  Shapes (``hessian_cases.GPU_KEYS``, the adjoint test's seven; their modules, batch parts and Hessian parts are
 compiled by ``__graft_entry__.build``): B5 - 5 nodes, light columns only; G17 - 17 nodes, parameterised, one heavy
 column; layout_8 - two phases, 130 variables without a term, two heavy columns; P2U - a parameterised module; B90 - 90
 nodes, the final time is heavy and its 272 terms take a thread through its chain twice.  tests/test_hessian.py checks on

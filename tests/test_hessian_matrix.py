@@ -241,6 +241,20 @@ def test_the_shapes_cover_every_path_of_the_kernel():
     assert all(sparse.values())
     hp = mc.plan(mc.case("layout_8"))
     assert (np.diff(hp.indptr) == 0).sum() >= 130
+    # bit 1 of a slot's `reads` word (the dynamics term of every defect row of the own block, not of row k == l alone):
+    # NL2's np.sum(x * x) has curvature along x_l in all N rows, so the diagonal entry of x_l lists N terms of the own
+    # block; NL0's cos(x - x[0]) couples x_k with x_0 - a stored pair inside one state's slice, its terms in that block
+    assert len(mc.GPU_KEYS) == 7
+    for key, l, partner, count in (("NL2", 5, 5, 21), ("NL0", 5, 0, 1)):
+        C = mc.case(key)
+        hp, sl = mc.plan(C), C.program.mv[0]
+        assert sl.length == 21 and codegen.SweepPlan(C.program).mv_generic[0] == 1
+        j, b = sl.leaf_base + l, sl.leaf_base + partner
+        at = [q for q in range(hp.indptr[j], hp.indptr[j + 1]) if hp.cols[q] == b]
+        assert len(at) == 1, (key, "the pair is not stored")
+        lst = hp.tlist[hp.tptr[at[0]]:hp.tptr[at[0] + 1]]
+        items = hp.terms[hp.owner[at[0]]] - sl.length
+        assert sum(1 for t in lst if t >= items) == count, (key, lst)
 
 
 # ------------------------------------------------------------------------------------------------ 5. the probe's own checks

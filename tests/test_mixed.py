@@ -45,7 +45,7 @@ import adjoint_cases as ac
 import mixed_cases as mc
 import og_math_cases
 import parameter_exact_cases as ec
-from opengoddard_amd import _native, build, optimize, problems
+from opengoddard_amd import _native, build, codegen, optimize, problems
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REPORT = os.path.join(ROOT, "profiles", "mixed.md")
@@ -239,6 +239,40 @@ def test_the_shapes_cover_every_path_of_the_kernel(probe_dir):
     C, r = runs["P2U"]
     assert np.abs(r.S[2, 5]).max() > 0
     assert set(mc.case("P2U").unread) == {4}
+    # bit 1 of a slot's `reads` word (og_mix.h: the dynamics part of every entry of the own block): NLP, and only it
+    assert len(mc.KEYS) == 7
+    assert set(int(v) for v in runs["NLP"][1].reads) == {-1, 1, 3}
+    assert all(set(int(v) for v in r.reads) <= {-1, 0, 1} for key, (_, r) in runs.items() if key != "NLP")
+
+
+def test_the_nonlocal_case_has_mixed_terms_off_the_diagonal_of_the_own_block(probe_dir):
+    """``NLP``: ``dx[0] = v - a * (x - x.mean())`` - ``d2 defect_x(k) / dx_l da`` is ``(delta_kl - 1/N)`` times half the
+    phase's duration, so off the diagonal it is ``-0.5 / 21``.  og_mix.h reaches those entries through ``reads & 2`` alone.
+    From the oracle (differences in ``a`` of the complex-step Jacobian), which knows nothing of the bit: at least 1e-4."""
+    C, r = _probed("NLP", probe_dir)
+    assert set(int(v) for v in r.reads) == {-1, 1, 3} and C.names == ("a", "b") and len(C.thetas) == 2
+    sl = C.program.mv[0]
+    plan = codegen.SweepPlan(C.program)
+    assert (plan.mv_diag[0], plan.mv_generic[0], sl.length) == (1, 1, 21)
+    leaf, N, row0 = sl.leaf_base, sl.length, plan.slot_row0[0]
+    ks = (2, 17)
+    W = np.zeros((len(ks), C.m))
+    for d, k in enumerate(ks):
+        W[d, row0 + k] = 1.0                            # row d of the result: d2 defect_x(k) / dx da
+    exe = mc.build_probe(C, probe_dir, "g++")
+    for theta in C.thetas:
+        ref, err = mc.oracle_mixed(C, C.points[1], W, theta, 0)
+        got = mc.run_probe(C, exe, probe_dir, C.points[1], W, theta, "own_block").S[:, 0, :]
+        assert err.max() <= SMOOTH
+        for d, k in enumerate(ks):
+            off = np.array([l for l in range(N) if l != k])
+            assert np.abs(ref[d, leaf + off]).min() >= 1e-4, (k, float(np.abs(ref[d, leaf + off]).min()))
+            assert np.abs(got[d, leaf + off]).min() >= 1e-4
+            assert np.max(np.abs(got[d] - ref[d]).astype(float)) <= max(10.0 * err.max(), 1e-12)
+            # closed form: the oracle's entries are -(t_f - t_0) / 2 / N there
+            half = 0.5 * (C.points[1][C.n - 2] - 0.0)
+            assert np.allclose(ref[d, leaf + off].astype(float), half / N, rtol=1e-6, atol=0) or \
+                np.allclose(ref[d, leaf + off].astype(float), -half / N, rtol=1e-6, atol=0)
 
 
 def test_a_vector_of_nine_is_the_call_with_that_vector_alone(probe_dir):
