@@ -7,8 +7,11 @@ subproblem, relaxed QP for an inconsistent linearisation (``rho`` = 100, x10 up 
 multiplier averaging for the L1 merit function, the inexact line search
 (``alpha = max(h3 / (2 (h3 - h1)), 0.1)``, at most ten cuts), Powell-damped BFGS, up to five
 resets on a non-descent direction, the relaxed convergence test after the last reset, and the exit
-modes 0 / 4 / 6 / 8 / 9 with SciPy's messages - so iteration counts and results match SciPy's up
-to the rounding of the QP solution (``tests/test_slsqp_core.py`` replays SciPy's own iterates).
+modes 0 / 4 / 5 / 6 / 8 / 9 with SciPy's messages - so iteration counts and results match SciPy's up
+to the rounding of the QP solution (``tests/test_slsqp_core.py`` replays SciPy's own iterates).  A
+trial point where the problem's functions are NaN or inf is cut like SciPy cuts it, and a
+linearisation at such a point ends the solve before the QP core sees it
+(``tests/test_sqp_nonfinite.py``).
 
 What is different is where the data lives.  The FD Jacobian never leaves HBM: the sweep kernel
 writes it transposed, the QP core (``include/ogsqp.h``) reads it in place, and only O(n) vectors
@@ -183,6 +186,38 @@ def prepare(engine):
     return None
 
 
+# ``MAX`` as SciPy's SLSQP shows it at non-finite trial points (observed on SciPy 1.15.3, tests/test_sqp_nonfinite.py; its
+# Fortran source is not available here): ``MAX(a, b)`` with a NaN first argument gives the second one.  The step cut
+# ``MAX(h3 / (2 (h3 - h1)), 0.1)`` is 0.1 when the trial point's merit is NaN, and ``MAX(-c_j, 0)`` of an inequality row
+# that is NaN is 0: the merit function and the violation sums do not see such a row.  (Equality rows go through
+# ``MAX(-c_j, c_j)``, which stays NaN, as ``abs`` does.)  On finite data both are the plain maximum, bit for bit.
+def _fmax(a, b):
+    return a if a > b else b
+
+
+def _fmax0(v):
+    return np.where(v > 0.0, v, 0.0)
+
+
+def _finite_linearisation(c, g):
+    """Can a QP subproblem be built on this linearisation?  SciPy's LSQ, handed a non-finite ``c`` or ``g``, ends the
+    run (observed on SciPy 1.15.3 over tests/sqp_nonfinite_cases.py; :func:`_nonfinite_exit` gives its mode).  A
+    non-finite COST VALUE alone does not: ``f`` never enters the subproblem, SciPy goes on with its line searches
+    (every trial point is then rejected, eleven evaluations per iteration).  The Jacobian stays on the device and is
+    not looked at: NaN in ``J_T`` alone is not caught here."""
+    return bool(np.all(np.isfinite(c)) and np.all(np.isfinite(g)))
+
+
+def _nonfinite_exit(it, c_eq):
+    """SciPy's exit mode for a subproblem on non-finite data, as OBSERVED (tests/test_sqp_nonfinite.py: the two-variable
+    ``start_*`` and mode-5 cases, and four traced problems of 16 to 28 variables started outside their domain): 5
+    ("Singular matrix E in LSQ subproblem") - except for the FIRST subproblem with finite equality rows, where the NaN or inf arrives
+    through ``g`` or an inequality row only: 4 ("Inequality constraints incompatible").  Why is not known (SciPy's
+    Fortran source was not read); that its BFGS update has been fed the non-finite gradient from the second subproblem
+    on, and not before the first, is a guess that fits."""
+    return 4 if it == 1 and bool(np.all(np.isfinite(c_eq))) else 5
+
+
 def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivative=None, disp=False,
                        callback=None, iprint=1):
     """Minimise with the engine's callbacks.  ``engine`` is a :class:`~.engine.HipEngine`;
@@ -218,7 +253,9 @@ def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivati
         F = jacobian.sweep(xv, lb, ub)
         last_p[0] = xv.copy()
         last_p[0][-1] += jacobian.last_step[-1]          # quirk Q13: the FD loop ends on the last column
-        if cost_derivative is None:
+        if not np.all(np.isfinite(F[1:])):
+            grad = np.full(n, np.nan)                    # (the solve ends here: no launch on a J_T that holds NaN)
+        elif cost_derivative is None:
             grad = core.jt_times(jacobian.ptr, jacobian.ld, unit0, jacobian.stream)
         else:
             grad = np.asarray(cost_derivative(xv), dtype=float).reshape(n)
@@ -231,16 +268,17 @@ def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivati
         return grad + core.jt_times(jacobian.ptr, jacobian.ld, coef, jacobian.stream)
 
     def violation(cv):
-        return float(np.sum(np.abs(cv[:meq])) + np.sum(np.maximum(-cv[meq:], 0.0)))
+        return float(np.sum(np.abs(cv[:meq])) + np.sum(_fmax0(-cv[meq:])))
 
     acc = abs(ftol)
     tol = 10.0 * acc
     f, c, g = linearise(x)
+    finite = _finite_linearisation(c, g)
     nfev, njev = 1, 1
     mu = np.zeros(m)
 
     def merit_terms(cv):
-        return float(mu[:meq] @ np.abs(cv[:meq]) + mu[meq:] @ np.maximum(-cv[meq:], 0.0))
+        return float(mu[:meq] @ np.abs(cv[:meq]) + mu[meq:] @ _fmax0(-cv[meq:]))
 
     itermx = maxiter - 1
     it = 0
@@ -263,6 +301,10 @@ def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivati
         it += 1
         if it > itermx:
             status = 9
+            break
+        if not finite:
+            # (before the QP core is handed such data)
+            status = _nonfinite_exit(it, c[:meq])
             break
         dl, du = lb - x, ub - x
         t = time.perf_counter()
@@ -334,7 +376,7 @@ def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivati
             h1 = f + merit_terms(c) - t0
             if h1 <= h3 / 10.0 or line > 10:
                 break
-            alpha = max(h3 / (2.0 * (h3 - h1)), 0.1)
+            alpha = _fmax(h3 / (2.0 * (h3 - h1)), 0.1)
         if callback is not None:
             callback(np.copy(x))
         if disp and iprint >= 2:
@@ -345,8 +387,11 @@ def minimize_slsqp_hip(engine, x0, lb, ub, ftol=1e-6, maxiter=100, cost_derivati
             break
         f, c, g_new = linearise(x)
         njev += 1
-        eta = lagrangian_gradient(g_new, r) - v
         g = g_new
+        finite = _finite_linearisation(c, g)
+        if not finite:
+            continue                                     # no A'r, no BFGS update, no reset: the next subproblem is mode 5
+        eta = lagrangian_gradient(g_new, r) - v
         t = time.perf_counter()
         if core.bfgs(s, eta, fraction * Bd):
             reset = True

@@ -10,7 +10,8 @@ running SciPy itself on the same inputs (``tests/test_slsqp_core.py``):
 * ``slsqp``      - the major iteration: QP subproblem, the augmented QP for inconsistent
                    linearisations, L1 merit function with multiplier averaging, Armijo-type
                    inexact line search (step ``max(h3/(2(h3-h1)), 0.1)``, at most 10 cuts), Powell-
-                   damped BFGS, the reset / relaxed-tolerance exits (modes 0, 4, 6, 8, 9).
+                   damped BFGS, the reset / relaxed-tolerance exits (modes 0, 4, 6, 8, 9), non-finite trial
+                   points and linearisations as SciPy treats them (mode 5; tests/test_sqp_nonfinite.py).
 * ``qp_solve``   - the strictly convex QP ``min 1/2 d'Bd + g'd  s.t.  C d + c = 0,  G d + h >= 0,
                    lb <= d <= ub``.  Its solution is unique, so any exact method reproduces the
                    step of SciPy's LSQ/LSEI/LSI/LDP/NNLS chain up to rounding.  The method here is
@@ -31,6 +32,7 @@ import numpy as np
 EXIT_MODES = {0: "Optimization terminated successfully",
               2: "More equality constraints than independent variables",
               4: "Inequality constraints incompatible",
+              5: "Singular matrix E in LSQ subproblem",
               6: "Singular matrix C in LSQ subproblem",
               8: "Positive directional derivative for linesearch",
               9: "Iteration limit reached"}
@@ -349,6 +351,37 @@ def bfgs_factor_update(Z, s, eta, Bs):
 # ----------------------------------------------------------------------------------------------
 # major iteration
 # ----------------------------------------------------------------------------------------------
+# ``MAX`` as SciPy's SLSQP shows it at non-finite trial points (observed on SciPy 1.15.3, tests/test_sqp_nonfinite.py; its
+# Fortran source is not available here): ``MAX(a, b)`` with a NaN first argument gives the second one.  The step cut
+# ``MAX(h3 / (2 (h3 - h1)), 0.1)`` is 0.1 when the trial point's merit is NaN, and ``MAX(-c_j, 0)`` of an inequality row
+# that is NaN is 0: the merit function and the violation sums do not see such a row.  (Equality rows go through
+# ``MAX(-c_j, c_j)``, which stays NaN, as ``abs`` does.)  On finite data both are the plain maximum, bit for bit.
+def _fmax(a, b):
+    return a if a > b else b
+
+
+def _fmax0(v):
+    return np.where(v > 0.0, v, 0.0)
+
+
+def _finite_linearisation(c, g):
+    """Can a QP subproblem be built on this linearisation?  SciPy's LSQ, handed a non-finite ``c`` or ``g``, ends the
+    run (observed on SciPy 1.15.3 over tests/sqp_nonfinite_cases.py; :func:`_nonfinite_exit` gives its mode).  A
+    non-finite COST VALUE alone does not: ``f`` never enters the subproblem, SciPy goes on with its line searches
+    (every trial point is then rejected, eleven evaluations per iteration)."""
+    return bool(np.all(np.isfinite(c)) and np.all(np.isfinite(g)))
+
+
+def _nonfinite_exit(it, c_eq):
+    """SciPy's exit mode for a subproblem on non-finite data, as OBSERVED (tests/test_sqp_nonfinite.py: the two-variable
+    ``start_*`` and mode-5 cases, and four traced problems of 16 to 28 variables started outside their domain): 5
+    ("Singular matrix E in LSQ subproblem") - except for the FIRST subproblem with finite equality rows, where the NaN or inf arrives
+    through ``g`` or an inequality row only: 4 ("Inequality constraints incompatible").  Why is not known (SciPy's
+    Fortran source was not read); that its BFGS update has been fed the non-finite gradient from the second subproblem
+    on, and not before the first, is a guess that fits."""
+    return 4 if it == 1 and bool(np.all(np.isfinite(c_eq))) else 5
+
+
 def slsqp(fun, jac, x0, lb, ub, meq, ftol=1e-6, maxiter=100, callback=None, trace=None,
           teacher=None, qp=None):
     """``fun(x) -> (f, c)`` with ``c`` = equalities then inequalities (``>= 0``); ``jac(x) ->
@@ -382,12 +415,13 @@ def slsqp(fun, jac, x0, lb, ub, meq, ftol=1e-6, maxiter=100, callback=None, trac
     ireset = 0
     badlin = False
     Z = np.eye(n)
+    finite = _finite_linearisation(c, g)
 
     def violation(cv):
-        return float(np.sum(np.abs(cv[:meq])) + np.sum(np.maximum(-cv[meq:], 0.0)))
+        return float(np.sum(np.abs(cv[:meq])) + np.sum(_fmax0(-cv[meq:])))
 
     def merit_terms(cv):
-        return float(mu[:meq] @ np.abs(cv[:meq]) + mu[meq:] @ np.maximum(-cv[meq:], 0.0))
+        return float(mu[:meq] @ np.abs(cv[:meq]) + mu[meq:] @ _fmax0(-cv[meq:]))
 
     reset = True
     while status is None:
@@ -403,6 +437,10 @@ def slsqp(fun, jac, x0, lb, ub, meq, ftol=1e-6, maxiter=100, callback=None, trac
         it += 1
         if it > itermx:
             status = 9
+            break
+        if not finite:
+            # (before any QP is solved on such data)
+            status = _nonfinite_exit(it, c[:meq])
             break
         dl, du = lb - x, ub - x
         C, G = A[:meq], A[meq:]
@@ -483,7 +521,7 @@ def slsqp(fun, jac, x0, lb, ub, meq, ftol=1e-6, maxiter=100, callback=None, trac
             h1 = t - t0
             if h1 <= h3 / 10.0 or line > 10:
                 break
-            alpha = max(h3 / (2.0 * (h3 - h1)), 0.1)
+            alpha = _fmax(h3 / (2.0 * (h3 - h1)), 0.1)
         if teacher is not None and len(teacher) > len(trace):
             forced = np.asarray(teacher[len(trace)], dtype=float)
             trace[-1]["mismatch"] = float(np.max(np.abs(forced - x)))
@@ -502,8 +540,11 @@ def slsqp(fun, jac, x0, lb, ub, meq, ftol=1e-6, maxiter=100, callback=None, trac
         njev += 1
         if callback is not None:
             callback(x.copy())
-        eta = (g_new - A_new.T @ r) - v
         g, A = g_new, A_new
+        finite = _finite_linearisation(c, g)
+        if not finite:
+            continue                                        # no A'r, no BFGS update, no reset: the next subproblem is mode 5
+        eta = (g - A.T @ r) - v
         Bs = step_fraction * Bs_unit
         Znew = bfgs_factor_update(Z, s, eta, Bs)
         if Znew is None:
