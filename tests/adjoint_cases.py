@@ -18,8 +18,9 @@ brachistochrone on 90 nodes, joins them:
 * a collocation slot's ``reads`` word (bit 0: the dynamics term at node k reads the state at node k, bit 1: it reads the
   state's slice in some other way, and then every entry of the column's own block has a dynamics part) takes the values
   0 and 1 on the surface problems and the parameterised ones: 1 on all five of their shapes, 0 on ``B5``, ``B90`` and
-  ``layout_8``.  ``NL2`` and ``NL0`` of ``nonlocal_cases`` bring the other two: 2 on ``NL2`` (``np.sum(x * x)`` and
-  nothing else of ``x`` in its own row), 3 on ``NL0`` (``cos(x - x[0])``; ``v[0]`` next to ``v``).  A column that is no
+  ``layout_8``.  (One surface problem that is no GPU shape has 3: ``wide_reductions`` reduces over a state's slice.)
+  ``NL2`` and ``NL0`` of ``nonlocal_cases`` bring the other two: 2 on ``NL2`` (``np.sum(x * x)`` and nothing else of ``x``
+  in its own row), 3 on ``NL0`` (``cos(x - x[0])``; ``v[0]`` next to ``v``).  A column that is no
   node of a collocated state (controls, final times; -1 here) is on all of them.
 """
 import os
@@ -37,6 +38,48 @@ PROBE_SOURCE = os.path.join(ROOT, "tests", "adj_probe.cpp")
 BOUND = surface.BOUND           # 1e-12, of max(1, sum_r |J_rj w_r|) per column
 
 CPU_KEYS = dc.CPU_KEYS
+# g++ needs more than ten minutes per probe for the build with the address and undefined-behaviour sanitizers on this
+# problem's header (407 variables, reductions over 135 nodes); the toolchain's clang++ needs four.  So the sanitizer builds
+# of this key are clang++'s, and ``__graft_entry__.build`` compiles them ahead (``hessian_matrix_cases.probe_jobs``).
+SANITIZE_WITH_CLANG = ("wide_reductions",)
+PREBUILT = os.path.join(ROOT, "tools", "_build", "hess_probes")
+
+
+def sanitizer_compiler(key):
+    import og_math_cases
+    return og_math_cases.clangxx() if key in SANITIZE_WITH_CLANG else "g++"
+
+
+_VERSIONS = {}
+
+
+def _version(compiler):
+    if compiler not in _VERSIONS:
+        _VERSIONS[compiler] = subprocess.run([compiler, "--version"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout
+    return _VERSIONS[compiler]
+
+
+def prebuilt_folder(C):
+    """``tools/_build/hess_probes/<key>_<digest>``: the digest is over everything a probe of this case is compiled from -
+    the header, the probes' sources, ``csrc/*.h``, the flags and both compilers' versions - so a stale one is never
+    picked up."""
+    import hashlib
+    import og_math_cases
+    h = hashlib.sha1(C.header.encode())
+    csrc, tests = os.path.join(ROOT, "opengoddard_amd", "csrc"), os.path.join(ROOT, "tests")
+    for path in sorted(os.path.join(tests, f) for f in os.listdir(tests) if f.endswith("_probe.cpp")) + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        with open(path, "rb") as fh:
+            h.update(fh.read())
+    h.update(repr(ec.PROBE_FLAGS).encode())
+    h.update(_version("g++") + _version(og_math_cases.clangxx()))
+    return os.path.join(PREBUILT, "%s_%s" % (C.key, h.hexdigest()[:16]))
+
+
+def probe_folder(C, fallback):
+    """Where probes of this case built ahead are: the folder ``build()`` filled, or ``fallback`` (compiled there)."""
+    folder = prebuilt_folder(C)
+    return folder if os.path.isdir(folder) else fallback
 GPU_KEYS = dc.GPU_KEYS + ("B90",)
 
 

@@ -2,8 +2,8 @@
 compiles the GPU cases' modules and directional parts ahead of the GPU run): problems, points, directions, the two
 references of ``F'(x) v`` and the host probe of ``csrc/og_dir.h``.
 
-Cases: ``brachistochrone``; ``table_ascent`` (``interp1d``); the edge problems ``ragged_two_phase`` and
-``wide_functions`` and the random layouts 5 and 8 of tests/test_exact_surface.py (their own four named points); the
+Cases: ``brachistochrone``; every problem of ``test_exact_surface.PROBLEMS`` - the 8 edge problems, the 9 random layouts
+and ``table_ascent`` (``interp1d``) - at their own four named points; the
 parameterised ``P2U`` and ``G17`` of tests/parameter_exact_cases.py (imported: their own points and parameter sets);
 ``B5``, the brachistochrone on 5 nodes.  Every case adds seeded 2 % perturbations of its first point.  ``NL2`` and ``NL0``
 are built by ``nonlocal_cases`` (dynamics that read a state across the nodes of its phase: bit 1 of a slot's ``reads``
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_SOURCE = os.path.join(ROOT, "tests", "dir_probe.cpp")
 BOUND = surface.BOUND           # 1e-12, of max(1, sum_j |J_rj v_j|) per row
 
-SURFACE_KEYS = ("brachistochrone", "table_ascent", "ragged_two_phase", "wide_functions", "layout_5", "layout_8")
+SURFACE_KEYS = ("brachistochrone",) + tuple(surface.PROBLEMS)
 PARAMETER_KEYS = ("P2U", "G17")
 NONLOCAL_KEYS = ("NL2", "NL0")
 CPU_KEYS = SURFACE_KEYS + PARAMETER_KEYS + NONLOCAL_KEYS

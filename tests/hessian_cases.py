@@ -8,6 +8,12 @@ What the seven contain (checked by tests/test_hessian.py from the probe's struct
 terms and a column the tracer marks heavy (the final time of ``B90``, both), columns with no term (``layout_8``), light
 columns (all), every value of a slot's ``reads`` word (2 and 3 on ``NL2`` and ``NL0`` of ``nonlocal_cases``: curvature in
 every entry of a state's own block).
+
+``SURFACE_KEYS`` (tests/test_hessian_surface.py, CPU) are the problems of ``test_exact_surface.PROBLEMS`` at their four
+named points - the whole traced surface with its reductions, selects, tables and jumps, and the ``switch`` point exactly
+on every tie and knot; their reference is ``oracle.exact_hess``, which follows the branches as the kernels do.
+``GPU_SURFACE_KEYS`` are the four of them tests/test_hessian_surface_gpu.py runs on the device.  ``GALLERY`` is a small
+problem with the kinds of node ``codegen`` can emit and no surface problem contains, at four named points of its own.
 """
 import os
 import subprocess
@@ -17,7 +23,7 @@ import numpy as np
 import adjoint_cases as ac
 import parameter_exact_cases as ec
 import test_exact_surface as surface
-from oracle import exact_jac
+from oracle import exact_hess, exact_jac
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE_SOURCE = os.path.join(ROOT, "tests", "hvp_probe.cpp")
@@ -25,7 +31,110 @@ RULES_SOURCE = os.path.join(ROOT, "tests", "dual2_probe.cpp")
 BOUND = surface.BOUND           # 1e-12: the project's bound for exact modes (the symmetry test)
 
 GPU_KEYS = ac.GPU_KEYS
-case = ac.case
+SURFACE_KEYS = tuple(surface.PROBLEMS)
+# where the central-difference reference (``oracle_products``) leaves no column out at the guess, the generic and the
+# minus point: every surface problem whose callbacks are smooth away from the switch point
+SMOOTH_KEYS = ("wide_reductions", "running_cost_shapes", "preallocated_outputs", "wide_functions", "layout_5",
+               "ragged_two_phase", "smooth_knots", "bryson_denham", "constant_scratch_buffers")
+# the device's shapes: reductions, clip, tables and ties through the workgroup path and a chain's second trip (n 407, 137
+# heavy columns, one of 270 terms); table lookups on knots and mask assignment under a 200-term final time (n 281); the
+# jumps of % and mod, heaviside at 0 and a tie of max(axis=0) (n 55); a where threshold and a tie of maximum over two
+# ragged phases (n 48)
+GPU_SURFACE_KEYS = ("wide_reductions", "table_ascent", "preallocated_outputs", "ragged_two_phase")
+
+
+# the kinds of node ``codegen`` can emit that no surface problem contains: a problem of its own (``Gallery``), so that the
+# second-order path runs through every one of them
+GALLERY = "kinds_gallery"
+GALLERY_KNOTS = np.array([-1.0, 0.0, 0.5, 1.0, 1.5, 3.0])
+GALLERY_TABLE = np.array([0.5, 1.0, 1.5, 1.25, 2.0, 4.0])
+
+
+def gallery_problem():
+    """``arctan2``, ``tan``, ``log``, ``arcsin``, ``arccos``, ``np.fmod``, ``>=`` / ``<=`` / ``!=`` under ``&`` and ``|``, and
+    a table that refuses an argument outside its knots (``bounds_error``) - two states and a control on 7 nodes."""
+    from scipy import interpolate
+    from opengoddard_amd.optimize import Condition, Dynamics, Problem
+    table = interpolate.interp1d(GALLERY_KNOTS, GALLERY_TABLE)
+
+    def dynamics(prob, obj, section):
+        x, y, u = prob.states(0, section), prob.states(1, section), prob.controls(0, section)
+        dx = Dynamics(prob, section)
+        dx[0] = np.arctan2(y, 1.0 + x * x) + np.tan(0.4 * u)
+        dx[1] = np.log(1.5 + x * x) * np.arcsin(0.5 * u) - np.arccos(0.3 * y) * x
+        return dx()
+
+    def equality(prob, obj):
+        x, y = prob.states(0, 0), prob.states(1, 0)
+        rows = Condition()
+        rows.equal(x[0], 0.3)
+        rows.equal(np.fmod(y[-1] * 3.0, 0.7) * x[-1], 0.1)
+        return rows()
+
+    def inequality(prob, obj):
+        x, y, u = prob.states(0, 0), prob.states(1, 0), prob.controls(0, 0)
+        rows = Condition()
+        rows.lower_bound(np.where((x >= 0.5) & (u <= 0.25), x * u * u, y * y * x), -50.0)
+        rows.lower_bound(np.where((y != 0.75) | (x > 2.0), np.sin(y) * x, x ** 3 * y), -50.0)
+        rows.upper_bound(table(x) * y * y, 50.0)
+        rows.upper_bound(np.fmod(x, 0.25) * u * x, 50.0)
+        return rows()
+
+    prob = Problem([0.0, 1.0], [7], [2], [1], 1)
+    rng = np.random.default_rng(31)
+    prob.p[:-1] = rng.uniform(0.3, 1.2, prob.number_of_variables - 1)
+    prob.dynamics = [dynamics]
+    prob.cost = lambda prob, obj: prob.states(1, 0)[-1] ** 2
+    prob.equality = equality
+    prob.inequality = inequality
+    return prob, object()
+
+
+class Gallery(ac.dc.Case):
+    """``kinds_gallery`` at four named points of its own: the guess, two generic points and a ``switch`` point exactly on
+    the ties of ``>=``, ``<=`` and ``!=``, on a jump of ``fmod`` and on a knot of the table."""
+
+    def __init__(self):
+        from opengoddard_amd import codegen
+        self.key = GALLERY
+        self.thetas = [None]
+        self.prob, self.obj = gallery_problem()
+        self.program = codegen.trace_problem(self.prob, self.obj)
+        self.header = codegen.emit_header(self.program)
+        self.n, self.m = self.program.n, self.program.m
+        guess = np.array(self.prob.p, dtype=float)
+        rng = np.random.default_rng(37)
+        a = rng.standard_normal(self.n)
+        generic, minus = guess * (1.0 + 0.02 * a), guess * (1.0 - 0.02 * a)
+        switch = generic.copy()
+        X, Y, U = (lambda k: self.prob.index_states(0, 0, k)), (lambda k: self.prob.index_states(1, 0, k)), \
+            (lambda k: self.prob.index_controls(0, 0, k))
+        switch[X(1)], switch[U(1)] = 0.5, 0.25                  # x >= 0.5 and u <= 0.25, both on the tie; a knot of the table
+        switch[Y(2)] = 0.75                                     # y != 0.75 is false here only
+        switch[X(3)] = 1.0                                      # a knot, and fmod(x, 0.25) on a jump
+        switch[X(4)], switch[U(4)] = 0.5, 0.5                   # the tie of >= with <= false
+        switch[X(5)] = 0.75                                     # a jump of fmod between two knots
+        self.points = [guess, generic, switch, minus]
+
+
+def case(key):
+    if key == GALLERY:
+        if key not in ac.dc._CASES:
+            ac.dc._CASES[key] = Gallery()
+        return ac.dc._CASES[key]
+    return ac.case(key)
+
+
+def named_point(C, name):
+    """One of the four named points of a surface case (``directional_cases.Case`` lists them first) or of the gallery."""
+    assert C.key in SURFACE_KEYS + (GALLERY,)
+    return C.points[surface.POINTS.index(name)]
+
+
+def exact_products(C, x, W, V, theta=None, dtype=complex):
+    """``(ref[K, n], scale[K, n])`` of ``oracle.exact_hess`` for the pairs ``(W[k], V[k])``: the product in
+    ``np.longdouble`` and the reference's own ``sum_r |w_r d2F_r/dx_j dv|``."""
+    return exact_hess.products(C.at(theta), C.prob, x, W, V, dtype=dtype)
 
 
 def pairs(C):
@@ -251,7 +360,7 @@ def rule_truth(record):
     return [mp.fsum(p) for p in parts], [mp.fsum(abs(t) for t in p) for p in parts]
 
 
-# what __graft_entry__.build compiles for tests/test_hessian_gpu.py: (label, header), each with its Hessian part and its
-# batch part
+# what __graft_entry__.build compiles for tests/test_hessian_gpu.py and tests/test_hessian_surface_gpu.py: (label, header),
+# each with its Hessian part and its batch part
 def modules():
-    return [("hessian " + key, case(key).header) for key in GPU_KEYS]
+    return [("hessian " + key, case(key).header) for key in GPU_KEYS + GPU_SURFACE_KEYS]

@@ -18,6 +18,7 @@ PROBE_SOURCE = os.path.join(ROOT, "tests", "hess_probe.cpp")
 BOUND = hc.BOUND                # 1e-12: the project's bound for exact modes (the symmetry test)
 
 GPU_KEYS = hc.GPU_KEYS
+SURFACE_KEYS, GPU_SURFACE_KEYS = hc.SURFACE_KEYS, hc.GPU_SURFACE_KEYS      # tests/test_hessian_surface*.py
 case = hc.case
 weights = hc.ac.weights
 
@@ -97,7 +98,33 @@ def unit_products(C, exe, folder, x, W, theta=None, tag="unit"):
     return r.Q.reshape(K, n, n), r.S.reshape(K, n, n)
 
 
-# what __graft_entry__.build compiles for tests/test_hessian_matrix_gpu.py: (label, header), each with its Hessian-matrix
-# part, its Hessian part (the unit-direction check) and its batch part
+# ------------------------------------------------------------------------------------------------ probes built ahead
+# The g++ probes of the surface shapes take up to half a minute to compile (wide_reductions: a header of 407 variables) and
+# that problem's sanitizer builds four minutes each with clang++; ``__graft_entry__.build`` compiles them into
+# ``adjoint_cases.prebuilt_folder`` so that tests/test_hessian_surface_gpu.py, tests/test_hessian_surface.py and
+# tests/test_adjoint.py only run them.
+prebuilt_folder, probe_folder = hc.ac.prebuilt_folder, hc.ac.probe_folder
+
+
+def probe_jobs():
+    """One callable per probe ``__graft_entry__.build`` compiles ahead."""
+    def job(key, build, compiler, sanitize):
+        def run():
+            C = case(key)
+            folder = prebuilt_folder(C)
+            os.makedirs(folder, exist_ok=True)
+            for entry in os.listdir(hc.ac.PREBUILT):    # an older revision's
+                if entry.startswith(key + "_") and entry != os.path.basename(folder):
+                    import shutil
+                    shutil.rmtree(os.path.join(hc.ac.PREBUILT, entry), ignore_errors=True)
+            return build(C, folder, compiler, sanitize)
+        return run
+    jobs = [job(key, build, hc.ac.sanitizer_compiler(key), True) for key in hc.ac.SANITIZE_WITH_CLANG
+            for build in (hc.build_probe, build_probe, hc.ac.build_probe)]         # the long ones first
+    return jobs + [job(key, build, "g++", False) for key in GPU_SURFACE_KEYS for build in (hc.build_probe, build_probe)]
+
+
+# what __graft_entry__.build compiles for tests/test_hessian_matrix_gpu.py and tests/test_hessian_surface_gpu.py: (label,
+# header), each with its Hessian-matrix part, its Hessian part (the unit-direction check) and its batch part
 def modules():
-    return [("hessian matrix " + key, case(key).header) for key in GPU_KEYS]
+    return [("hessian matrix " + key, case(key).header) for key in GPU_KEYS + GPU_SURFACE_KEYS]

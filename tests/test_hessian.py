@@ -36,7 +36,10 @@ HEAD = ["# Exact grad^2 (w . F)(x) v: the rules of csrc/og_dual2.h and the host 
         "Rules: worst difference from mpmath (50 digits) over the four parts of every record of the function, in units of",
         "the sum of the absolute values of the rule's terms.  Shapes: the oracle reference's own error estimate and the",
         "probe's worst difference from it, per column in units of max(1, sum_r |w_r d2F_r/dx_j dv|).  Written by",
-        "tests/test_hessian.py.", "", "| what | figure |", "|---|---|"]
+        "tests/test_hessian.py; the \"referee\", \"surface\" and \"surface triangles\" lines (oracle/exact_hess.py against the",
+        "difference reference, the probe against that referee in units of its own scale, and the two orientations of a Hessian",
+        "entry, over the traced surface at its four named points) by tests/test_hessian_surface.py.", "",
+        "| what | figure |", "|---|---|"]
 
 
 def _note(key, text):
