@@ -584,6 +584,43 @@ int og_hessian_matrix_batch_dev(og_batch b, int32_t count, const double* d_X, co
                                 double* d_H, void* hip_stream);
 int og_hessian_matrix_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* H);
 
+/* ---- exact second derivatives of w . F in the run-time parameters: the theta-theta block ---------------
+ * S[d][k][l] = sum_r W[d][r] d2F_r/dtheta_k dtheta_l of F = [cost | c_eq | c_ineq], [kw][n_par][n_par] row-major and
+ * dense, for kw weight vectors W[d][m] over the rows of F, at the handle's current parameter values: with W = [1, lambda]
+ * it is d2L/dtheta2, the third block of the Hessian of the Lagrangian in (x, theta) next to og_hessian_vector /
+ * og_hessian_matrix (xx) and og_adjoint_parameter (x theta); with x held fixed the exact Hessian in theta.  For a pair
+ * (k, l) the entries summed are those of the work lists of its OWNER - the parameter with fewer entries, a tie to the
+ * lower index - each evaluated on second-order dual numbers (csrc/og_dual2.h) with the unit seed of slot 1 on the
+ * owner's table entry and the unit seed of slot 2 on the partner's (csrc/og_pp.h); the ORDER of the sum is og_adjoint's
+ * (csrc/og_adj.h), so the result is reproducible to the bit and vector d of a call with kw vectors is bit for bit the
+ * call with that vector alone.  A row whose weight is zero is not skipped; an entry that does not read the partner
+ * contributes an exact +0.0; a parameter that nothing reads gets a row and a column of +0.0; S[d][l][k] is a copy of
+ * S[d][k][l]; every call writes all kw * n_par * n_par doubles.  No step in theta, no og_set_parameters launch.  At a
+ * switch of the callbacks the derivative is that of the branch F(x) takes.
+ * Load rule: the kernels live in a part of the callback module of its own (pp_part_path:
+ * opengoddard_amd.build.build_pp_part).  og_parameter_hessian_load loads it once per handle - a later call is a no-op
+ * and may pass NULL - and og_problem_destroy closes it; error 4: the part is missing or cannot be loaded, 5: it belongs
+ * to another module.  The other four fail with error 4 while it is not loaded.  All five fail with error 1 (and a
+ * message in og_last_error) for a module that declares no run-time parameter, for null pointers, kw < 1 or kw > 65535,
+ * or a count outside 1 .. capacity.
+ * og_parameter_hessian_dev: two launches on hip_stream - the evaluation at d_x (F into d_F0, or into the handle's own
+ * array when d_F0 is NULL) and the kernel, one workgroup per pair k <= l and chunk of 8 weight vectors, which evaluates
+ * an entry once for all vectors of its chunk.  Asynchronous and capturable: a captured graph replays on new contents of
+ * d_x and d_W and on new parameter values.  No J_T is written and no registered buffer's bookkeeping moves.
+ * og_parameter_hessian: host pointers, blocking; F0 may be NULL.
+ * The batched forms: lane c works at X[c], with the ONE weight vector W[c] and at the lane's own parameters
+ * (og_parameters_batch*), and writes S[c][n_par][n_par] and F0[c][m] (d_F0 / F0 may be NULL); bit for bit the
+ * single-point call at that point, vector and those values.  Three launches whatever count is: bind, the batched
+ * evaluation, the kernel.  A multi-device handle (og_multi_*) has no form of this call and does not split it.
+ * No reference counterpart: the reference has no derivative at all. */
+int og_parameter_hessian_load(og_handle h, const char* pp_part_path);
+int og_parameter_hessian_dev(og_handle h, const double* d_x, int32_t kw, const double* d_W, double* d_S, double* d_F0,
+                             void* hip_stream);
+int og_parameter_hessian(og_handle h, const double* x, int32_t kw, const double* W, double* S, double* F0);
+int og_parameter_hessian_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                   double* d_S, void* hip_stream);
+int og_parameter_hessian_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* S);
+
 /* ---- diagnostics ---------------------------------------------------------------------------*/
 const char* og_last_error(void);
 /* Diagnostics: synchronise `device` and copy `bytes` bytes of its memory to the host (tests read the replicas of

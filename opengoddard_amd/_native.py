@@ -146,6 +146,13 @@ SIGNATURES = {
     "og_hessian_matrix_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
     "og_hessian_matrix_batch": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "og_parameter_hessian_load": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "og_parameter_hessian_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "og_parameter_hessian": (C.c_int, [C.c_void_p, _c_double_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p]),
+    "og_parameter_hessian_batch_dev": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "og_parameter_hessian_batch": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "og_device_read": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "og_trace_read": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
     "og_last_error": (C.c_char_p, []),

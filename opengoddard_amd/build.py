@@ -71,7 +71,7 @@ def _core_sources():
 
 def _kernel_sources():
     return [os.path.join(CSRC, f) for f in ("ogk_kernels.hip", "ogk_fused_workgroup.inc", "ogk.h", "og_math.h", "og_dual.h", "og_par.h",
-                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h", "og_mix.h", "og_hess.h")]
+                                               "og_dir.h", "og_adj.h", "og_dual2.h", "og_hvp.h", "og_mix.h", "og_hess.h", "og_pp.h")]
 
 
 def _build_library(lib, sources, override, force):
@@ -276,6 +276,21 @@ def build_hessian_matrix_part(header_source, force=False):
     the module and the other on-demand parts are what they were, and a user who never asks builds and loads what they
     did before.  (``hessian_part_path`` and ``.hvp.so`` stay the Hessian-vector part's.)"""
     return _build_on_demand_part(header_source, HESSIAN_MATRIX_PART, hessian_matrix_part_path, force)
+
+
+PP_PART = 12                    # OGK_PART_PP, <module>.pp.so: exact second derivatives of w . F in the parameters
+
+
+def pp_part_path(out):
+    return out[:-3] + ".pp.so"
+
+
+def build_pp_part(header_source, force=False):
+    """``ogk_exact_pp`` / ``ogk_exact_pp_batch`` (``OGK_PART=12``) -> path of ``<module>.pp.so``.  A part of its own,
+    built when a parameter Hessian is first asked for (``HipEngine.parameter_hessian``,
+    ``BatchSweep.parameter_hessian``): the module and the other on-demand parts are what they were, and a user who never
+    asks builds and loads what they did before."""
+    return _build_on_demand_part(header_source, PP_PART, pp_part_path, force)
 
 
 def build_module(header_source, digest=None, force=False, out_suffix="", parts=None):

@@ -1102,6 +1102,12 @@ def _parameter_section(P):
             "decltype((void)x.par_seed, typename X::scalar()) {",
             "        return typename X::scalar(cv[i], i == x.par_seed ? 1.0 : 0.0);",
             "    }",
+            "    // (an accessor with the members par_seed1 and par_seed2 and no par_seed - csrc/og_pp.h - seeds both slots of a",
+            "    // second-order dual number: slot 1 on the one index, slot 2 on the other, both on one leaf when they are equal)",
+            "    template <class X> OG_HDI static auto par_leaf(const X& x, const double* cv, const int i, int) -> "
+            "decltype((void)x.par_seed2, typename X::scalar()) {",
+            "        return typename X::scalar(cv[i], i == x.par_seed1 ? 1.0 : 0.0, i == x.par_seed2 ? 1.0 : 0.0, 0.0);",
+            "    }",
             "    template <class X> OG_HDI static typename X::scalar par_leaf(const X&, const double* cv, const int i, long) "
             "{ return cv[i]; }",
             "    // dF/dtheta_k, work lists: the row groups PAR_ROW_G(PAR_ROW_PTR(k) ..) - every element of each is one entry, in",

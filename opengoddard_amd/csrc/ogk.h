@@ -120,8 +120,20 @@ enum ogk_mode {
 #define OGK_HESS_HEAD 8
 #define OGK_HESS_WORKGROUPS(nnz, n_light, n_units) (((nnz) - (n_light)) + ((n_units) + 3) / 4)   /* four units per workgroup */
 
+// The two modes of the parameter-Hessian part (OGK_PART_PP; macros for the same reason): exact second derivatives
+// S_kl = sum_r w_r d2F_r/dtheta_k dtheta_l of w . F in the run-time parameters (csrc/og_pp.h).  OGK_PP (ogk_launch):
+// K = col_hi - col_lo weight vectors of one point, vector d read at args->h + d * m as in OGK_ADJ, its [n_par][n_par]
+// doubles written to args->jt + d * n_par * n_par.  OGK_BATCH_PP (ogk_launch_batch): one weight vector per lane, lane c
+// reads H + c * m and writes vals + c * n_par * n_par of the launch's own ogk_batch_args (OGK_BATCH_BIND before it binds
+// X and F0 only); every lane at its own parameters, its record's cvec.  Both need an evaluation at the same point before
+// them on the same stream (y0), write every one of the n_par * n_par entries - S[l][k] a copy of S[k][l] - in the order
+// of sums that og_adj.h fixes, and touch no jt_state / jt_launches word.  A module without parameters answers
+// hipErrorInvalidValue.
+#define OGK_PP 27
+#define OGK_BATCH_PP 28
+
 // The parts a module is compiled in (-DOGK_PART=<value>, build.py: MODULE_PARTS, BATCH_PART, BATCH_EXACT_PART, PARAMETER_PART,
-// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART, MIX_PART, HESSIAN_MATRIX_PART).
+// DIRECTIONAL_PART, ADJOINT_PART, HESSIAN_PART, MIX_PART, HESSIAN_MATRIX_PART, PP_PART).
 // Preprocessor names: csrc/ogk_kernels.hip selects its kernels with them.
 #define OGK_PART_MAIN 0         /* <module>.so: OGK_EVAL, OGK_PATTERN_*, OGK_PACK, OGK_UNPACK, OGK_COUNT_LAUNCH */
 #define OGK_PART_AUX 1          /* <module>.p3.so: OGK_DENSE, OGK_EXACT_DENSE, OGK_EXACT */
@@ -135,6 +147,7 @@ enum ogk_mode {
 #define OGK_PART_HVP 9          /* <module>.hvp.so, on demand: OGK_HVP, OGK_BATCH_HVP */
 #define OGK_PART_MIX 10         /* <module>.mix.so, on demand: OGK_MIX, OGK_BATCH_MIX */
 #define OGK_PART_HESS 11        /* <module>.hess.so, on demand: OGK_HESS, OGK_BATCH_HESS */
+#define OGK_PART_PP 12          /* <module>.pp.so, on demand: OGK_PP, OGK_BATCH_PP */
 
 // The words of a handle's (and of every batch lane's) flag block: og_problem_s::d_flags, OGK_FLAG_WORDS ints.
 enum ogk_flag {

@@ -46,7 +46,8 @@
 #include <hip/hip_runtime.h>
 #include "ogk.h"
 #include "og_dual.h"
-#if defined(OGK_PART) && (OGK_PART == OGK_PART_HVP || OGK_PART == OGK_PART_MIX || OGK_PART == OGK_PART_HESS)
+#if defined(OGK_PART) && (OGK_PART == OGK_PART_HVP || OGK_PART == OGK_PART_MIX || OGK_PART == OGK_PART_HESS || \
+                          OGK_PART == OGK_PART_PP)
 #include "og_dual2.h"       // (ahead of the generated header, whose functions name ogm:: at their definition)
 #endif
 #include OG_GEN_HEADER
@@ -220,6 +221,9 @@ __device__ __forceinline__ int defect_block_to_group(int bx, int* nt_out) {
 #endif
 #if defined(OGK_PART) && OGK_PART == OGK_PART_HESS
 #define OGK_HAS_HESS 1       // OGK_HESS, OGK_BATCH_HESS: the exact sparse Hessian of w . F; built on demand
+#endif
+#if defined(OGK_PART) && OGK_PART == OGK_PART_PP
+#define OGK_HAS_PP 1         // OGK_PP, OGK_BATCH_PP: exact second derivatives of w . F in the parameters; built on demand
 #endif
 // (the split is at the kernels: a __global__ function is what costs code generation; the device functions below
 // them are templates or forced-inline and cost nothing where no kernel of the part uses them)
@@ -1600,7 +1604,7 @@ __global__ __launch_bounds__(SWEEP_THREADS) OGK_FUSED_ATTR void ogk_fused(const 
 // record in registers would cost the occupancy the amdgpu_waves_per_eu floor is there for.
 // ------------------------------------------------------------------------------------------
 #if defined(OGK_HAS_BATCH) || defined(OGK_HAS_BATCH_EXACT) || defined(OGK_HAS_PAR) || defined(OGK_HAS_DIR) || \
-    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP) || defined(OGK_HAS_MIX) || defined(OGK_HAS_HESS)
+    defined(OGK_HAS_ADJ) || defined(OGK_HAS_HVP) || defined(OGK_HAS_MIX) || defined(OGK_HAS_HESS) || defined(OGK_HAS_PP)
 typedef const ogk_args __attribute__((address_space(4))) * ogk_lane_table;
 __device__ __forceinline__ const ogk_args& batch_lane(const ogk_args* lanes) {
     // (written by the host when the batch was created and by ogk_batch_bind in an earlier launch; never by this one)
@@ -2318,6 +2322,85 @@ __global__ __launch_bounds__(HESS_THREADS) void ogk_exact_hess_batch(const ogk_a
 static_assert(OGK_HESS_WORKGROUPS(9, 2, 5) == 7 + (5 + HESS_WAVES - 1) / HESS_WAVES, "the runtime sizes the grid (ogk.h)");
 #endif
 
+// ------------------------------------------------------------------------------------------
+// Modes 27 and 28 (the parameter-Hessian part, OGK_PART_PP): exact second derivatives of w . F in the run-time
+// parameters, S_kl = sum_r w_r d2F_r/dtheta_k dtheta_l, [n_par][n_par] doubles per weight vector w.  S_kl is the sum that
+// og_pp.h defines: the entries of the work lists of the pair's OWNER (the parameter with fewer entries), each the mixed
+// part of the entry on second-order dual numbers - unit seed of slot 1 on the owner's table entry, of slot 2 on the
+// partner's - times the weight of its row, in the chains and the tree of og_adj.h.  One workgroup of OG_ADJ_CHAINS
+// threads serves ONE pair (blockIdx.x, of n_par (n_par + 1) / 2) and one chunk of up to PP_CHUNK weight vectors
+// (blockIdx.y; blockIdx.z the lane of a batch, one vector per lane): thread c is chain c, it evaluates each of its
+// entries ONCE and applies it to every vector of the chunk - the forward-mode work does not depend on w, which is the
+// sharing ogk_exact_mix lacks.  The tree's levels 32 .. 1 are a shuffle-down reduction inside a wavefront and the four
+// block sums meet in LDS as (p0 + p1) + (p2 + p3): the heavy path of exact_mix_block.  The pair, its owner and the ranges
+// of the owner's lists are the workgroup's, so they stay scalar loads.  Every S[d][k][l] and S[d][l][k] is written on
+// every call, +0.0 where the owner's list is empty; no J_T, no jt_state / jt_launches word, no atomics.  y0 is the
+// evaluation's (OGK_EVAL / OGK_BATCH_EVAL before this launch on the same stream).
+// ------------------------------------------------------------------------------------------
+#if defined(OGK_HAS_PP) && defined(OG_GEN_HAS_PAR)
+#include "og_pp.h"
+constexpr int PP_THREADS = OG_ADJ_CHAINS;
+constexpr int PP_WAVES = PP_THREADS / 64;
+constexpr int PP_CHUNK = 8;             // weight vectors per chunk: 16 VGPRs of partial sums per thread
+constexpr int PP_PAIRS = OgGen::N_PAR * (OgGen::N_PAR + 1) / 2;
+static_assert(PP_WAVES == 4 && PP_CHUNK <= 64, "og_adj_tree combines four blocks of 64 chains");
+
+// w: the chunk's first weight vector (the next at w + M), S: the [N_PAR][N_PAR] block of that vector (the next at
+// S + N_PAR * N_PAR), kc: the chunk's vectors, 1 .. PP_CHUNK.  Every thread reaches the barrier.
+__device__ __forceinline__ void exact_pp_block(const ogk_args& a, const double* w, double* S, const int kc) {
+    __shared__ double part[PP_CHUNK][PP_WAVES];
+    const int tid = (int)threadIdx.x;
+    // (the same in all 64 lanes of a wavefront - said to the compiler, as in exact_adj_block)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const OgPpPair p = og_pp_pair<OgGen>((int)blockIdx.x);
+    double r[PP_CHUNK];
+#pragma unroll
+    for (int d = 0; d < PP_CHUNK; ++d) r[d] = 0.0;
+    for (int e = tid; e < p.entries; e += OG_ADJ_CHAINS) {
+        int row;
+        const double t = og_pp_term<OgGen>(p.owner, p.partner, e, a.x0, a.y0, a.cvec, a.dfrag, &row).dd;
+#pragma unroll
+        for (int d = 0; d < PP_CHUNK; ++d)
+            if (d < kc) r[d] = __builtin_fma(w[(long)d * OgGen::M + row], t, r[d]);
+    }
+    // the levels s = 32 .. 1 of og_adj_tree -> valid in lane 0 (lane i of level s needs lane i + s < 2 s <= 64 only)
+#pragma unroll
+    for (int d = 0; d < PP_CHUNK; ++d)
+        if (d < kc) {
+#pragma unroll
+            for (int s = 32; s >= 1; s >>= 1) r[d] = r[d] + __shfl_down(r[d], s, 64);
+        }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int d = 0; d < PP_CHUNK; ++d) part[d][wave] = r[d];
+    }
+    __syncthreads();
+    if (tid < kc) {
+        const double v = (part[tid][0] + part[tid][1]) + (part[tid][2] + part[tid][3]);
+        double* Sd = S + (long)tid * (OgGen::N_PAR * OgGen::N_PAR);
+        Sd[p.k * OgGen::N_PAR + p.l] = v;
+        Sd[p.l * OgGen::N_PAR + p.k] = v;
+    }
+}
+
+// blockIdx.y: the chunk of the K = nw weight vectors, read at h + d * m, written to jt + d * n_par * n_par
+__global__ __launch_bounds__(PP_THREADS) void ogk_exact_pp(const ogk_args a, const int nw) {
+    const int d0 = (int)blockIdx.y * PP_CHUNK;
+    const int kc = nw - d0 < PP_CHUNK ? nw - d0 : PP_CHUNK;
+    exact_pp_block(a, a.h + (long)d0 * OgGen::M, a.jt + (long)d0 * (OgGen::N_PAR * OgGen::N_PAR), kc);
+}
+
+// the same on a lane's record (blockIdx.z: the lane; the record's own cvec gives every lane its own theta): one weight
+// vector per lane, row `lane` of W[count][m], the result slice `lane` of S[count][n_par][n_par] (the launch's own
+// arguments)
+__global__ __launch_bounds__(PP_THREADS) void ogk_exact_pp_batch(const ogk_args* __restrict__ lanes, const double* W,
+                                                                 double* S) {
+    const long lane = (long)blockIdx.z;
+    const ogk_args& a = *(const ogk_args*)((ogk_lane_table)lanes + blockIdx.z);
+    exact_pp_block(a, W + lane * OgGen::M, S + lane * (OgGen::N_PAR * OgGen::N_PAR), 1);
+}
+#endif
+
 #ifdef OGK_HAS_SWEEP
 __global__ __launch_bounds__(SWEEP_THREADS) void ogk_sweep(const ogk_args a) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2660,6 +2743,19 @@ extern "C" int ogk_launch(const ogk_args* args, int mode, void* stream_) {
         return (int)hipGetLastError();
     }
 #endif
+#ifdef OGK_HAS_PP
+    if (mode == OGK_PP) {
+#ifdef OG_GEN_HAS_PAR
+        // ncols weight vectors (gridDim.y: their chunks), one workgroup per pair of parameters and chunk
+        if (!args->jt || !args->x0 || !args->y0 || !args->h || ncols < 1 || ncols > 65535) return (int)hipErrorInvalidValue;
+        hipLaunchKernelGGL(ogk_exact_pp, dim3(PP_PAIRS, (ncols + PP_CHUNK - 1) / PP_CHUNK), dim3(PP_THREADS), 0, stream,
+                           *args, ncols);
+        return (int)hipGetLastError();
+#else
+        return (int)hipErrorInvalidValue;           // a module without run-time parameters
+#endif
+    }
+#endif
     return OGK_OTHER_PART;
 }
 
@@ -2829,5 +2925,25 @@ extern "C" int ogk_hess_terms(int32_t* terms) {
     if (e == hipSuccess) e = hipMemcpy(terms, d_terms, sizeof(int) * OgGen::N_VAR, hipMemcpyDeviceToHost);
     hipFree(d_terms);
     return (int)e;
+}
+#endif
+
+#ifdef OGK_HAS_PP
+// the parameter-Hessian part's batched mode, under the entry name of the batch parts as the mixed part's is; any other
+// mode is another part's.  H: the weight vectors W[count][m], vals: the result S[count][n_par][n_par] (the lane records
+// hold neither)
+extern "C" int ogk_launch_batch(const ogk_batch_args* b, int mode, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mode != OGK_BATCH_PP) return OGK_OTHER_PART;
+    if (!b || !b->lanes || b->count < 1 || b->count > b->capacity || b->count > 65535 || !b->H || !b->vals)
+        return (int)hipErrorInvalidValue;
+#ifdef OG_GEN_HAS_PAR
+    hipLaunchKernelGGL(ogk_exact_pp_batch, dim3(PP_PAIRS, 1, b->count), dim3(PP_THREADS), 0, stream,
+                       (const ogk_args*)b->lanes, b->H, b->vals);
+    return (int)hipGetLastError();
+#else
+    (void)stream;
+    return (int)hipErrorInvalidValue;               // a module without run-time parameters
+#endif
 }
 #endif

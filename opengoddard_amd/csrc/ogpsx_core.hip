@@ -248,6 +248,13 @@ struct og_problem_s {
     int32_t hess_grid = 0;
     double* d_hess = nullptr;
     size_t hess_capacity = 0;
+    // exact second derivatives of w . F in the parameters (og_parameter_hessian_load): the arrangement of the mixed part;
+    // d_pp: [W[k][m] | S[k][n_par][n_par]] staging of the host-pointer call, pp_capacity weight vectors large
+    void* pp_module = nullptr;
+    ogk_launch_fn pp_launch = nullptr;
+    ogk_launch_batch_fn pp_launch_batch = nullptr;
+    double* d_pp = nullptr;
+    size_t pp_capacity = 0;
 };
 static const int OG_MAX_JT_REGS = 63;
 static const size_t OG_TRACE_DOUBLES = (size_t)1 << 20;     // 16384 workgroups x 8 wavefronts x 8 stamps
@@ -900,6 +907,7 @@ void og_problem_destroy(og_handle p) {
     if (p->hvp_module) dlclose(p->hvp_module);
     if (p->mix_module) dlclose(p->mix_module);
     if (p->hess_module) dlclose(p->hess_module);
+    if (p->pp_module) dlclose(p->pp_module);
     og_shard_comm_destroy(p);
     if (p->stream) hipStreamDestroy(p->stream);
     hipFree(p->d_dfrag);
@@ -910,6 +918,7 @@ void og_problem_destroy(og_handle p) {
     hipFree(p->d_adj);
     hipFree(p->d_hvp);
     hipFree(p->d_mix);
+    hipFree(p->d_pp);
     hipFree(p->d_hess_plan);
     hipFree(p->d_hess);
     hipFree(p->d_x);
@@ -1446,6 +1455,7 @@ struct og_batch_s {
     double* d_aj = nullptr;                 // [W[capacity][m] | G[capacity][n]] staging of the host-pointer og_adjoint_batch
     double* d_hj = nullptr;                 // [W[capacity][m] | Q[capacity][n]] staging of the host-pointer og_hessian_vector_batch
     double* d_mj = nullptr;                 // [W[capacity][m] | S[capacity][n_par][n]] staging of the host-pointer og_adjoint_parameter_batch
+    double* d_ppj = nullptr;                // [W[capacity][m] | S[capacity][n_par][n_par]] staging of the host-pointer og_parameter_hessian_batch
     double* d_hm = nullptr;                 // [W[capacity][m] | H[capacity][nnz]] staging of the host-pointer og_hessian_matrix_batch
 };
 
@@ -1628,6 +1638,7 @@ void og_batch_destroy(og_batch b) {
     hipFree(b->d_aj);
     hipFree(b->d_hj);
     hipFree(b->d_mj);
+    hipFree(b->d_ppj);
     hipFree(b->d_hm);
     if (b->h_th) hipHostFree(b->h_th);
     if (b->h_up) hipHostFree(b->h_up);
@@ -2795,6 +2806,140 @@ int og_adjoint_parameter_batch(og_batch b, int32_t count, const double* X, const
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
     rc = og_adjoint_parameter_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_S, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(S, d_S, sizeof(double) * c * out, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+// ---- exact second derivatives of w . F in the run-time parameters, the theta-theta block (include/ogpsx.h) ----
+static int parameter_hessian_check(const og_problem_s* p, const char* who) {
+    if (p->n_par == 0) return fail(1, std::string(who) + ": the module has no run-time parameters");
+    if (!p->pp_launch)
+        return fail(4, std::string(who) + ": the module's parameter-Hessian part is not loaded (og_parameter_hessian_load)");
+    return 0;
+}
+
+// (one launch: the chunks of weight vectors are a grid dimension, the lanes of a batch another)
+static int parameter_hessian_count_check(int32_t kw, const char* who) {
+    if (kw < 1) return fail(1, std::string(who) + ": kw must be at least 1");
+    if (kw > OG_MAX_WEIGHT_VECTORS)
+        return fail(1, std::string(who) + ": kw " + std::to_string(kw) + " exceeds " +
+                           std::to_string(OG_MAX_WEIGHT_VECTORS) + " weight vectors of one call");
+    return 0;
+}
+
+int og_parameter_hessian_load(og_handle p, const char* pp_part_path) {
+    if (!p) return fail(1, "og_parameter_hessian_load: null handle");
+    if (p->n_par == 0) return fail(1, "og_parameter_hessian_load: the module has no run-time parameters");
+    if (p->pp_launch) return 0;
+    OG_HIP(hipSetDevice(p->device));
+    void* mod = nullptr;
+    ogk_launch_batch_fn batch_fn = nullptr;
+    int rc = load_module_part(p, pp_part_path, "og_parameter_hessian_load", "parameter-Hessian part", &mod, &batch_fn);
+    if (rc) return rc;
+    ogk_launch_fn fn = (ogk_launch_fn)dlsym(mod, "ogk_launch");
+    ogk_args probe;
+    memset(&probe, 0, sizeof probe);
+    // (another part of the same module passes the checks above: only the parameter-Hessian part knows the mode)
+    if (!fn || fn(&probe, OGK_PP, nullptr) != (int)hipErrorInvalidValue) {
+        dlclose(mod);
+        return fail(5, "og_parameter_hessian_load: the parameter-Hessian part does not belong to the handle's module");
+    }
+    p->pp_module = mod;
+    p->pp_launch = fn;
+    p->pp_launch_batch = batch_fn;
+    return 0;
+}
+
+int og_parameter_hessian_dev(og_handle p, const double* d_x, int32_t kw, const double* d_W, double* d_S, double* d_F0,
+                             void* hip_stream) {
+    if (!p || !d_x || !d_W || !d_S) return fail(1, "og_parameter_hessian_dev: null argument");
+    int rc = parameter_hessian_check(p, "og_parameter_hessian_dev");
+    if (!rc) rc = parameter_hessian_count_check(kw, "og_parameter_hessian_dev");
+    if (rc) return rc;
+    ogk_args a;
+    p->flag_slot ^= 1;
+    // (as og_adjoint_parameter_dev: no J_T among the arguments, the weight vectors in the step pointer and their number
+    // as a column range)
+    fill_args(p, &a, d_x, d_W, d_F0 ? d_F0 : p->d_f0, nullptr, 0, kw);
+    p->nf_read = a.nonfinite;
+    rc = clear_count_in_a_capture(a.nonfinite, hip_stream);
+    if (rc) return rc;
+    rc = p->launch(&a, OGK_EVAL, hip_stream);       // F(x0) and the base collocation products
+    a.jt = d_S;
+    if (!rc) rc = p->pp_launch(&a, OGK_PP, hip_stream);
+    return launched(rc, "og_parameter_hessian_dev");
+}
+
+int og_parameter_hessian(og_handle p, const double* x, int32_t kw, const double* W, double* S, double* F0) {
+    if (!p || !x || !W || !S) return fail(1, "og_parameter_hessian: null argument");
+    int rc = parameter_hessian_check(p, "og_parameter_hessian");
+    if (!rc) rc = parameter_hessian_count_check(kw, "og_parameter_hessian");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t m = (size_t)p->m, kk = (size_t)kw, out = (size_t)p->n_par * (size_t)p->n_par;
+    if (kk > p->pp_capacity) {
+        if (p->d_pp) OG_HIP(hipFree(p->d_pp));
+        p->d_pp = nullptr;
+        p->pp_capacity = 0;
+        OG_HIP(hipMalloc(&p->d_pp, sizeof(double) * kk * (m + out)));
+        p->pp_capacity = kk;
+    }
+    double *d_W = p->d_pp, *d_S = d_W + kk * m;
+    rc = upload_point(p, x, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * kk * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_parameter_hessian_dev(p, p->d_x, kw, d_W, d_S, p->d_f0, p->stream);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(S, d_S, sizeof(double) * kk * out, hipMemcpyDeviceToHost, p->stream));
+    if (F0) OG_HIP(hipMemcpyAsync(F0, p->d_f0, sizeof(double) * m, hipMemcpyDeviceToHost, p->stream));
+    OG_HIP(hipStreamSynchronize(p->stream));
+    return 0;
+}
+
+int og_parameter_hessian_batch_dev(og_batch b, int32_t count, const double* d_X, const double* d_W, double* d_F0,
+                                   double* d_S, void* hip_stream) {
+    int rc = batch_check(b, count, "og_parameter_hessian_batch_dev");
+    if (rc) return rc;
+    if (!d_X || !d_W || !d_S) return fail(1, "og_parameter_hessian_batch_dev: null argument");
+    og_problem_s* p = b->p;
+    rc = parameter_hessian_check(p, "og_parameter_hessian_batch_dev");
+    if (!rc && count > OG_MAX_WEIGHT_VECTORS)
+        rc = fail(1, "og_parameter_hessian_batch_dev: count " + std::to_string(count) + " exceeds " +
+                         std::to_string(OG_MAX_WEIGHT_VECTORS) + " lanes of one call");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // record set 1, as og_adjoint_parameter_batch_dev: the records learn X and F0 only, the weight vectors [count][m] and
+    // the result [count][n_par][n_par] are arguments of the launch itself
+    rc = batch_bind(b, count, d_X, nullptr, d_F0 ? d_F0 : b->d_f, nullptr, 1, s, "og_parameter_hessian_batch_dev");
+    if (rc) return rc;
+    rc = batch_run(b, 1, OGK_BATCH_EVAL, count, s);
+    if (!rc) {
+        ogk_batch_args ba = batch_args(b, 1, count);
+        ba.H = d_W, ba.vals = d_S, ba.nnz = (int64_t)p->n_par * (int64_t)p->n_par;
+        rc = p->pp_launch_batch(&ba, OGK_BATCH_PP, s);
+    }
+    return launched(rc, "og_parameter_hessian_batch_dev");
+}
+
+int og_parameter_hessian_batch(og_batch b, int32_t count, const double* X, const double* W, double* F0, double* S) {
+    int rc = batch_check(b, count, "og_parameter_hessian_batch");
+    if (rc) return rc;
+    if (!X || !W || !S) return fail(1, "og_parameter_hessian_batch: null argument");
+    og_problem_s* p = b->p;
+    rc = parameter_hessian_check(p, "og_parameter_hessian_batch");
+    if (rc) return rc;
+    OG_HIP(hipSetDevice(p->device));
+    const size_t m = (size_t)p->m, c = (size_t)count, cap = (size_t)b->capacity;
+    const size_t out = (size_t)p->n_par * (size_t)p->n_par;
+    if (!b->d_ppj) OG_HIP(hipMalloc(&b->d_ppj, sizeof(double) * cap * (m + out)));
+    double *d_W = b->d_ppj, *d_S = b->d_ppj + cap * m;
+    rc = batch_upload(b, c, X, nullptr);
+    if (rc) return rc;
+    OG_HIP(hipMemcpyAsync(d_W, W, sizeof(double) * c * m, hipMemcpyHostToDevice, p->stream));
+    rc = og_parameter_hessian_batch_dev(b, count, b->d_xh, d_W, b->d_f, d_S, p->stream);
     if (rc) return rc;
     OG_HIP(hipMemcpyAsync(S, d_S, sizeof(double) * c * out, hipMemcpyDeviceToHost, p->stream));
     if (F0) OG_HIP(hipMemcpyAsync(F0, b->d_f, sizeof(double) * c * m, hipMemcpyDeviceToHost, p->stream));

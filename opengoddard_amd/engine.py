@@ -368,6 +368,42 @@ class HipEngine:
         _native.check(self._lib.og_adjoint_parameter_dev(self._handle, d_x, int(k), d_W, d_S, d_F0, stream),
                       "og_adjoint_parameter_dev")
 
+    # ------------------------------------------------------------------ exact d2(w . F)/dtheta2
+    def _load_pp_part(self):
+        """The module's parameter-Hessian part (``build.build_pp_part``): compiled by the first parameter-Hessian call,
+        loaded once per handle (``og_parameter_hessian_load``)."""
+        if self.n_par == 0:
+            raise ValueError("this problem declares no parameter")
+        if getattr(self, "pp_part_path", None) is None:
+            path = build.build_pp_part(self.header)
+            _native.check(self._lib.og_parameter_hessian_load(self._handle, path.encode()), "og_parameter_hessian_load")
+            self.pp_part_path = path
+
+    def parameter_hessian(self, x, W):
+        """``(S, F0)``: ``S[d, k, l] = sum_r W[d, r] d2F_r/dtheta_k dtheta_l``, ``[K, n_par, n_par]``, the EXACT second
+        derivatives of ``W[d] . F`` in the run-time parameters at ``x`` and the parameters on the device, for each of
+        the ``K`` weight vectors ``W[d]`` (``[K, m]``, over the rows of ``F``) (``og_parameter_hessian``: an evaluation
+        and one launch, a workgroup per pair ``k <= l`` and chunk of 8 vectors; second-order dual numbers with one seed
+        on each parameter of the pair, the order of every sum fixed - csrc/og_pp.h), and ``F0 = F(x)``.  Symmetric by
+        construction.  With ``devices=[...]`` the first device's handle serves it; the call is not split."""
+        self._load_pp_part()
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        assert x.shape == (self.n,)
+        if W.ndim != 2 or W.shape[1] != self.m or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, %d] with K >= 1, got %s" % (self.m, W.shape))
+        S, F0 = np.empty((W.shape[0], self.n_par, self.n_par)), np.empty(self.m)
+        _native.check(self._lib.og_parameter_hessian(self._handle, _native.dptr(x), W.shape[0], _native.dptr(W),
+                                                     _native.dptr(S), _native.dptr(F0)), "og_parameter_hessian")
+        return S, F0
+
+    def parameter_hessian_dev(self, d_x, k, d_W, d_S, d_F0=None, stream=0):
+        """``og_parameter_hessian_dev``: ints from ``torch.Tensor.data_ptr()``; ``d_W`` ``[k, m]``, ``d_S``
+        ``[k, n_par, n_par]``, ``d_F0`` ``[m]`` or None; asynchronous on ``stream``, capturable."""
+        self._load_pp_part()
+        _native.check(self._lib.og_parameter_hessian_dev(self._handle, d_x, int(k), d_W, d_S, d_F0, stream),
+                      "og_parameter_hessian_dev")
+
     # ------------------------------------------------------------------ batches
     def batch(self, capacity):
         """``capacity`` lanes of this problem that are evaluated / swept together, one launch per call
@@ -814,6 +850,34 @@ class BatchSweep:
         self.engine._load_mix_part()
         _native.check(self._lib.og_adjoint_parameter_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_S, stream),
                       "og_adjoint_parameter_batch_dev")
+
+    def parameter_hessian(self, X, W, count=None):
+        """``(S[B, n_par, n_par], F0[B, m])``: lane ``k``'s exact second derivatives of ``W[k] . F`` in the parameters at
+        ``X[k]`` - one weight vector (``m`` entries) per lane, at the lane's own parameters (:meth:`set_parameters`) -
+        bit for bit :meth:`HipEngine.parameter_hessian` at that point, vector and those values
+        (``og_parameter_hessian_batch``; three launches whatever ``B`` is).  ``count``: only the first ``count`` rows
+        (default: all).  No lane's J_T is written."""
+        X = self._points(X, "X")
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        if W.ndim != 2 or W.shape[1] != self.m:
+            raise ValueError("BatchSweep: W must have shape [B, %d], got %s" % (self.m, W.shape))
+        if W.shape[0] != X.shape[0]:
+            raise ValueError("BatchSweep: %d weight vectors for %d points" % (W.shape[0], X.shape[0]))
+        B = X.shape[0] if count is None else int(count)
+        if not 1 <= B <= X.shape[0]:
+            raise ValueError("BatchSweep: count %d for %d points" % (B, X.shape[0]))
+        self.engine._load_pp_part()
+        S, F0 = np.empty((B, self.engine.n_par, self.engine.n_par)), np.empty((B, self.m))
+        _native.check(self._lib.og_parameter_hessian_batch(self._handle, B, _native.dptr(X), _native.dptr(W),
+                                                           _native.dptr(F0), _native.dptr(S)), "og_parameter_hessian_batch")
+        return S, F0
+
+    def parameter_hessian_dev(self, count, d_X, d_W, d_S, d_F0=None, stream=0):
+        """``og_parameter_hessian_batch_dev``: ``d_X`` ``[count, n]``, ``d_W`` ``[count, m]``, ``d_S``
+        ``[count, n_par, n_par]``, ``d_F0`` ``[count, m]`` or None."""
+        self.engine._load_pp_part()
+        _native.check(self._lib.og_parameter_hessian_batch_dev(self._handle, int(count), d_X, d_W, d_F0, d_S, stream),
+                      "og_parameter_hessian_batch_dev")
 
     def sweep(self, P, H, persistent=False):
         """``(F0[B, m], vals[B, nnz], nonfinite[B])`` for the points ``P`` and the signed steps ``H`` (both ``[B, n]``):

@@ -110,6 +110,7 @@ class BatchResult:
         self.adjoint = None             # [B, n]: exact F'(x_k)^T w_k (evaluate_batch(adjoints=W))
         self.hessian_product = None     # [B, n]: exact grad^2 (w_k . F)(x_k) v_k (evaluate_batch(hessian_products=(W, V)))
         self.adjoint_parameter = None   # [B, n_par, n]: exact d(F'(x_k)^T w_k)/dtheta (evaluate_batch(adjoint_parameter=W))
+        self.parameter_hessian = None   # [B, n_par, n_par]: exact d2(w_k . F)(x_k)/dtheta2 (evaluate_batch(parameter_hessians=W))
         self.hessian = None             # [B, nnz]: exact sparse Hessian of w_k . F at x_k (evaluate_batch(hessians=W))
         self.hessian_pattern = None     # (indptr, cols) of it: the lower triangle in CSR form
 
@@ -873,9 +874,39 @@ class Problem:
         S = np.array(engine.adjoint_parameter(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
         return S[0] if single else S
 
+    def parameter_hessian(self, obj, weights, p=None):
+        """``S_kl = sum_r w_r d2F_r/dtheta_k dtheta_l``, the second derivatives of ``w . F`` in the declared run-time
+        parameters, ``F = [cost | c_eq | c_ineq]``, at the decision vector ``p`` (default ``prob.p``) and the current
+        parameter values, EXACT (``HipEngine.parameter_hessian``: an evaluation and one launch for all ``K`` weight
+        vectors and all pairs; second-order dual numbers with one seed on each parameter of a pair, no step in ``theta``
+        and no ``set_parameters`` launch).  ``weights``: ``[K, m]`` over the rows of ``F`` -> ``[K, n_par, n_par]``, or
+        one vector -> ``[n_par, n_par]``.  With ``w = [1, lambda]`` it is ``d2L/dtheta2``: the block of the Hessian of
+        the Lagrangian in ``(x, theta)`` next to :meth:`hessian_vector_product` / :meth:`hessian_matrix` (``xx``) and
+        :meth:`adjoint_parameter_sensitivity` (``x theta``); with ``x`` held fixed the exact Hessian in ``theta``.  The
+        order of every sum is :meth:`adjoint_product`'s, so the result is reproducible to the bit; it is symmetric by
+        construction, and a parameter nothing reads gets a row and a column of ``+0.0``.  A problem that declares no
+        parameter, an engine without ``parameter_hessian`` and a weight vector of the wrong length are ``ValueError``s."""
+        W = np.asarray(weights, dtype=float)
+        single = W.ndim == 1
+        if single:
+            W = W[None, :]
+        if W.ndim != 2 or W.shape[0] < 1:
+            raise ValueError("weights must have shape [K, m] or [m], got shape %s" % (np.shape(weights),))
+        if not self._par_names:
+            raise ValueError("this problem declares no parameter")
+        engine = self._batch_engine(obj)
+        if not hasattr(engine, "parameter_hessian"):
+            raise ValueError("this engine has no exact parameter Hessian (it has no parameter_hessian)")
+        point = np.asarray(self.p if p is None else p, dtype=float).reshape(-1)
+        m = self._rows_of(engine, point)
+        if W.shape[1] != m:
+            raise ValueError("weights must have %d entries (the rows of F) each, got shape %s" % (m, np.shape(weights)))
+        S = np.array(engine.parameter_hessian(point, np.ascontiguousarray(W))[0], dtype=float, copy=True)
+        return S[0] if single else S
+
     # ------------------------------------------------------------------ many points at once
     def evaluate_batch(self, obj, points, jacobian=False, parameters=None, parameter_jacobian=False, directions=None,
-                       adjoints=None, hessian_products=None, adjoint_parameter=None, hessians=None):
+                       adjoints=None, hessian_products=None, adjoint_parameter=None, hessians=None, parameter_hessians=None):
         """Cost, constraints and constraint violation of ``B`` decision vectors in one GPU launch - screening initial
         guesses before a solve, a dispersed family of trajectories around a solution, a parameter scan.  ``points`` has
         shape ``[B, number_of_variables]`` in the layout of ``Problem.p`` (scaled by the canonical units);
@@ -943,8 +974,17 @@ class Problem:
         ``hessian_pattern``, without them: ``ValueError``).  A point with its own row of ``parameters`` is
         differentiated at those values; one point scanned over ``parameters`` takes its one vector along.  It combines
         with every other keyword.  ``None``: nothing is computed and the call builds, loads and launches exactly what it
-        does without the keyword."""
-        if (parameter_jacobian or adjoint_parameter is not None) and not self._par_names:
+        does without the keyword.
+
+        ``parameter_hessians=W`` (``[B, m]``, one weight vector over the rows of ``F`` per row of ``points``) adds
+        ``BatchResult.parameter_hessian``, ``[B, n_par, n_par]``: the EXACT second derivatives of ``w_k . F`` in the
+        declared parameters at every point with its own vector (``BatchSweep.parameter_hessian``; a stand-in engine is
+        served point by point through its ``parameter_hessian``, without one: ``ValueError``).  A point with its own
+        row of ``parameters`` is differentiated at those values; one point scanned over ``parameters`` takes its one
+        vector along.  It combines with every other keyword; a problem without parameters is a ``ValueError``.
+        ``None``: nothing is computed and the call builds, loads and launches exactly what it does without the
+        keyword."""
+        if (parameter_jacobian or adjoint_parameter is not None or parameter_hessians is not None) and not self._par_names:
             raise ValueError("this problem declares no parameter")
         points = np.asarray(points, dtype=float)
         if directions is not None:
@@ -967,6 +1007,13 @@ class Problem:
                 raise ValueError("adjoint_parameter must have shape [B, m] (the rows of F), got %s" % (mix_w.shape,))
             if points.ndim == 2 and mix_w.shape[0] != points.shape[0]:
                 raise ValueError("adjoint_parameter holds %d rows for %d points" % (mix_w.shape[0], points.shape[0]))
+        pp_w = None
+        if parameter_hessians is not None:
+            pp_w = np.asarray(parameter_hessians, dtype=float)
+            if pp_w.ndim != 2:
+                raise ValueError("parameter_hessians must have shape [B, m] (the rows of F), got %s" % (pp_w.shape,))
+            if points.ndim == 2 and pp_w.shape[0] != points.shape[0]:
+                raise ValueError("parameter_hessians holds %d rows for %d points" % (pp_w.shape[0], points.shape[0]))
         full_w = None
         if hessians is not None:
             full_w = np.asarray(hessians, dtype=float)
@@ -1013,6 +1060,8 @@ class Problem:
                 mix_w = np.repeat(mix_w, TH.shape[0], axis=0)
             if full_w is not None:
                 full_w = np.repeat(full_w, TH.shape[0], axis=0)
+            if pp_w is not None:
+                pp_w = np.repeat(pp_w, TH.shape[0], axis=0)
         points = np.ascontiguousarray(points)
         if directions is not None:
             directions = np.ascontiguousarray(directions)
@@ -1039,6 +1088,13 @@ class Problem:
             m_rows = self._rows_of(engine, points[0])
             if mix_w.shape[1] != m_rows:
                 raise ValueError("adjoint_parameter must have shape [B, %d] (the rows of F), got %s" % (m_rows, mix_w.shape))
+        if pp_w is not None:
+            if not hasattr(engine, "parameter_hessian"):
+                raise ValueError("this engine has no exact parameter Hessian (it has no parameter_hessian)")
+            pp_w = np.ascontiguousarray(pp_w)
+            m_rows = self._rows_of(engine, points[0])
+            if pp_w.shape[1] != m_rows:
+                raise ValueError("parameter_hessians must have shape [B, %d] (the rows of F), got %s" % (m_rows, pp_w.shape))
         if full_w is not None:
             if not hasattr(engine, "hessian_matrix") or not hasattr(engine, "hessian_pattern"):
                 raise ValueError("this engine has no exact sparse Hessian (it has no hessian_matrix / hessian_pattern)")
@@ -1066,7 +1122,7 @@ class Problem:
                         engine.set_parameters(TH[k])
                     yield p
             saved = self.p
-            par_jac = along = back = curv = mixed = full = None
+            par_jac = along = back = curv = mixed = full = second = None
             try:
                 if full_w is not None:
                     full = np.stack([np.array(engine.hessian_matrix(p, full_w[k:k + 1])[0], dtype=float).reshape(-1)
@@ -1085,13 +1141,16 @@ class Problem:
                 if mix_w is not None:
                     mixed = np.stack([np.array(engine.adjoint_parameter(p, mix_w[k:k + 1])[0], dtype=float)[0]
                                       for k, p in enumerate(lanes())])
+                if pp_w is not None:
+                    second = np.stack([np.array(engine.parameter_hessian(p, pp_w[k:k + 1])[0], dtype=float)[0]
+                                       for k, p in enumerate(lanes())])
                 if not jacobian:
                     rows = [np.concatenate([np.atleast_1d(np.asarray(v, dtype=float)) for v in engine.values(p)])
                             for p in lanes()]
                     # (m_eq from the LAST point: the engine is at the last lane's parameters now, its cached values serve)
                     res = BatchResult(np.stack(rows), int(np.atleast_1d(engine.values(points[-1])[1]).size))
                     res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-                    res.hessian_product, res.adjoint_parameter = curv, mixed
+                    res.hessian_product, res.adjoint_parameter, res.parameter_hessian = curv, mixed, second
                     if full is not None:
                         res.hessian, res.hessian_pattern = full, engine.hessian_pattern()
                     return res
@@ -1115,7 +1174,7 @@ class Problem:
                     engine.set_parameters(list(self._par_values))      # (the engine goes back to the current values)
             res = BatchResult(np.stack(rows), m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-            res.hessian_product, res.adjoint_parameter = curv, mixed
+            res.hessian_product, res.adjoint_parameter, res.parameter_hessian = curv, mixed, second
             if full is not None:
                 res.hessian, res.hessian_pattern = full, engine.hessian_pattern()
             m = rows[0].size
@@ -1160,6 +1219,11 @@ class Problem:
             if not hasattr(batch, "adjoint_parameter"):
                 raise ValueError("this engine has no exact mixed derivative (its batch has no adjoint_parameter)")
             mixed = batch.adjoint_parameter(points, mix_w)[0]
+        second = None
+        if pp_w is not None:
+            if not hasattr(batch, "parameter_hessian"):
+                raise ValueError("this engine has no exact parameter Hessian (its batch has no parameter_hessian)")
+            second = batch.parameter_hessian(points, pp_w)[0]
         full = full_pattern = None
         if full_w is not None:
             if not hasattr(batch, "hessian_matrix"):
@@ -1168,7 +1232,7 @@ class Problem:
         if not jacobian:
             res = BatchResult(batch.values(points), engine.m_eq)
             res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-            res.hessian_product, res.adjoint_parameter = curv, mixed
+            res.hessian_product, res.adjoint_parameter, res.parameter_hessian = curv, mixed, second
             res.hessian, res.hessian_pattern = full, full_pattern
             return res
         if jacobian == "exact":
@@ -1178,7 +1242,7 @@ class Problem:
             F0, vals, nonfinite, H = batch.jacobians(points, lb, ub)
         res = BatchResult(F0, engine.m_eq)
         res.parameters, res.parameter_jacobian, res.directional, res.adjoint = used, par_jac, along, back
-        res.hessian_product, res.adjoint_parameter = curv, mixed
+        res.hessian_product, res.adjoint_parameter, res.parameter_hessian = curv, mixed, second
         res.hessian, res.hessian_pattern = full, full_pattern
         indptr, rows = batch.pattern
         res.pattern, res.values, res.steps, res.jacobian = (indptr, rows), vals, H, jacobian
